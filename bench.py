@@ -13,10 +13,13 @@ already resident in HBM.  Prints one JSON line (rank 0).
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --env maze                     # config 3 / the Maze leg of config 5 (scripts/maze.sh:7)
     python bench.py --utd_sweep                    # U = 1, 4, 16, 64 updates per lock-step iteration
+    python bench.py --full                         # + secondary legs, per-kernel rooflines, planner, CPU baseline
+    python bench.py --steps K --dump-outputs DIR   # + what the last timed step computed, as DIR/<name>.npy
 
-Timing: W warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + synchronize; blocks are
-repeated until >= MIN_TIMED_S of timed work exists (a 20-step block is 6 ms -- too short to report on), the
-number of blocks is agreed over ranks, and every figure is over all timed steps (max over ranks of the time).
+Timing: PREWARM_STEPS untimed steps (cold-box clocks), W warm-up steps, then ONE block of exactly K steps bracketed by
+barrier + synchronize (max over ranks of the time).  `--min_seconds S` repeats the block until >= S of timed work exists
+(the number of blocks is agreed over ranks).  A plain run does only the headline; whatever else the bench measures runs
+under --full.
 """
 import argparse
 import json
@@ -37,9 +40,12 @@ from recovery_rl_amd import runtime as rrl_runtime  # noqa: E402
 RUNTIME = rrl_runtime.configure(graph_packet_capture=rrl_runtime.LAUNCHER_GRAPH_PACKET_CAPTURE, log=False)
 
 NUM_ENVS = 4096
-MIN_TIMED_S = 3.0                # timed region of the headline leg (an external SMI sampler must be able to see it)
-PREWARM_S = 1.5       # untimed busy time before the warm-up steps of the headline run (cold-box clocks)
+MIN_TIMED_S = 3.0                # timed_blocks' default minimum; the U = 16 leg takes min(--min_seconds or this, MIN_TIMED_LEG_S)
+PREWARM_S = 1.5       # untimed busy time before the warm-up steps of a secondary leg (cold-box clocks)
+PREWARM_STEPS = 10000  # ... of the headline run: a fixed count (~1.5 s), so the timed steps' inputs depend on the arguments alone
 MIN_TIMED_LEG_S = 1.0            # ... of the secondary legs (U = 16, config 4)
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+DUMP_REPLAY_ROWS = 1 << 16       # ... of which a fixed, seeded sample of each replay ring's rows
 HBM_PEAK_GBS = 8000.0            # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 achievable
 NAV_STEP_ALGO_BYTES = 39         # algorithmic bytes per env-step (f32 contract)
 STEP_PUSH_ALGO_BYTES = 39 + 32 + 32   # + one 32-byte replay row into each of the two buffers (section 8d "replay")
@@ -213,6 +219,58 @@ def device_update_counts(loop):
     if fast is None:
         return None
     return int(fast.critic.step[0].item()), int(fast.qrisk.step[0].item())
+
+
+def step_outputs(loop, replay_rows=DUMP_REPLAY_ROWS):
+    """What the loop's last iteration handed its caller, by name: the env state it stepped to (observation, f64 position,
+    status word), the executed action and recovery mask, the counters and reward sums, every network's parameters and the
+    losses after the updates, and a fixed, seeded sample of the rows of both replay rings (index draws from a generator
+    seeded with 0, over the filled part of each ring)."""
+    import torch
+    env = loop.env
+    out = {"obs": loop.obs, "pos": env.pos, "real_action": getattr(loop, "_last_real_action", None),
+           "recovery": getattr(loop, "_last_recovery", None), "ep_reward": loop.ep_reward, "stats": loop.stats,
+           "reward_sums": loop.reward_sums}
+    out["env_status" if getattr(env, "_status_live", False) else "env_t"] = \
+        (env.status.to(torch.int32) & 0xFFFF) if getattr(env, "_status_live", False) else env.t
+    fast = getattr(loop.agent, "fast", None)
+    if fast is not None:
+        for name in ("critic", "critic_target", "policy", "qrisk", "qrisk_target", "recpolicy"):
+            out["params_" + name] = getattr(fast, name).flat
+        out["losses"] = fast.losses
+    else:
+        qr = loop.agent.safety_critic
+        nets = {"critic": loop.agent.critic, "critic_target": loop.agent.critic_target, "policy": loop.agent.policy,
+                "qrisk": qr.safety_critic, "qrisk_target": qr.safety_critic_target, "recpolicy": qr.policy}
+        for name, net in nets.items():
+            out["params_" + name] = torch.cat([p.detach().reshape(-1) for p in net.parameters()])
+    g = torch.Generator(device="cpu")
+    g.manual_seed(0)
+    for tag, mem in (("replay", loop.memory), ("constraint_replay", loop.recovery_memory)):
+        size = int(mem.state[1].item())
+        if size == 0:
+            continue
+        idx = torch.randint(0, size, (replay_rows,), generator=g).sort().values.to(mem.s.device)
+        for field in ("s", "a", "r", "s2", "m"):
+            out["%s_%s" % (tag, field)] = getattr(mem, field).index_select(0, idx)
+    return {k: v for k, v in out.items() if v is not None}
+
+
+def write_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES):
+    """Write every array as out_dir/<name>.npy: float32 and float64 as they are, other dtypes (counters, masks, status words)
+    as float64, which holds them exactly.  Refuses to write more than `limit` bytes in all.  Returns the names written."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        x = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        host[name] = np.ascontiguousarray(x if x.dtype in (np.float32, np.float64) else x.astype(np.float64))
+    total = sum(x.nbytes for x in host.values())
+    if total > limit:
+        raise ValueError("--dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, limit))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+    return sorted(host)
 
 
 def timed_blocks(step, steps, world, device, min_seconds=MIN_TIMED_S, max_blocks=100000):
@@ -728,8 +786,10 @@ def cpu_baseline(budget_s=24.0):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-def run_config(a, cfg, device, world, rank, updates_per_step=1, min_seconds=MIN_TIMED_S):
-    """Build the loop for `cfg`, capture, warm up, time.  Returns (result dict, loop)."""
+def run_config(a, cfg, device, world, rank, updates_per_step=1, min_seconds=MIN_TIMED_S, prewarm_steps=None):
+    """Build the loop for `cfg`, capture, warm up, time.  Returns (result dict, loop).  prewarm_steps: a fixed number of
+    untimed steps before the warm-up (the headline: what the timed steps start from is then a function of the arguments);
+    None = PREWARM_S seconds of them when min_seconds > 0."""
     import torch
     from recovery_rl_amd import distributed as dist_utils
     loop = build_loop(cfg, device, fast=not a.autograd_updates)
@@ -739,8 +799,13 @@ def run_config(a, cfg, device, world, rank, updates_per_step=1, min_seconds=MIN_
         loop.capture(online_qrisk=True)
     # untimed: bring a cold box to its working clocks (the first process on a fresh box measured 0.197 ms per iteration for
     # three seconds, the same command a minute later 0.187), then the W warm-up steps the caller asked for
+    if prewarm_steps is not None:
+        for k in range(0, prewarm_steps, 50):
+            for _ in range(min(50, prewarm_steps - k)):
+                step()
+            torch.cuda.synchronize(device)
     t_pre = time.perf_counter()
-    while min_seconds > 0 and time.perf_counter() - t_pre < PREWARM_S:
+    while prewarm_steps is None and min_seconds > 0 and time.perf_counter() - t_pre < PREWARM_S:
         for _ in range(50):
             step()
         torch.cuda.synchronize(device)
@@ -808,7 +873,7 @@ def run_config_packed(a, device, world, rank, S, updates_per_step=1, min_seconds
                "adam_steps_per_seed": [y[0] - x[0] for x, y in zip(c0, c1)],
                "launches_per_packed_iteration": packed.launches}
     return {"elapsed": elapsed, "blocks": blocks, "steps_total": n_steps, "agg": agg, "device_counters": True,
-            "seed_pack": witness}, loops[0]
+            "seed_pack": witness, "loops": loops}, loops[0]
 
 
 def run_seed_pack_leg(a, device, seeds=(1, 2, 4, 8), min_seconds=MIN_TIMED_LEG_S, updates_per_step=1):
@@ -942,21 +1007,32 @@ def main():
     ap.add_argument("--log_every", type=int, default=LOG_EVERY,
                     help="iterations between the driver's log points inside the timed region (counters read, episode table "
                          "drained); 0 = never (what the GPU-side iteration alone costs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the secondary legs, the per-kernel rooflines (step_push, stage table), the "
+                         "planner kernels on single-GPU runs and the CPU baseline (off: the headline only)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (env state, actions, counters, parameters, losses, a "
+                         "seeded sample of the replay rings) as DIR/<name>.npy, f32 / f64, <= 64 MB; identical arguments "
+                         "give identical inputs (with --min_seconds the block count, and so the inputs, depend on timing)")
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--planner", action="store_true",
                     help="time the fused planner kernel of config 4 (MFMA roofline) -> roofline_planner; "
-                         "on by default for single-GPU runs")
+                         "on by default for single-GPU runs under --full")
     ap.add_argument("--no_planner", action="store_true")
     ap.add_argument("--sweep", action="store_true",
                     help="also time rrl_nav_step / step_push at N = 2^12..2^24 (the bandwidth regime of the env kernels)")
-    ap.add_argument("--min_seconds", type=float, default=MIN_TIMED_S,
-                    help="timed blocks of --steps steps are repeated until this much timed work exists")
+    ap.add_argument("--min_seconds", type=float, default=None,
+                    help="repeat the timed block of --steps steps until this much timed work exists (default: one block, "
+                         "exactly --steps timed steps)")
     ap.add_argument("--no_legs", action="store_true",
-                    help="skip the secondary legs of a single-GPU run: U = 16 updates per iteration (UTD 1/256, the "
+                    help="skip the secondary legs of a --full single-GPU run: U = 16 updates per iteration (UTD 1/256, the "
                          "learning regime) and config 4 (Navigation2, model-based recovery, trained gate)")
     ap.add_argument("--autograd_updates", action="store_true",
                     help="PyTorch autograd + vendor GEMMs for the updates instead of the fused HIP kernels")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    min_seconds = a.min_seconds if a.min_seconds is not None else 0.0
 
     spawn, world_expected = resolve_world(a.gpus, os.environ)
     if spawn:
@@ -974,18 +1050,28 @@ def main():
     torch.cuda.set_device(device)
 
     U = a.updates_per_step
-    cfg = arg_utils.get_args(config_argv(a.env, dist_utils.rank_seed(1, rank), a.num_envs, U))
     S = max(1, a.seeds_per_gpu)
+    prewarm_steps = 0 if S > 1 else PREWARM_STEPS // 20 if a.no_graph else PREWARM_STEPS   # eager steps: ~20x longer
+    cfg = arg_utils.get_args(config_argv(a.env, dist_utils.rank_seed(1, rank), a.num_envs, U))
     if S > 1:
-        res, loop = run_config_packed(a, device, world, rank, S, U, min_seconds=a.min_seconds)
+        res, loop = run_config_packed(a, device, world, rank, S, U, min_seconds=min_seconds)
     else:
-        res, loop = run_config(a, cfg, device, world, rank, U, min_seconds=a.min_seconds)
+        res, loop = run_config(a, cfg, device, world, rank, U, min_seconds=min_seconds, prewarm_steps=prewarm_steps)
     elapsed, agg, n_steps = res["elapsed"], res["agg"], res["steps_total"]
+    loops = res.pop("loops", [loop])
+    if a.dump_outputs and rank == 0:
+        # what the last timed step left, before anything else runs on the device
+        arrays = step_outputs(loops[0]) if len(loops) == 1 else \
+            {"seed%d_%s" % (1 + k, name): x for k, l in enumerate(loops)
+             for name, x in step_outputs(l, max(1, DUMP_REPLAY_ROWS // len(loops))).items()}
+        write_outputs(arrays, a.dump_outputs)
+        del arrays
+    del loops
 
     extra = {}
     if S > 1:
         extra["seed_pack_headline"] = res["seed_pack"]
-    elif world > 1 and not a.no_legs and not a.no_graph:
+    elif world > 1 and a.full and not a.no_legs and not a.no_graph:
         # a multi-GPU node is best used with several seeds per GPU (the solo iteration is latency-bound): S = 4 on every rank
         del loop
         torch.cuda.empty_cache()
@@ -1016,14 +1102,15 @@ def main():
                           "qrisk_grad_steps_per_s": r["agg"]["qrisk_updates"] / r["elapsed"]})
         extra["utd_sweep"] = sweep
 
-    if world == 1 and not a.no_legs and not a.no_graph:
+    if world == 1 and a.full and not a.no_legs and not a.no_graph:
         import contextlib
         # the learning regime: 16 updates per lock-step iteration (UTD 1/256), same graph mechanism
         if U != 16:
             del loop
             torch.cuda.empty_cache()
             cfg_u = arg_utils.get_args(config_argv(a.env, dist_utils.rank_seed(1, rank), a.num_envs, 16))
-            r16, loop = run_config(a, cfg_u, device, world, rank, 16, min_seconds=min(a.min_seconds, MIN_TIMED_LEG_S))
+            leg_s = min(MIN_TIMED_S if a.min_seconds is None else a.min_seconds, MIN_TIMED_LEG_S)
+            r16, loop = run_config(a, cfg_u, device, world, rank, 16, min_seconds=leg_s)
             extra["utd_1_256"] = {
                 "updates_per_step": 16, "utd": "16/%d" % a.num_envs, "ms_per_step": r16["elapsed"] / r16["steps_total"] * 1e3,
                 "env_steps_per_s": r16["agg"]["env_steps"] / r16["elapsed"],
@@ -1050,7 +1137,7 @@ def main():
                     return {prec: run_config4_leg(device, prec) for prec in ("f32", "f16x3")}
             leg("config4", config4)
 
-    if rank == 0:
+    if rank == 0 and a.full:
         t_k = time_step_push_kernel(device, a.env, a.num_envs, log=True)
         gbs = a.num_envs * STEP_PUSH_ALGO_BYTES / t_k / 1e9
         traffic, traffic_src = committed_pmc("step_push_pmc", a.num_envs) if a.env == "navigation1" else (None, None)
@@ -1069,6 +1156,7 @@ def main():
             "note": "N=%d moves only %d KB per launch: latency-bound by construction; bandwidth regime "
                     "(N up to 2^24, `bench.py --sweep`): %s"
                     % (a.num_envs, a.num_envs * STEP_PUSH_ALGO_BYTES // 1024, latest_sweep())}
+    if rank == 0:
         if a.sweep:
             sweep, sweep_sp, sweep_c = [], [], []
             for logn in (12, 16, 20, 24):
@@ -1103,7 +1191,7 @@ def main():
                 "achieved_GBs": n_r * t_r * 13 / tr / 1e9, "frac": n_r * t_r * 13 / tr / 1e9 / HBM_PEAK_GBS,
                 "note": "8 B action read + 4 B reward + 1 B constraint written per env-step; the state never leaves "
                         "registers, so the f64 Philox / Box-Muller arithmetic, not HBM, is the limit"}
-        if (a.planner or world == 1) and not a.no_planner:
+        if (a.planner or (world == 1 and a.full)) and not a.no_planner:
             import contextlib
             with contextlib.redirect_stdout(sys.stderr):       # the controller announces itself: stdout carries the JSON line only
                 t_p, row_steps = time_planner_kernel(device)
@@ -1138,7 +1226,7 @@ def main():
                 "frac": f16 / t_h / 1e12 / F16_MFMA_PEAK_TF,
                 "note": "costs agree with the f32 kernel to < 2e-5 (tests/test_plan_gpu.py); the K=32 f16 MFMA shape sustains 2460 TF on "
                         "this pool (profiles/mfma_f16_rate.hip)"}
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             extra["cpu_baseline"] = cpu_baseline()
 
     if rank == 0:
@@ -1150,7 +1238,7 @@ def main():
             "value": env_rate, "unit": "env-steps/s", "n_gpus": world, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": elapsed / n_steps * 1e3, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "prewarm_seconds": PREWARM_S, "timed_blocks": res["blocks"], "timed_steps_total": n_steps, "timed_seconds": elapsed,
+            "prewarm_steps": prewarm_steps, "timed_blocks": res["blocks"], "timed_steps_total": n_steps, "timed_seconds": elapsed,
             "sac_grad_steps_per_s": agg["sac_updates"] / elapsed,
             "qrisk_grad_steps_per_s": agg["qrisk_updates"] / elapsed,
             "grad_step_witness": "device-side Adam step counters" if res["device_counters"] else "host counters",

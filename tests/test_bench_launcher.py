@@ -151,8 +151,8 @@ def test_bench_gpus_2_runs_two_ranks_and_reports_them(tmp_path):
     env = dict(os.environ, RRL_DIST_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-                          "--num_envs", "512", "--no_cpu_baseline", "--no_planner", "--no_legs", "--min_seconds", "0.5"],
-                         env=env, capture_output=True, text=True, timeout=600)
+                          "--num_envs", "512", "--no_cpu_baseline", "--no_planner", "--no_legs", "--min_seconds", "0.5",
+                          "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(line) == 1, out.stdout[-2000:]
@@ -311,13 +311,13 @@ def test_rrl_main_two_ranks_pack_consecutive_seeds(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_gpus_2_default_legs_add_the_packed_leg():
-    """What the driver's scaling run issues (`bench.py --gpus N --steps K --warmup W`, legs on): at N > 1 the line carries a second
+    """The scaling run with its legs on (`bench.py --gpus N --steps K --warmup W --full`): at N > 1 the line carries a second
     leg with S = 4 seeds packed per rank (`seed_pack_multi_gpu`) next to the one-seed-per-GPU headline.  Two gloo ranks on the
     box's GPU, small envs."""
     env = dict(os.environ, RRL_DIST_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-                          "--num_envs", "256", "--no_cpu_baseline", "--no_planner", "--min_seconds", "0.3"],
+                          "--num_envs", "256", "--no_cpu_baseline", "--no_planner", "--min_seconds", "0.3", "--full"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
