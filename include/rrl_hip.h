@@ -472,9 +472,13 @@ int rrl_mlp_hidden_backward(int G, int B, int H, const float* dh2, const float* 
  *                         (the backward of GaussianPolicy.sample, model.py:324-340)
  *   RRL_LOSS_STOCH_HEAD   (G=1,dout=2) out=raw, v0=eps, v1=log_std, v2=scale, f0=min_log_std, d_action...;
  *                         loss[2] = dlog_std                                            (model.py:511-525)
+ *   RRL_LOSS_DGD_QRISK    (G=2,dout=1) out=zp (Q_risk at (s, pi)), f0=nu; loss[1] = mean max sigmoid(zp): the Q_risk half of
+ *                         the Lagrangian policy loss nu (max sigmoid(zp) - eps_safe) of --DGD_constraints (sac.py:221-228),
+ *                         dOut = nu w_g / B q_g (1 - q_g) -- RRL_LOSS_QRISK_POLICY scaled by nu, a critic-loss kind
+ *                         wherever those are accepted (the paired launch included)
  * out / out_t take (n_part, part_stride) like the stand-alone kernels. */
 enum { RRL_LOSS_SAC_CRITIC = 0, RRL_LOSS_SAC_POLICY = 1, RRL_LOSS_QRISK_CRITIC = 2, RRL_LOSS_QRISK_POLICY = 3,
-       RRL_LOSS_GAUSS_HEAD = 4, RRL_LOSS_STOCH_HEAD = 5 };
+       RRL_LOSS_GAUSS_HEAD = 4, RRL_LOSS_STOCH_HEAD = 5, RRL_LOSS_DGD_QRISK = 6 };
 typedef struct {
     int kind;
     int n_part;
@@ -592,6 +596,10 @@ int rrl_mlp_backward_pair_multi(int n, const rrl_head_bwd_t* heads, const rrl_hi
  *   rrl_qrisk_critic_grad    target c + m gamma_safe max sigmoid(z') and d(mse1+mse2)/dz on PRE-sigmoid
  *                            outputs (recovery_rl/qrisk.py:118-148)
  *   rrl_qrisk_policy_grad    d mean(max sigmoid(z))/dz (qrisk.py:150-154)
+ *   rrl_dgd_qrisk_grad       nu times the same: the Q_risk half of the --DGD_constraints policy loss (sac.py:221-228)
+ *   rrl_rcpo_penalty         penalty[b] = lambda[0] max sigmoid(z[.][b]) for rrl_sac_critic_grad's `penalty` (--RCPO,
+ *                            sac.py:202-205; lambda read from device memory) and mean[0] = the batch mean of max sigmoid(z)
+ *                            (penalty = NULL: the mean only -- the nu step of --update_nu at (s, pi))
  *   rrl_stoch_head_fwd/bwd   StochasticPolicy.sample and its backward (model.py:511-525)
  *   rrl_adam_step            torch.optim.Adam step over one flat f32 buffer + optional Polyak update
  *                            of a target buffer (recovery_rl/utils.py:46-49); step_dev = uint64[2]
@@ -618,6 +626,10 @@ int rrl_qrisk_critic_grad(int B, const float* z, const float* zt, int n_part, lo
                           const float* c, const float* m, float gamma_safe, float* dz, float* loss, void* stream);
 int rrl_qrisk_policy_grad(int B, const float* zp, int n_part, long long part_stride, float* dzp, float* loss,
                           void* stream);
+int rrl_dgd_qrisk_grad(int B, const float* zp, int n_part, long long part_stride, float nu, float* dzp, float* loss,
+                       void* stream);
+int rrl_rcpo_penalty(int B, const float* z, int n_part, long long part_stride, const float* lambda, float* penalty,
+                     float* mean, void* stream);
 int rrl_stoch_head_fwd(int B, const float* raw, int n_part, long long part_stride, const float* eps,
                        const float* log_std, float min_log_std, const float* scale, const float* bias,
                        float* action, int ld_action, float* mean_out, void* stream);
@@ -654,6 +666,25 @@ typedef struct {
 } rrl_adam_seg_t;
 int rrl_adam_step_multi(int n_seg, const rrl_adam_seg_t* segs, float lr, float beta1, float beta2, float eps,
                         void* stream);
+/* The dual variables of the comparison algorithms (sac.py:256-271: log_nu of --update_nu, log_lambda of --RCPO) as members
+ * of the same launch: one torch.optim.Adam step (capturable; beta1, beta2, eps of the launch, lr of the member) of the 0-dim
+ * parameter log_p on the optimiser's own state tensors, gradient eps_safe - stat[0] (stat = the batch mean of max sigmoid(z)),
+ * then value[0] = exp(log_p) (SAC._set_dual).  log_p = NULL: no step.  loss_out (nullable): loss_out[0] = loss_in[0] +
+ * f_loss (stat[0] - eps_safe) -- the Lagrangian policy loss statistic of --DGD_constraints from its two halves, read from
+ * stat BEFORE anything of the launch writes.  n_dual <= RRL_ADAM_MAX_DUALS; n_seg may be 0. */
+#define RRL_ADAM_MAX_DUALS 4
+typedef struct {
+    float *log_p, *exp_avg, *exp_avg_sq, *step;
+    float* value;
+    const float* stat;
+    float eps_safe;
+    float lr;
+    const float* loss_in;
+    float* loss_out;
+    float f_loss;
+} rrl_dual_t;
+int rrl_adam_step_multi_duals(int n_seg, const rrl_adam_seg_t* segs, int n_dual, const rrl_dual_t* duals, float lr,
+                              float beta1, float beta2, float eps, void* stream);
 /* W2p = the G row-major [H, H] matrices W2 (out, in -- model.py's nn.Linear weights) in the order the forward kernels' MFMA B
  * operands consume them: W2p[g][n][j][q][i][c] = W2[g][16 n + i][16 j + 4 q + c] (n, j < H / 16; q, c < 4; i < 16), i.e. the float4
  * lane (i, q) of the wave that owns output columns 16 n .. 16 n + 15 needs for K chunk j sits at float4 index

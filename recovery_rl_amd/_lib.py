@@ -49,6 +49,7 @@ EXPORTS = [
     "rrl_mlp_input_backward_multi", "rrl_mlp_backward_pair_multi", "rrl_policy_heads_fwd_multi",
     "rrl_gauss_head_fwd", "rrl_gauss_head_bwd", "rrl_sac_critic_grad", "rrl_sac_policy_grad",
     "rrl_qrisk_critic_grad", "rrl_qrisk_policy_grad", "rrl_stoch_head_fwd", "rrl_stoch_head_bwd",
+    "rrl_dgd_qrisk_grad", "rrl_rcpo_penalty", "rrl_adam_step_multi_duals",
     "rrl_adam_step", "rrl_adam_step_multi", "rrl_w2_pack", "rrl_normal_fill", "rrl_recovery_select", "rrl_episode_log_append",
     "rrl_plan_supported", "rrl_plan_pack_floats", "rrl_plan_scratch_floats", "rrl_plan_pack", "rrl_plan_cost", "rrl_plan_pack_f16x3",
     "rrl_plan_cost_f16x3", "rrl_plan_cost_n",
@@ -143,7 +144,8 @@ class rrl_episode_log_t(C.Structure):
 
 EPLOG_I32 = 6
 ADAM_MAX_SEGS = 12
-LOSS_SAC_CRITIC, LOSS_SAC_POLICY, LOSS_QRISK_CRITIC, LOSS_QRISK_POLICY, LOSS_GAUSS_HEAD, LOSS_STOCH_HEAD = range(6)
+LOSS_SAC_CRITIC, LOSS_SAC_POLICY, LOSS_QRISK_CRITIC, LOSS_QRISK_POLICY, LOSS_GAUSS_HEAD, LOSS_STOCH_HEAD, LOSS_DGD_QRISK = range(7)
+ADAM_MAX_DUALS = 4
 
 
 class rrl_ens_t(C.Structure):
@@ -234,6 +236,12 @@ class rrl_adam_seg_t(C.Structure):
                 ("w2_heads", C.c_int)]
 
 
+class rrl_dual_t(C.Structure):
+    _fields_ = [("log_p", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("step", C.c_void_p),
+                ("value", C.c_void_p), ("stat", C.c_void_p), ("eps_safe", C.c_float), ("lr", C.c_float),
+                ("loss_in", C.c_void_p), ("loss_out", C.c_void_p), ("f_loss", C.c_float)]
+
+
 class rrl_plan_weights_t(C.Structure):
     _fields_ = [("hq", C.c_int), ("he", C.c_int), ("n_nets", C.c_int)] + [
         (name, C.c_void_p) for name in ("q_w1", "q_b1", "q_w2", "q_b2", "q_w3", "q_b3", "e_w0", "e_b0", "e_w1",
@@ -318,6 +326,9 @@ def _declare(lib):
         "rrl_sac_policy_grad": (ci, [ci, vp, ci, ll, vp, vp, vp, vp, vp]),
         "rrl_qrisk_critic_grad": (ci, [ci, vp, vp, ci, ll, vp, vp, f32, vp, vp, vp]),
         "rrl_qrisk_policy_grad": (ci, [ci, vp, ci, ll, vp, vp, vp]),
+        "rrl_dgd_qrisk_grad": (ci, [ci, vp, ci, ll, f32, vp, vp, vp]),
+        "rrl_rcpo_penalty": (ci, [ci, vp, ci, ll, vp, vp, vp, vp]),
+        "rrl_adam_step_multi_duals": (ci, [ci, C.POINTER(rrl_adam_seg_t), ci, C.POINTER(rrl_dual_t), f32, f32, f32, f32, vp]),
         "rrl_stoch_head_fwd": (ci, [ci, vp, ci, ll, vp, vp, f32, vp, vp, vp, ci, vp, vp]),
         "rrl_stoch_head_bwd": (ci, [ci, vp, ci, ll, vp, vp, f32, vp, vp, ci, ci, ll, vp, vp, vp]),
         "rrl_adam_step": (ci, [C.c_longlong, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp, f32, vp]),

@@ -107,6 +107,7 @@ def agent_state(agent):
         out["noise_tick"] = _cpu(agent.fast.noise_tick)
         out["actor_rows"] = agent.fast.actor_rows        # layout of the per-iteration noise fill
     out["optim"] = {k: o.state_dict() for k, o in _optimisers(agent).items()}
+    out["update_path"] = "fused" if agent.fast is not None else "autograd"
     return out
 
 
@@ -136,7 +137,8 @@ def load_agent_state(agent, sd):
         if learned[name]:                                   # the live exp(log) value the losses read
             agent._set_dual(name, log_param)
     if ("flat" in sd) != (agent.fast is not None):
-        raise ValueError("checkpoint and run disagree on the fused update path (--no_fast_path)")
+        raise ValueError("checkpoint and run disagree on the fused update path (--no_fast_path; the comparison "
+                         "algorithms take it under RRL_FAST_BASELINES=1 only)")
     if agent.fast is not None:
         for name in _FLAT_NETS:
             net = getattr(agent.fast, name)
@@ -237,7 +239,8 @@ def load_experiment_state(exp, sd):
         if not capacity_fits(sd[name], getattr(exp, name).capacity):
             raise _capacity_error(name, sd[name], getattr(exp, name).capacity)
     if ("flat" in sd["agent"]) != (exp.agent.fast is not None):
-        raise ValueError("checkpoint and run disagree on the fused update path (--no_fast_path)")
+        raise ValueError("checkpoint and run disagree on the fused update path (--no_fast_path; the comparison "
+                         "algorithms take it under RRL_FAST_BASELINES=1 only)")
     if ("mpc" in sd) != (exp.recovery_policy is not None):
         raise ValueError("checkpoint and run disagree on model-based recovery")
     load_agent_state(exp.agent, sd["agent"])

@@ -924,10 +924,12 @@ __device__ __forceinline__ float dout_at(const rrl_loss_t& a, int B, int g, int 
         term = e * e;
         return 2.f * e / B * q * (1.f - q);
     } else if constexpr (KIND == RRL_LOSS_QRISK_POLICY) {
+        // RRL_LOSS_DGD_QRISK runs on this instantiation: the same gradient times nu = f0 (1 for QRISK_POLICY: the same bits)
+        const float s = a.kind == RRL_LOSS_DGD_QRISK ? a.f0 : 1.f;
         const float q0 = sigm(psum(a.out, b, np, ps)), q1 = sigm(psum(a.out, B + b, np, ps));
         const float w0 = q0 > q1 ? 1.f : (q0 == q1 ? 0.5f : 0.f);
         if (g == 0) term = fmaxf(q0, q1);
-        return g == 0 ? w0 / B * q0 * (1.f - q0) : (1.f - w0) / B * q1 * (1.f - q1);
+        return g == 0 ? s * w0 / B * q0 * (1.f - q0) : s * (1.f - w0) / B * q1 * (1.f - q1);
     } else {
         static_assert(KIND == RRL_LOSS_QRISK_POLICY, "the policy-head kinds: head_in_load + gauss_head_eval / stoch_head_eval");
         return 0.f;
@@ -1180,7 +1182,8 @@ __device__ __forceinline__ void head_bwd_dispatch(const HeadBwdArgs& hb, int bx,
         case RRL_LOSS_SAC_CRITIC: head_bwd_loss_body<RRL_LOSS_SAC_CRITIC>(hb, bx, g, red, dsh); break;
         case RRL_LOSS_SAC_POLICY: head_bwd_loss_body<RRL_LOSS_SAC_POLICY>(hb, bx, g, red, dsh); break;
         case RRL_LOSS_QRISK_CRITIC: head_bwd_loss_body<RRL_LOSS_QRISK_CRITIC>(hb, bx, g, red, dsh); break;
-        case RRL_LOSS_QRISK_POLICY: head_bwd_loss_body<RRL_LOSS_QRISK_POLICY>(hb, bx, g, red, dsh); break;
+        case RRL_LOSS_QRISK_POLICY:
+        case RRL_LOSS_DGD_QRISK: head_bwd_loss_body<RRL_LOSS_QRISK_POLICY>(hb, bx, g, red, dsh); break;
         case RRL_LOSS_GAUSS_HEAD: head_bwd_loss_body<RRL_LOSS_GAUSS_HEAD>(hb, bx, g, red, dsh); break;
         case RRL_LOSS_STOCH_HEAD: head_bwd_loss_body<RRL_LOSS_STOCH_HEAD>(hb, bx, g, red, dsh); break;
         default: head_bwd_loss_body<kPlainDOut>(hb, bx, g, red, dsh); break;
@@ -1263,7 +1266,7 @@ __device__ __forceinline__ void pair_eval_dout(const rrl_loss_t& la, int B, int 
             case RRL_LOSS_SAC_CRITIC: eval_dout_rows<RRL_LOSS_SAC_CRITIC>(la, B, g, dsh, unused, b0, nb); break;
             case RRL_LOSS_SAC_POLICY: eval_dout_rows<RRL_LOSS_SAC_POLICY>(la, B, g, dsh, unused, b0, nb); break;
             case RRL_LOSS_QRISK_CRITIC: eval_dout_rows<RRL_LOSS_QRISK_CRITIC>(la, B, g, dsh, unused, b0, nb); break;
-            default: eval_dout_rows<RRL_LOSS_QRISK_POLICY>(la, B, g, dsh, unused, b0, nb); break;
+            default: eval_dout_rows<RRL_LOSS_QRISK_POLICY>(la, B, g, dsh, unused, b0, nb); break;   // (and DGD_QRISK)
         }
     }
 }
@@ -1298,7 +1301,7 @@ __device__ __forceinline__ void backward_pair_body(const PairJobs& pj, int x, fl
                 case RRL_LOSS_SAC_CRITIC: head_bwd_loss_body<RRL_LOSS_SAC_CRITIC>(hb, bx, g, red, smem + 1024); break;
                 case RRL_LOSS_SAC_POLICY: head_bwd_loss_body<RRL_LOSS_SAC_POLICY>(hb, bx, g, red, smem + 1024); break;
                 case RRL_LOSS_QRISK_CRITIC: head_bwd_loss_body<RRL_LOSS_QRISK_CRITIC>(hb, bx, g, red, smem + 1024); break;
-                default: head_bwd_loss_body<RRL_LOSS_QRISK_POLICY>(hb, bx, g, red, smem + 1024); break;
+                default: head_bwd_loss_body<RRL_LOSS_QRISK_POLICY>(hb, bx, g, red, smem + 1024); break;   // (and DGD_QRISK)
             }
         }
         return;
@@ -1410,7 +1413,7 @@ __global__ __launch_bounds__(256) void backward_pair_block_pack_kernel(const Pai
                 case RRL_LOSS_SAC_CRITIC: head_bwd_loss_body<RRL_LOSS_SAC_CRITIC>(hb, bx, g, red, smem + 1024); break;
                 case RRL_LOSS_SAC_POLICY: head_bwd_loss_body<RRL_LOSS_SAC_POLICY>(hb, bx, g, red, smem + 1024); break;
                 case RRL_LOSS_QRISK_CRITIC: head_bwd_loss_body<RRL_LOSS_QRISK_CRITIC>(hb, bx, g, red, smem + 1024); break;
-                default: head_bwd_loss_body<RRL_LOSS_QRISK_POLICY>(hb, bx, g, red, smem + 1024); break;
+                default: head_bwd_loss_body<RRL_LOSS_QRISK_POLICY>(hb, bx, g, red, smem + 1024); break;   // (and DGD_QRISK)
             }
         }
         return;
@@ -1789,9 +1792,10 @@ static int head_loss_args(const rrl_loss_t* la, int G, int B, int H, int dout, c
     if (!la || !la->out || !h2 || !W3) return RRL_EINVAL;          // dh2 == NULL: weight gradients and loss scalars only
     if (G <= 0 || B <= 0 || B > 1024 || H <= 0 || dout <= 0 || dout > 4) return RRL_ERANGE;
     if (la->kind != kPlainDOut) {
-        if (la->kind < 0 || la->kind > RRL_LOSS_STOCH_HEAD || la->n_part <= 0 || la->n_part > 4) return RRL_ERANGE;
-        const int heads = la->kind <= RRL_LOSS_QRISK_POLICY ? 2 : 1;
-        const int width = la->kind <= RRL_LOSS_QRISK_POLICY ? 1 : (la->kind == RRL_LOSS_GAUSS_HEAD ? 4 : 2);
+        if (la->kind < 0 || la->kind > RRL_LOSS_DGD_QRISK || la->n_part <= 0 || la->n_part > 4) return RRL_ERANGE;
+        const bool critic = la->kind <= RRL_LOSS_QRISK_POLICY || la->kind == RRL_LOSS_DGD_QRISK;
+        const int heads = critic ? 2 : 1;
+        const int width = critic ? 1 : (la->kind == RRL_LOSS_GAUSS_HEAD ? 4 : 2);
         if (G != heads || dout != width) return RRL_EINVAL;
         if (la->da_parts < 0 || la->da_parts > 16) return RRL_ERANGE;
         if ((la->da_group != 0 && la->da_group != 1 && la->da_group != 4) || (la->da_group == 4 && (la->da_parts & 3)))
@@ -1822,6 +1826,9 @@ int rrl_mlp_head_backward_loss(const rrl_loss_t* la, int G, int B, int H, int do
         RRL_LAUNCH_LOSS(RRL_LOSS_QRISK_POLICY)
         RRL_LAUNCH_LOSS(RRL_LOSS_GAUSS_HEAD)
         RRL_LAUNCH_LOSS(RRL_LOSS_STOCH_HEAD)
+        case RRL_LOSS_DGD_QRISK:
+            hipLaunchKernelGGL((head_bwd_loss_kernel<RRL_LOSS_QRISK_POLICY>), grid, block, 0, st, hb);
+            break;
         default:
             return RRL_EINVAL;
     }
@@ -1856,7 +1863,8 @@ static void launch_head_group(const HeadBwdGroup& hg, int n, hipStream_t st) {
             case RRL_LOSS_SAC_CRITIC: hipLaunchKernelGGL((head_bwd_loss_kernel<RRL_LOSS_SAC_CRITIC>), grid, block, 0, st, hb); return;
             case RRL_LOSS_SAC_POLICY: hipLaunchKernelGGL((head_bwd_loss_kernel<RRL_LOSS_SAC_POLICY>), grid, block, 0, st, hb); return;
             case RRL_LOSS_QRISK_CRITIC: hipLaunchKernelGGL((head_bwd_loss_kernel<RRL_LOSS_QRISK_CRITIC>), grid, block, 0, st, hb); return;
-            case RRL_LOSS_QRISK_POLICY: hipLaunchKernelGGL((head_bwd_loss_kernel<RRL_LOSS_QRISK_POLICY>), grid, block, 0, st, hb); return;
+            case RRL_LOSS_QRISK_POLICY:
+            case RRL_LOSS_DGD_QRISK: hipLaunchKernelGGL((head_bwd_loss_kernel<RRL_LOSS_QRISK_POLICY>), grid, block, 0, st, hb); return;
             case RRL_LOSS_GAUSS_HEAD: hipLaunchKernelGGL((head_bwd_loss_kernel<RRL_LOSS_GAUSS_HEAD>), grid, block, 0, st, hb); return;
             case RRL_LOSS_STOCH_HEAD: hipLaunchKernelGGL((head_bwd_loss_kernel<RRL_LOSS_STOCH_HEAD>), grid, block, 0, st, hb); return;
             default: break;
@@ -1899,7 +1907,7 @@ static int build_pair_jobs(int n, const rrl_head_bwd_t* heads, const rrl_hidden_
         const int nn_tiles = hd.per_head[k] - hd.tn_tiles[k];
         // every member of one launch has the same number of outputs (the kernel is compiled per DOUT): the critic-loss kinds
         // (1), the tanh-Gaussian head (4) or the stochastic head (2)
-        const int my = (kind >= RRL_LOSS_SAC_CRITIC && kind <= RRL_LOSS_QRISK_POLICY) ? 1
+        const int my = ((kind >= RRL_LOSS_SAC_CRITIC && kind <= RRL_LOSS_QRISK_POLICY) || kind == RRL_LOSS_DGD_QRISK) ? 1
                        : kind == RRL_LOSS_GAUSS_HEAD ? 4 : kind == RRL_LOSS_STOCH_HEAD ? 2 : 0;
         pair = my != 0 && (dout == 0 || dout == my) && h.dout == my && h.dh2 && h.dh2 == d.dh2 &&
                h.G == d.G && h.B == d.B && h.H == d.H && h.B * my <= kPairDsh && h.H <= 256 && hd.fast[k] &&

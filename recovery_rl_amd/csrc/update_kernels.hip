@@ -179,14 +179,15 @@ __global__ void qrisk_critic_grad_kernel(int B, const float* z, const float* zt,
 }
 
 // loss = mean(max(sigmoid(z1), sigmoid(z2))) (qrisk.py:150-154): dz on the larger head
-__global__ void qrisk_policy_grad_kernel(int B, const float* zp, int np, long long ps, float* dzp, float* loss) {
+// s = nu: the Q_risk half of the --DGD_constraints policy loss nu (max sigmoid(zp) - eps_safe) (sac.py:221-228); s = 1: the same bits
+__global__ void qrisk_policy_grad_kernel(int B, const float* zp, int np, long long ps, float s, float* dzp, float* loss) {
     __shared__ float red[kBlock];
     float l = 0.f;
     for (int b = threadIdx.x; b < B; b += kBlock) {
         const float q0 = sigmoidf(psum(zp, b, np, ps)), q1 = sigmoidf(psum(zp, B + b, np, ps));
         const float w0 = q0 > q1 ? 1.f : (q0 == q1 ? 0.5f : 0.f);
-        dzp[b] = w0 / B * q0 * (1.f - q0);
-        dzp[B + b] = (1.f - w0) / B * q1 * (1.f - q1);
+        dzp[b] = s * w0 / B * q0 * (1.f - q0);
+        dzp[B + b] = s * (1.f - w0) / B * q1 * (1.f - q1);
         l += fmaxf(q0, q1);
     }
     red[threadIdx.x] = l;
@@ -196,6 +197,29 @@ __global__ void qrisk_policy_grad_kernel(int B, const float* zp, int np, long lo
         __syncthreads();
     }
     if (threadIdx.x == 0 && loss) loss[0] = red[0] / B;
+}
+
+// ---- RCPO reward penalty (sac.py:202-205): penalty[b] = lambda max(sigmoid(z1), sigmoid(z2)) at the batch's own (s, a) ------
+// lambda is the live multiplier (read from device memory: the dual step of the same iteration writes it); mean[0] = the batch
+// mean of max sigmoid(z), the gradient's operand of the lambda step (sac.py:265-271).  penalty = NULL: the mean only (the nu
+// step of --update_nu without the Lagrangian term, at (s, pi))
+__global__ void rcpo_penalty_kernel(int B, const float* z, int np, long long ps, const float* lambda, float* penalty,
+                                    float* mean) {
+    __shared__ float red[kBlock];
+    const float lam = penalty ? lambda[0] : 0.f;
+    float l = 0.f;
+    for (int b = threadIdx.x; b < B; b += kBlock) {
+        const float q = fmaxf(sigmoidf(psum(z, b, np, ps)), sigmoidf(psum(z, B + b, np, ps)));
+        if (penalty) penalty[b] = lam * q;
+        l += q;
+    }
+    red[threadIdx.x] = l;
+    __syncthreads();
+    for (int off = kBlock / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && mean) mean[0] = red[0] / B;
 }
 
 // ---- model-free recovery policy head (StochasticPolicy, model.py:511-525) ------------------------
@@ -516,6 +540,50 @@ __global__ __launch_bounds__(kBlock) void adam_multi_kernel(AdamSegs a, int n_se
     adam_seg_body(sg, vec != 0, lr, b1, b2, eps, blockIdx.x, blocks, sh);
 }
 
+// the dual variables of the comparison algorithms (rrl_dual_t): one thread per member, torch.optim.Adam's capturable step on
+// a 0-dim parameter (sac.py:256-271) -- the arithmetic of adam_elem, the bias corrections in double as in adam_seg_body
+struct DualSet {
+    rrl_dual_t d[RRL_ADAM_MAX_DUALS];
+    int n;
+};
+__device__ __forceinline__ void dual_body(rrl_dual_t d, float b1, float b2, float eps) {
+    rrl_pack::to_global_all(d.log_p, d.exp_avg, d.exp_avg_sq, d.step, d.value, d.stat, d.loss_in, d.loss_out);
+    const float stat = d.stat[0];
+    if (d.loss_out) d.loss_out[0] = d.loss_in[0] + d.f_loss * (stat - d.eps_safe);
+    if (!d.log_p) return;
+    const float t = d.step[0] + 1.f;
+    const float step_size = d.lr / float(1.0 - pow(double(b1), double(t)));
+    const float bc2_sqrt = float(sqrt(1.0 - pow(double(b2), double(t))));
+    float p = d.log_p[0], m = d.exp_avg[0], v = d.exp_avg_sq[0];
+    adam_elem(p, d.eps_safe - stat, m, v, step_size, bc2_sqrt, b1, b2, eps, 0.f);
+    d.log_p[0] = p;
+    d.exp_avg[0] = m;
+    d.exp_avg_sq[0] = v;
+    d.step[0] = t;
+    if (d.value) d.value[0] = expf(p);
+}
+// rrl_adam_step_multi's grid with one more row (blockIdx.y == n_seg): thread 0 of its first workgroup steps the duals, one
+// after the other (a handful of scalars)
+__global__ __launch_bounds__(kBlock) void adam_multi_dual_kernel(AdamSegs a, int n_seg, DualSet ds, float lr, float b1,
+                                                                 float b2, float eps) {
+    __shared__ float sh[4];
+    const int k = blockIdx.y;
+    if (k == n_seg) {
+        if (blockIdx.x != 0 || threadIdx.x != 0) return;
+#pragma unroll
+        for (int j = 0; j < RRL_ADAM_MAX_DUALS; ++j)
+            if (j < ds.n) dual_body(ds.d[j], b1, b2, eps);
+        return;
+    }
+    rrl_adam_seg_t sg = a.seg[k];
+    const int vec = a.vec[k], blocks = a.first_block[k + 1] - a.first_block[k];
+    rrl_pack::to_global_all(sg.p, sg.g, sg.m, sg.v, sg.step_dev, sg.target, sg.g2, sg.g_part, sg.w2p, sg.target_w2p);
+    asm volatile("" ::"s"(sg.n), "s"(sg.tau), "s"(sg.weight_decay), "s"(sg.n_part), "s"(sg.part_stride), "s"(sg.part_elems),
+                 "s"(vec), "s"(blocks), "s"(sg.w2_off), "s"(sg.w2_heads));
+    if ((int)blockIdx.x >= blocks) return;
+    adam_seg_body(sg, vec != 0, lr, b1, b2, eps, blockIdx.x, blocks, sh);
+}
+
 // the same launch for S seeds (pack.hpp): grid (workgroups of the seeds' largest segments under the XCD-aware placement,
 // segments) -- blockIdx.y IS the segment and the seed follows from blockIdx.x by arithmetic, so the segment's block arrives in
 // one batch of scalar loads from the plan's device copy, as in the solo launch
@@ -664,7 +732,23 @@ int rrl_qrisk_policy_grad(int B, const float* zp, int n_part, long long part_str
                           void* stream) {
     if (!zp || !dzp || B <= 0 || n_part <= 0 || n_part > 4) return RRL_EINVAL;
     hipLaunchKernelGGL(qrisk_policy_grad_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, B, zp, n_part,
-                       part_stride, dzp, loss);
+                       part_stride, 1.f, dzp, loss);
+    return check_launch();
+}
+
+int rrl_dgd_qrisk_grad(int B, const float* zp, int n_part, long long part_stride, float nu, float* dzp, float* loss,
+                       void* stream) {
+    if (!zp || !dzp || B <= 0 || n_part <= 0 || n_part > 4) return RRL_EINVAL;
+    hipLaunchKernelGGL(qrisk_policy_grad_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, B, zp, n_part,
+                       part_stride, nu, dzp, loss);
+    return check_launch();
+}
+
+int rrl_rcpo_penalty(int B, const float* z, int n_part, long long part_stride, const float* lambda, float* penalty,
+                     float* mean, void* stream) {
+    if (!z || (penalty && !lambda) || (!penalty && !mean) || B <= 0 || n_part <= 0 || n_part > 4) return RRL_EINVAL;
+    hipLaunchKernelGGL(rcpo_penalty_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, B, z, n_part, part_stride,
+                       lambda, penalty, mean);
     return check_launch();
 }
 
@@ -756,6 +840,30 @@ int rrl_adam_step_multi(int n_seg, const rrl_adam_seg_t* segs, float lr, float b
     int most = 1;
     for (int k = 0; k < n_seg; ++k) most = a.first_block[k + 1] - a.first_block[k] > most ? a.first_block[k + 1] - a.first_block[k] : most;
     hipLaunchKernelGGL(adam_multi_kernel, dim3(most, n_seg), dim3(kBlock), 0, (hipStream_t)stream, a, n_seg,
+                       lr, beta1, beta2, eps);
+    return check_launch();
+}
+
+int rrl_adam_step_multi_duals(int n_seg, const rrl_adam_seg_t* segs, int n_dual, const rrl_dual_t* duals, float lr,
+                              float beta1, float beta2, float eps, void* stream) {
+    if (n_dual <= 0 || n_dual > RRL_ADAM_MAX_DUALS || !duals || n_seg < 0) return RRL_EINVAL;
+    DualSet ds{};
+    ds.n = n_dual;
+    for (int k = 0; k < n_dual; ++k) {
+        const rrl_dual_t& d = duals[k];
+        if (!d.stat || (d.log_p && (!d.exp_avg || !d.exp_avg_sq || !d.step)) || (d.loss_out && !d.loss_in) ||
+            (!d.log_p && !d.loss_out))
+            return RRL_EINVAL;
+        ds.d[k] = d;
+    }
+    AdamSegs a{};
+    int most = 1;
+    if (n_seg > 0) {
+        const int rc = build_adam_segs(n_seg, segs, a);
+        if (rc != RRL_OK) return rc;
+        for (int k = 0; k < n_seg; ++k) most = std::max(most, a.first_block[k + 1] - a.first_block[k]);
+    }
+    hipLaunchKernelGGL(adam_multi_dual_kernel, dim3(most, n_seg + 1), dim3(kBlock), 0, (hipStream_t)stream, a, n_seg, ds,
                        lr, beta1, beta2, eps);
     return check_launch();
 }

@@ -108,7 +108,8 @@ class VectorLoop:
                 # (fast_update.FastUpdater.update_pair): same results as the two calls below, ~30 % fewer launches
                 with trace_range("sample+sac_update+qrisk_update"):
                     fast.update_pair(self.memory, self.recovery_memory if online_qrisk else None,
-                                     rider=rider if u == cfg.updates_per_step - 1 else None)
+                                     rider=rider if u == cfg.updates_per_step - 1 else None,
+                                     nu=self.nu_schedule(i_episode))
                 self.host_updates[0] += 1
                 if online_qrisk:
                     qr.updates += 1
@@ -134,8 +135,9 @@ class VectorLoop:
         """Batched get_action (experiment.py:546-577): (task action, executed action, recovery)."""
         cfg = self.cfg
         fast = getattr(self.agent, "fast", None)
+        # (SQRL's constraint sampling, sac.py:139-161, draws its 100 candidates through SAC.select_action)
         if (fast is not None and train and not random_actions and obs.shape[0] == self.n
-                and (not cfg.use_recovery or cfg.MF_recovery)):
+                and (not cfg.use_recovery or cfg.MF_recovery) and not cfg.use_constraint_sampling):
             if self._actor is None:
                 from .fast_update import FastActor
                 self._actor = FastActor(fast, self.n)
@@ -323,7 +325,8 @@ class VectorLoop:
         cfg = self.cfg
         fast = getattr(self.agent, "fast", None)
         if not (self.carry_actor and do_update and online_qrisk and not random_actions and fast is not None
-                and cfg.use_recovery and cfg.MF_recovery and fast.can_carry_actor() and fast.sync_world == 1
+                and cfg.use_recovery and cfg.MF_recovery and not cfg.use_constraint_sampling and fast.can_carry_actor()
+                and fast.sync_world == 1
                 and cfg.batch_size == fast.B and hasattr(self.memory, "draw_desc")
                 and self.agent.safety_critic.clamp_batch_size(cfg.batch_size, len(self.recovery_memory)) == fast.B
                 and self.obs is self.env.obs and self.obs.shape[0] == self.n and self._can_fuse_step()):
@@ -512,11 +515,14 @@ class Experiment:
         if getattr(exp_cfg, "dp_mode", "replicas") not in ("replicas", "env_shard"):
             raise ValueError("--dp_mode must be 'replicas' or 'env_shard'")
         if self.env_shard:
-            from .fast_update import fast_path_supported
+            from .fast_update import fast_path_supported, uses_baseline_terms
             if exp_cfg.num_envs < 2 or not fast_path_supported(exp_cfg) or getattr(exp_cfg, "no_fast_path", False) \
                     or exp_cfg.batch_size % world_size or uses_mb_recovery(exp_cfg):
                 raise ValueError("--dp_mode env_shard needs the lock-step loop (--num_envs > 1), a configuration of "
                                  "the fused update path, and batch_size divisible by the number of ranks")
+            if uses_baseline_terms(exp_cfg):       # (RRL_FAST_BASELINES: the duals' gradients are not all-reduced)
+                raise ValueError("--dp_mode env_shard does not run the comparison algorithms (--DGD_constraints, "
+                                 "--update_nu, --nu_schedule, --use_constraint_sampling, --RCPO)")
             # ONE learner with the reference's batch: every rank contributes batch_size / world rows
             exp_cfg.global_batch_size = exp_cfg.batch_size
             exp_cfg.batch_size = exp_cfg.batch_size // world_size
@@ -579,6 +585,9 @@ class Experiment:
         from .fast_update import fast_path_supported
         if fast_path_supported(exp_cfg) and not getattr(exp_cfg, "no_fast_path", False):
             self.agent.enable_fast_path(exp_cfg.batch_size)
+        # which update path ran (run_stats.pkl, the checkpoint): the comparison algorithms take the fused one under
+        # RRL_FAST_BASELINES=1 only
+        self.vector_rules["update_path"] = "fused" if self.agent.fast is not None else "autograd"
         if self.env_shard:
             self.agent.fast.enable_grad_sync(world_size)
         self.loop = VectorLoop(exp_cfg, self.env, self.agent, self.memory, self.recovery_memory,
@@ -636,7 +645,7 @@ class Experiment:
         # the rules that change what the critics train on, next to the results they produced: printed, written into
         # run_stats.pkl ("vector_rules") and the checkpoint
         self.vector_rules = {"demo_share": share if share > 0 else 0.0, "pinned_demonstrations": int(pinned),
-                             **{k: self.vector_rules[k] for k in ("replay_capacities", "cover_rows_limit",
+                             **{k: self.vector_rules[k] for k in ("update_path", "replay_capacities", "cover_rows_limit",
                                                                    "buffers_cover_the_run", "plan_warm_start")}}
         if cfg.num_envs > 1:
             print("Q_risk batch: %s (--demo_share; 0 = the reference's single uniform draw, replay_memory.py:54-72)"
@@ -1065,10 +1074,10 @@ def run_packed(exp_cfg, rank=0, world_size=1):
     `episode_stats.bin`) and, with `--info_envs K`, the per-step `train_stats` of the first K envs -- the files the solo
     lock-step run of that seed writes.  Returns the list of per-seed histories."""
     import copy
-    from .fast_update import fast_path_supported
+    from .fast_update import fast_path_supported, uses_baseline_terms
     from .packed import PackedLoop
     S = int(exp_cfg.seeds_per_gpu)
-    if exp_cfg.num_envs < 2 or not fast_path_supported(exp_cfg) or uses_mb_recovery(exp_cfg) or \
+    if exp_cfg.num_envs < 2 or not fast_path_supported(exp_cfg) or uses_baseline_terms(exp_cfg) or uses_mb_recovery(exp_cfg) or \
             not (exp_cfg.use_recovery and exp_cfg.MF_recovery) or getattr(exp_cfg, "dp_mode", "replicas") != "replicas":
         raise ValueError("--seeds_per_gpu needs the lock-step loop (--num_envs > 1) on the fused update path with model-free "
                          "recovery (every rank of a multi-GPU launch packs its own seeds: replicas, no exchange)")

@@ -3,7 +3,8 @@
 (recovery_rl/sac.py:170-277) and `QRiskWrapper.update_parameters` (recovery_rl/qrisk.py:86-163).
 
 Same mathematics as the autograd path in sac.py / qrisk.py (which stays as the general path for
-the baseline flags: DGD / RSPO / RCPO / SQRL / automatic entropy tuning / Deterministic policy);
+automatic entropy tuning / Deterministic policy, and for the comparison algorithms LR / RSPO / SQRL / RCPO unless
+RRL_FAST_BASELINES=1 routes them here);
 `tests/test_fast_update_gpu.py` checks the two paths against each other and against the
 reference KATs.  ~37 launches per update instead of ~150, no vendor GEMM.
 
@@ -129,9 +130,10 @@ class FlatNet:
         _lib.check(rc, "rrl_adam_step")
 
 
-def adam_multi(lr, nets, betas=(0.9, 0.999), eps=1e-8):
+def adam_multi(lr, nets, betas=(0.9, 0.999), eps=1e-8, duals=None):
     """One rrl_adam_step_multi launch over several FlatNets: nets = [(net, target or None, tau[, part]), ...];
-    part = (first_part [T, stride], n_first) or None, see FlatNet.adam."""
+    part = (first_part [T, stride], n_first) or None, see FlatNet.adam.  duals = [rrl_dual_t, ...]: the dual variables
+    of the comparison algorithms step in the same launch (rrl_adam_step_multi_duals)."""
     lib = _lib.load()
     segs = (_lib.rrl_adam_seg_t * len(nets))()
     for k, item in enumerate(nets):
@@ -149,6 +151,12 @@ def adam_multi(lr, nets, betas=(0.9, 0.999), eps=1e-8):
                                       net.w2p.data_ptr() if pack else None,
                                       target.w2p.data_ptr() if pack and target is not None else None,
                                       net.offset["W2"] if pack else 0, net.p["W2"].shape[0] if pack else 0)
+    if duals:
+        arr = (_lib.rrl_dual_t * len(duals))(*duals)
+        record("unsupported", "rrl_adam_step_multi_duals")
+        _lib.check(lib.rrl_adam_step_multi_duals(len(nets), segs, len(duals), arr, lr, betas[0], betas[1], eps,
+                                                 _lib.current_stream()), "rrl_adam_step_multi_duals")
+        return
     record("adam", segs, len(nets), float(lr), float(betas[0]), float(betas[1]), float(eps))
     _lib.check(lib.rrl_adam_step_multi(len(nets), segs, lr, betas[0], betas[1], eps, _lib.current_stream()),
                "rrl_adam_step_multi")
@@ -481,11 +489,99 @@ class FastUpdater:
         self.bias = agent.policy.action_bias.to(dev).float().contiguous()
         self.rscale = self.qr.policy.action_scale.to(dev).float().contiguous()
         self.rbias = self.qr.policy.action_bias.to(dev).float().contiguous()
+        self._init_baselines(agent, B, z)
+
+    def _init_baselines(self, agent, B, z):
+        """The comparison algorithms' terms of the SAC update (sac.py:170-277): --DGD_constraints (the Lagrangian term
+        nu (max sigmoid(Q_risk(s, pi)) - eps_safe) of the policy loss), --update_nu (the nu step), --RCPO (the penalty
+        lambda max sigmoid(Q_risk(s, a)) of the critic target and the lambda step).  Q_risk runs in the SAC update at its
+        weights before this iteration's Q_risk step, on workspaces of its own: (s, pi) saved with an input gradient, (s, a)
+        forward only."""
+        dev = self.dev
+        self.dgd, self.update_nu, self.rcpo = bool(agent.DGD_constraints), bool(agent.update_nu), bool(agent.RCPO)
+        self.qr_p, self.qr_sa = Stack(self.qrisk, B), Stack(self.qrisk, B)
+        self.penalty = z(B)
+        self.dual_stats = z(4)          # mean max sigmoid(z) at (s, pi) | at (s, a) | Lagrangian policy loss | (pad)
+        self.dq_r = z(2, B, 1)
+        # the multipliers the kernels read and the dual step writes: persistent float32 device scalars (SAC._set_dual keeps
+        # writing them in place)
+        if self.update_nu and not torch.is_tensor(agent.nu):
+            agent.nu = torch.tensor(float(agent.nu), dtype=torch.float32, device=dev)
+        if self.rcpo and not torch.is_tensor(agent.lambda_RCPO):
+            agent.lambda_RCPO = torch.tensor(float(agent.lambda_RCPO), dtype=torch.float32, device=dev)
+        if self.dgd:
+            self._join_dx(self.cri_b, self.qr_p)
+        for opt, prm, on in ((agent.nu_optim, agent.log_nu, self.update_nu),
+                             (agent.lambda_RCPO_optim, agent.log_lambda_RCPO, self.rcpo)):
+            if on:
+                dual_state(opt, prm)
+
+    def _join_dx(self, a, b):
+        """The policy loss of --DGD_constraints has two action-gradient sources, critic(s, pi) and Q_risk(s, pi): their dx
+        buffers become the two halves of ONE tensor, so that one d_action description of the policy-head backward covers
+        both (joint_d_action)."""
+        assert a.net.H == b.net.H and a.net.din == b.net.din and a.net.G == b.net.G == 2 and a.B == b.B
+        if a.first_part is not None and not a.fold_dx:
+            # unfolded tile partials of two stacks are more than the head backward adds up per source: plain dx
+            for st in (a, b):
+                st.fuse_first, st.first_part, st.dx_part = False, None, None
+        j = torch.zeros(4, a.B, a.net.din, dtype=torch.float32, device=self.dev)
+        a.dx, b.dx = j[0:2], j[2:4]
+        if a.dx_part is not None:
+            jp = torch.zeros(2, *a.dx_part.shape, dtype=torch.float32, device=self.dev)
+            a.dx_part, b.dx_part = jp[0], jp[1]
+
+    def joint_d_action(self):
+        """(d_action, (n_heads, head_stride)) of critic(s, pi) + Q_risk(s, pi) after both backwards (input_grad).  Each
+        source's partials (tile t, head g) lie (2 t + g) B din floats apart, so one source is 2 t partials added one after
+        the other, and the second source's block follows the first's: a fixed order, the same bits from run to run."""
+        a, b = self.cri_b, self.qr_p
+        B, din = a.B, a.net.din
+        if a.fuse_first:
+            assert b.fuse_first and a._folded == b._folded
+            n = a.dx_part.shape[0] // 4 if a._folded else a.dx_part.shape[0]
+            assert 2 * n <= 16
+            return (a.dx_part[0], 2 * n, B * din, 1), (2, a.dx_part.numel())
+        return a.dx, (4, B * din)
+
+    def _duals(self, nu):
+        """rrl_dual_t members of this SAC update's optimiser launch."""
+        ag, p = self.agent, _lib.ptr
+        out = []
+        if self.dgd or self.update_nu:
+            d = _lib.rrl_dual_t(stat=p(self.dual_stats[0:1]), eps_safe=float(ag.eps_safe), lr=float(0.1 * ag.lr))
+            if self.update_nu:
+                st = dual_state(ag.nu_optim, ag.log_nu)
+                d.log_p, d.exp_avg, d.exp_avg_sq, d.step = p(ag.log_nu), p(st["exp_avg"]), p(st["exp_avg_sq"]), p(st["step"])
+                d.value = p(ag.nu)
+            if self.dgd:
+                d.loss_in, d.loss_out, d.f_loss = p(self.losses[2:3]), p(self.dual_stats[2:3]), float(nu)
+            out.append(d)
+        if self.rcpo:
+            st = dual_state(ag.lambda_RCPO_optim, ag.log_lambda_RCPO)
+            out.append(_lib.rrl_dual_t(p(ag.log_lambda_RCPO), p(st["exp_avg"]), p(st["exp_avg_sq"]), p(st["step"]),
+                                       p(ag.lambda_RCPO), p(self.dual_stats[1:2]), float(ag.eps_safe), float(0.1 * ag.lr),
+                                       None, None, 0.0))
+        return out
+
+    def _penalty(self, z, want_penalty=True, mean=None):
+        """rrl_rcpo_penalty: penalty = lambda max sigmoid(z) (want_penalty) and the batch mean of max sigmoid(z)."""
+        t, n_part, ps = z
+        record("unsupported", "rrl_rcpo_penalty")
+        p = _lib.ptr
+        self._check(self.lib.rrl_rcpo_penalty(self.B, p(t), n_part, ps, p(self.agent.lambda_RCPO) if want_penalty else None,
+                                              p(self.penalty) if want_penalty else None, p(mean), _lib.current_stream()),
+                    "rrl_rcpo_penalty")
+
+    def policy_loss(self):
+        """The SAC policy loss statistic of the last update (with the Lagrangian term under --DGD_constraints, put together
+        by the optimiser launch)."""
+        return self.dual_stats[2] if self.dgd else self.losses[2]
 
     # -- helpers ---------------------------------------------------------------------------------
     def stacks(self):
         return [self.pol_a, self.pol_ab, self.pol_next, self.pol_b, self.cri_a, self.cri_b, self.cri_t, self.qr_a,
-                self.qr_b, self.qr_t, self.rec_a]
+                self.qr_b, self.qr_t, self.rec_a, self.qr_p, self.qr_sa]
 
     def set_fuse_first(self, on):
         """First layer of every stack backward inside the hidden-layer launch (partial sums read by Adam and by the
@@ -530,9 +626,10 @@ class FastUpdater:
             grad.mul_(1.0 / self.sync_world)
 
     def _loss(self, kind, out, n_part, part_stride, out_t=None, v0=None, v1=None, v2=None, v3=None, alpha=None,
-              f0=0.0, d_action=None, loss=None):
+              f0=0.0, d_action=None, loss=None, d_heads=None):
         """rrl_loss_t for Stack.backward: the head-backward kernel evaluates the loss gradient itself.
-        d_action = the critic's input gradient dx [2, B, 4] whose action columns feed a policy head."""
+        d_action = the critic's input gradient dx [2, B, 4] whose action columns feed a policy head; d_heads =
+        (n_heads, head_stride) when it is not that tensor's two heads (joint_d_action)."""
         p = _lib.ptr
         ld = n_heads = hs = parts = ps = group = 0
         da = None
@@ -540,6 +637,8 @@ class FastUpdater:
             if isinstance(d_action, tuple):           # Stack.dx_parts(): column-tile partials of the critic's dx
                 d_action, parts, ps, group = d_action
             da, ld, n_heads, hs = d_action[0, :, 2:4].data_ptr(), d_action.stride(1), 2, d_action.stride(0)
+            if d_heads is not None:
+                n_heads, hs = d_heads
         return _lib.rrl_loss_t(kind, n_part, part_stride, p(out), p(out_t), p(v0), p(v1), p(v2), p(v3), p(alpha),
                                float(f0), ld, n_heads, hs, da, p(loss), parts, ps, group)
 
@@ -618,12 +717,13 @@ class FastUpdater:
                                       p(self.rbias), p(action_view), action_view.stride(0), None, None, None, None,
                                       p(self.recpolicy.p["log_std"]), float(self.qr.policy.min_log_std))
 
-    def update_pair(self, memory, recovery_memory, rider=None):
+    def update_pair(self, memory, recovery_memory, rider=None, nu=None):
         """One SAC update and (recovery_memory not None) one Q_risk + recovery-policy update of a lock-step iteration
         (experiment.py:397-416): both replay draws and the iteration's policy noise in ONE launch, then the two
         updates on the grouped kernels.  Same draws, same arithmetic, same parameters as the separate calls.
         `rider` = (FastActor, obs): the acting pass that follows this update takes two of its three forwards along in the
-        Q_risk update's launches (FastActor.ride_*; the LAST update pair of an iteration only)."""
+        Q_risk update's launches (FastActor.ride_*; the LAST update pair of an iteration only).
+        `nu`: the multiplier of the Lagrangian term (--DGD_constraints), the value SAC.update_parameters is passed."""
         B, qr = self.B, self.qr
         d1, batch = memory.draw_desc(B, rows=self.rows)
         d2 = batch_q = None
@@ -644,14 +744,18 @@ class FastUpdater:
         self._actor_noise = self._noise_buf[4 * B * 2:].view(2, n_act, 2) if n_act else None
         self._actor_noise_fresh = n_act > 0
         n = self._noise
-        self.sac_update_grouped(batch, n[0], n[1])
+        self.sac_update_grouped(batch, n[0], n[1], nu=nu)
         if recovery_memory is not None:
             self.qrisk_update_grouped(batch_q, n[2], n[3], rider=rider)
         return self.losses
 
-    def sac_update_grouped(self, batch, eps_next, eps_pi):
-        """sac_update with 11 launches instead of 17 (rows already written by the draw)."""
+    def sac_update_grouped(self, batch, eps_next, eps_pi, nu=None):
+        """sac_update with 11 launches instead of 17 (rows already written by the draw).  The comparison algorithms'
+        Q_risk forwards join the critic forwards' launch (a second one when both (s, pi) and (s, a) are needed: four
+        members at most), their backward the critic backwards' launch, the duals the optimiser launch; the RCPO
+        penalty is one launch more."""
         ag, B = self.agent, self.B
+        nu = self._nu(nu)
         s, a, r, s2, m = batch
         r, m = r.reshape(-1), m.reshape(-1)
         if self.pol_ab.split:      # one-member group: the stand-alone launch's kernel body, and a launch the tape can pack
@@ -667,24 +771,54 @@ class FastUpdater:
             hd2 = hd1 = None
         # critic_target(s', a'), critic(s, a), critic(s, pi): three independent forwards (sac.py:192-218); a' and pi are
         # evaluated by the stacks that consume them
-        forward_multi([self.cri_t.forward_desc(self.x2u, params=self.critic_target, save=False, in_head=hd2),
-                       self.cri_a.forward_desc(self.xu), self.cri_b.forward_desc(self.xpu, in_head=hd1)])
+        fwd = [self.cri_t.forward_desc(self.x2u, params=self.critic_target, save=False, in_head=hd2),
+               self.cri_a.forward_desc(self.xu), self.cri_b.forward_desc(self.xpu, in_head=hd1)]
+        if self.dgd or self.update_nu:      # Q_risk(s, pi): pi evaluated by this stack too, written by the critic's only
+            hq = None
+            if hd1 is not None:
+                hq = _lib.rrl_policy_head_t.from_buffer_copy(hd1)
+                hq.action, hq.logp = None, None
+            fwd.append(self.qr_p.forward_desc(self.xpu, save=self.dgd, in_head=hq))
+        if self.rcpo:
+            fwd.append(self.qr_sa.forward_desc(self.xu, save=False))
+        forward_multi(fwd[:4])
+        if len(fwd) > 4:
+            forward_multi(fwd[4:])
         qt, n_part, ps = self.cri_t.parts
         q, qp = self.cri_a.parts[0], self.cri_b.parts[0]
+        if self.rcpo:
+            self._penalty(self.qr_sa.parts, mean=self.dual_stats[1:2])
+        if self.update_nu and not self.dgd:
+            self._penalty(self.qr_p.parts, want_penalty=False, mean=self.dual_stats[0:1])
         # the critic's backward for its own loss (weight gradients) and for the policy loss (input gradient)
-        backward_multi([
+        members = [
             self.cri_a.backward_descs(self._loss(_lib.LOSS_SAC_CRITIC, q, n_part, ps, out_t=qt, v0=self.logp2, v1=r,
-                                                 v2=m, alpha=self.alpha, f0=ag.gamma, loss=self.losses)),
+                                                 v2=m, v3=self.penalty if self.rcpo else None, alpha=self.alpha,
+                                                 f0=ag.gamma, loss=self.losses)),
             self.cri_b.backward_descs(self._loss(_lib.LOSS_SAC_POLICY, qp, n_part, ps, v0=self.logp, alpha=self.alpha,
-                                                 loss=self.losses[2:]), weight_grads=False, input_grad=True)])
+                                                 loss=self.losses[2:]), weight_grads=False, input_grad=True)]
+        if self.dgd:
+            zp, zn, zs = self.qr_p.parts
+            members.append(self.qr_p.backward_descs(self._loss(_lib.LOSS_DGD_QRISK, zp, zn, zs, f0=nu,
+                                                               loss=self.dual_stats[0:1]), weight_grads=False, input_grad=True))
+        backward_multi(members)
         ht, hn, hs = head
+        da, dh = self.joint_d_action() if self.dgd else (self.cri_b.dx_parts(), None)
         self.pol_b.backward(self._loss(_lib.LOSS_GAUSS_HEAD, ht, hn, hs, v0=eps_pi, v1=self.scale,
-                                       f0=float(ag.alpha) / B, d_action=self.cri_b.dx_parts()))
+                                       f0=float(ag.alpha) / B, d_action=da, d_heads=dh))
         if self.sync_world > 1:
             self._sync(self.sac_bucket)
         adam_multi(ag.lr, [(self.critic, self.critic_target, ag.tau, self.cri_a.grad_part),
-                           (self.policy, None, 0.0, self.pol_b.grad_part)])
+                           (self.policy, None, 0.0, self.pol_b.grad_part)], duals=self._duals(nu))
         return self.losses
+
+    def _nu(self, nu):
+        """The multiplier of the Lagrangian term as a host float: the value passed in (the reference's nu_schedule), else
+        the agent's."""
+        if not self.dgd:
+            return 0.0
+        nu = self.agent.nu if nu is None else nu
+        return float(nu)
 
     def can_carry_actor(self):
         """The acting pass's task-policy and Q_risk forwards can ride in this update's forward launches (qrisk_update_grouped):
@@ -745,8 +879,9 @@ class FastUpdater:
         return self.losses
 
     # -- SAC -------------------------------------------------------------------------------------
-    def sac_update(self, batch, eps_next, eps_pi, rows_loaded=False):
+    def sac_update(self, batch, eps_next, eps_pi, rows_loaded=False, nu=None):
         ag, B, lib, st = self.agent, self.B, self.lib, _lib.current_stream()
+        nu = self._nu(nu)
         s, a, r, s2, m = self._load_batch(batch, rows_loaded)
         # pi(s') and pi(s) share the weights (both gradients are taken before either step): ONE policy forward
         self.pol_ab.forward(self.x_pol[:, 0:2])
@@ -755,12 +890,16 @@ class FastUpdater:
         self._gauss_fwd(head2, eps_next, self.x2u[:, 2:4], self.logp2)
         qt, n_part, ps = self.cri_b.forward(self.x2u, params=self.critic_target, save=False)
         q, _, _ = self.cri_a.forward(self.xu)
+        pen = None
+        if self.rcpo:                                                  # lambda max sigmoid(Q_risk(s, a)) (sac.py:202-205)
+            self._penalty(self.qr_sa.forward(self.xu, save=False), mean=self.dual_stats[1:2])
+            pen = self.penalty
         if self.fuse_loss:                                             # critic gradients (sac.py:233-235)
             self.cri_a.backward(self._loss(_lib.LOSS_SAC_CRITIC, q, n_part, ps, out_t=qt, v0=self.logp2, v1=r, v2=m,
-                                           alpha=self.alpha, f0=ag.gamma, loss=self.losses))
+                                           v3=pen, alpha=self.alpha, f0=ag.gamma, loss=self.losses))
         else:
             self._check(lib.rrl_sac_critic_grad(B, q.data_ptr(), qt.data_ptr(), n_part, ps, self.logp2.data_ptr(),
-                                                r.data_ptr(), m.data_ptr(), ag.gamma, self.alpha.data_ptr(), None,
+                                                r.data_ptr(), m.data_ptr(), ag.gamma, self.alpha.data_ptr(), _lib.ptr(pen),
                                                 self.dq.data_ptr(), self.losses.data_ptr(), st),
                         "rrl_sac_critic_grad")
             self.cri_a.backward(self.dq)
@@ -768,29 +907,46 @@ class FastUpdater:
         head = self.pol_b.after_forward()
         self._gauss_fwd(head, eps_pi, self.xpu[:, 2:4], self.logp)
         qp, n_part, ps = self.cri_b.forward(self.xpu)
+        zp = None
+        if self.dgd or self.update_nu:                                 # Q_risk(s, pi) at its pre-update weights
+            zp = self.qr_p.forward(self.xpu, save=self.dgd)
+            if not self.dgd:
+                self._penalty(zp, want_penalty=False, mean=self.dual_stats[0:1])
         ht, hn, hs = head
         if self.fuse_loss:
             self.cri_b.backward(self._loss(_lib.LOSS_SAC_POLICY, qp, n_part, ps, v0=self.logp, alpha=self.alpha,
                                            loss=self.losses[2:]), weight_grads=False, input_grad=True)
+            if self.dgd:
+                self.qr_p.backward(self._loss(_lib.LOSS_DGD_QRISK, *zp, f0=nu, loss=self.dual_stats[0:1]),
+                                   weight_grads=False, input_grad=True)
             # d pi = action columns of dx [2,B,4], summed over the two critic heads inside the policy's head backward
+            # (and over Q_risk's two after them: joint_d_action)
+            da, dh = self.joint_d_action() if self.dgd else (self.cri_b.dx_parts(), None)
             self.pol_b.backward(self._loss(_lib.LOSS_GAUSS_HEAD, ht, hn, hs, v0=eps_pi, v1=self.scale,
-                                           f0=float(ag.alpha) / B, d_action=self.cri_b.dx_parts()))
+                                           f0=float(ag.alpha) / B, d_action=da, d_heads=dh))
         else:
             assert not self.cri_b.fuse_first, "fuse_loss = False needs set_fuse_first(False)"
             self._check(lib.rrl_sac_policy_grad(B, qp.data_ptr(), n_part, ps, self.logp.data_ptr(),
                                                 self.alpha.data_ptr(), self.dq.data_ptr(),
                                                 self.losses[2:].data_ptr(), st), "rrl_sac_policy_grad")
             dx = self.cri_b.backward(self.dq, weight_grads=False, input_grad=True)      # [2,B,4]
+            heads = 2
+            if self.dgd:
+                zt, zn, zs = zp
+                self._check(lib.rrl_dgd_qrisk_grad(B, zt.data_ptr(), zn, zs, nu, self.dq_r.data_ptr(),
+                                                   self.dual_stats.data_ptr(), st), "rrl_dgd_qrisk_grad")
+                self.qr_p.backward(self.dq_r, weight_grads=False, input_grad=True)     # into dx's second half
+                heads = 4
             self._check(lib.rrl_gauss_head_bwd(B, ht.data_ptr(), hn, hs, eps_pi.data_ptr(), self.scale.data_ptr(),
-                                               dx[0, :, 2:4].data_ptr(), dx.stride(1), 2, dx.stride(0),
+                                               dx[0, :, 2:4].data_ptr(), dx.stride(1), heads, dx.stride(0),
                                                float(ag.alpha) / B, self.dhead.data_ptr(), st),
                         "rrl_gauss_head_bwd")
             self.pol_b.backward(self.dhead)
         if self.sync_world > 1:
             self._sync(self.sac_bucket)
-        # both optimiser steps + the soft target update (:273-274) in one launch
+        # both optimiser steps + the soft target update (:273-274) in one launch (+ the duals)
         adam_multi(ag.lr, [(self.critic, self.critic_target, ag.tau, self.cri_a.grad_part),
-                           (self.policy, None, 0.0, self.pol_b.grad_part)])
+                           (self.policy, None, 0.0, self.pol_b.grad_part)], duals=self._duals(nu))
         return self.losses
 
     # -- Q_risk ------------------------------------------------------------------------------------
@@ -972,9 +1128,34 @@ class FastActor:
 FastActor.act_gate = FastActor._act_gate
 
 
+def dual_state(opt, param):
+    """torch.optim.Adam's state of a dual variable (capturable: `step` a float32 device scalar), created up front in
+    torch's own format: the fused dual step (rrl_adam_step_multi_duals) reads and writes these tensors, so state_dict(),
+    checkpoints and a later autograd step see them as torch would have left them."""
+    st = opt.state[param]
+    if len(st) == 0:
+        st["step"] = torch.zeros((), dtype=torch.float32, device=param.device)
+        st["exp_avg"] = torch.zeros_like(param, memory_format=torch.preserve_format)
+        st["exp_avg_sq"] = torch.zeros_like(param, memory_format=torch.preserve_format)
+    return st
+
+
+BASELINE_FLAGS = ("DGD_constraints", "update_nu", "nu_schedule", "use_constraint_sampling", "RCPO")
+
+
+def fast_baselines_enabled():
+    """RRL_FAST_BASELINES=1: the comparison algorithms (LR, RSPO, SQRL, RCPO) take the fused update path too (opt-in)."""
+    return os.environ.get("RRL_FAST_BASELINES", "0") == "1"
+
+
+def uses_baseline_terms(cfg):
+    return any(bool(getattr(cfg, f, False)) for f in BASELINE_FLAGS)
+
+
 def fast_path_supported(cfg):
     """The fused path covers the Recovery-RL configurations (task SAC + Q_risk, model-free or
-    model-based recovery, reward penalty); the comparison algorithms use the autograd path."""
-    return (cfg.policy == "Gaussian" and not cfg.automatic_entropy_tuning and not cfg.DGD_constraints
-            and not cfg.RCPO and not cfg.update_nu and not cfg.use_constraint_sampling
+    model-based recovery, reward penalty); the comparison algorithms (BASELINE_FLAGS) use the autograd path
+    unless RRL_FAST_BASELINES=1."""
+    return (cfg.policy == "Gaussian" and not cfg.automatic_entropy_tuning
+            and (fast_baselines_enabled() or not uses_baseline_terms(cfg))
             and cfg.target_update_interval == 1 and not getattr(cfg, "cnn", False))

@@ -162,8 +162,8 @@ class SAC(object):
         if self.fast is not None and batch[2].shape[0] == self.fast.B:
             if eps_next is None:
                 eps_next, eps_pi = self.fast.noise(0)
-            losses = self.fast.sac_update(batch, eps_next, eps_pi, rows_loaded=rows_loaded)
-            out = (losses[0], losses[1], losses[2], self._zero, self._alpha_const)
+            losses = self.fast.sac_update(batch, eps_next, eps_pi, rows_loaded=rows_loaded, nu=nu)
+            out = (losses[0], losses[1], self.fast.policy_loss(), self._zero, self._alpha_const)
             return tuple(float(x) for x in out) if as_floats else out
         state, action, reward, next_state, mask = batch
         reward = reward.reshape(-1, 1)
