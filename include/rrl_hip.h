@@ -265,6 +265,21 @@ int rrl_sample_multi(const rrl_draw_t* first, const rrl_draw_t* second, long lon
                      uint64_t noise_counter, uint64_t* noise_counter_dev, uint64_t noise_counter_inc, float* noise_out,
                      void* stream);
 
+/* Draw-ahead: the uniform draw in two halves.  SELECT picks the B keys of `draw` for the ring as it will be `rows_ahead`
+ * pushed rows from now (size' = min(cap, size + rows_ahead); 0 = the ring as it is) at the tick as it is, and leaves them in
+ * `keys` [B + RRL_AHEAD_META] (keys, then tick, size' and the error code of the selection); it changes nothing else -- the
+ * tick is not advanced and no flag raised.  GATHER (a rider of rrl_mlp3_forward_riders) does, after those rows were pushed,
+ * what the draw does around its selection: flags rb.state[3] = 1 (B > size') before, = 2 (round cap) after advancing the
+ * tick, gathers the rows of the keys into the draw's outputs.  Select + pushes + gather leave exactly what the pushes + the
+ * stand-alone draw leave; keys drawn for another tick or size are refused (rb.state[3] = 4). */
+#define RRL_AHEAD_META 8
+typedef struct {
+    const rrl_draw_t* draw;      /* RRL_DRAW_UNIFORM */
+    int64_t rows_ahead;          /* select only */
+    uint32_t* keys;
+} rrl_draw_ahead_t;
+int rrl_draw_select(const rrl_draw_ahead_t* sel, void* stream);
+
 /* Fused lock-step iteration tail: env step + reward penalty + bootstrap mask + memory.push +
  * recovery_memory.push + episode counters in ONE launch (the body of recovery_rl/experiment.py:420-461
  * for n navigation envs).  `obs` holds the current observation on entry (it is the stored `state`) and
@@ -580,6 +595,26 @@ typedef struct {
     float *dW1, *db1, *dx;
 } rrl_input_bwd_t;
 int rrl_mlp3_forward_multi(int n, const rrl_stack_t* stacks, void* stream);
+/* ONE column-split stack (H = 256) with rider workgroups in front of its tiles: launches that nothing in this launch waits
+ * for, each the body of the launch it replaces on a workgroup of its own (batches of at most 256 rows).  All optional:
+ *   select   the select half of a draw (rrl_draw_ahead_t)
+ *   gather   the gather half for keys selected ahead; the stack must be the 2B-row forward over the batch's s' (rows
+ *            [0, B)) and s (rows [B, 2B)), din = 2: its rows are then read from the ring through the keys instead of from
+ *            `x` -- the values the gather writes -- so the forward does not wait for the gather
+ *   second   a whole draw (any mode), as rrl_sample_multi's member
+ *   noise_*  the noise fill of rrl_sample_multi
+ * Outputs equal the separate launches' bit for bit. */
+typedef struct {
+    const rrl_draw_ahead_t* select;
+    const rrl_draw_ahead_t* gather;
+    const rrl_draw_t* second;
+    long long noise_pairs;
+    uint64_t noise_seed, noise_counter;
+    uint64_t* noise_counter_dev;
+    uint64_t noise_counter_inc;
+    float* noise_out;
+} rrl_fwd_riders_t;
+int rrl_mlp3_forward_riders(const rrl_stack_t* stack, const rrl_fwd_riders_t* riders, void* stream);
 int rrl_mlp_head_backward_multi(int n, const rrl_head_bwd_t* members, void* stream);
 int rrl_mlp_hidden_backward_multi(int n, const rrl_hidden_bwd_t* members, void* stream);
 int rrl_mlp_input_backward_multi(int n, const rrl_input_bwd_t* members, void* stream);

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from recovery_rl_amd import _lib  # noqa: E402
-from test_w2_permute_cpu import LLVM, kernel_table  # noqa: E402
+from isa_util import LLVM, kernel_table  # noqa: E402
 
 
 def demangle(names):

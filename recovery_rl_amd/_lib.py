@@ -37,7 +37,7 @@ EXPORTS = [
     "rrl_nav_offline",
     "rrl_maze_step", "rrl_maze_reset", "rrl_maze_offline",
     "rrl_replay_push", "rrl_replay_sample_gather", "rrl_creplay_sample_gather", "rrl_replay_sample_gather_split",
-    "rrl_sample_multi",
+    "rrl_sample_multi", "rrl_draw_select", "rrl_mlp3_forward_riders",
     "rrl_nav_step_push", "rrl_maze_step_push", "rrl_nav_step_push_select", "rrl_maze_step_push_select",
     "rrl_nav_step_push_x", "rrl_maze_step_push_x",
     "rrl_sample_multi_packed", "rrl_pack_clear", "rrl_mlp3_forward_multi_packed", "rrl_mlp_head_backward_multi_packed",
@@ -228,6 +228,20 @@ class rrl_sample_args_t(C.Structure):
                 ("noise_counter_inc", C.c_uint64), ("noise_out", C.c_void_p)]
 
 
+AHEAD_META = 8
+
+
+class rrl_draw_ahead_t(C.Structure):
+    _fields_ = [("draw", C.POINTER(rrl_draw_t)), ("rows_ahead", C.c_int64), ("keys", C.c_void_p)]
+
+
+class rrl_fwd_riders_t(C.Structure):
+    _fields_ = [("select", C.POINTER(rrl_draw_ahead_t)), ("gather", C.POINTER(rrl_draw_ahead_t)),
+                ("second", C.POINTER(rrl_draw_t)), ("noise_pairs", C.c_longlong), ("noise_seed", C.c_uint64),
+                ("noise_counter", C.c_uint64), ("noise_counter_dev", C.c_void_p), ("noise_counter_inc", C.c_uint64),
+                ("noise_out", C.c_void_p)]
+
+
 class rrl_adam_seg_t(C.Structure):
     _fields_ = [("n", C.c_longlong), ("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
                 ("step_dev", C.c_void_p), ("target", C.c_void_p), ("tau", C.c_float), ("weight_decay", C.c_float),
@@ -287,6 +301,8 @@ def _declare(lib):
                                            f32, ci, rp, rp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "rrl_sample_multi": (ci, [C.POINTER(rrl_draw_t), C.POINTER(rrl_draw_t), ll, u64, u64, vp, u64, vp, vp]),
         "rrl_mlp3_forward_multi": (ci, [ci, C.POINTER(rrl_stack_t), vp]),
+        "rrl_draw_select": (ci, [C.POINTER(rrl_draw_ahead_t), vp]),
+        "rrl_mlp3_forward_riders": (ci, [C.POINTER(rrl_stack_t), C.POINTER(rrl_fwd_riders_t), vp]),
         "rrl_mlp_head_backward_multi": (ci, [ci, C.POINTER(rrl_head_bwd_t), vp]),
         "rrl_mlp_hidden_backward_multi": (ci, [ci, C.POINTER(rrl_hidden_bwd_t), vp]),
         "rrl_mlp_input_backward_multi": (ci, [ci, C.POINTER(rrl_input_bwd_t), vp]),

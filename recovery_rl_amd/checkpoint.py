@@ -65,6 +65,7 @@ def load_replay_state(mem, sd):
         getattr(mem, name)[:size].copy_(sd[name])
     mem.state.copy_(sd["state"])
     mem.tick.copy_(sd["tick"])
+    mem.ahead.drop()                       # keys drawn ahead belonged to the ring and tick that were just replaced
     mem.pin(sd.get("pinned", 0))
     if mem.pos_cnt is not None:
         same = sd.get("abi") == int(mem.lib.rrl_abi_version()) and sd["pos_cnt"].shape == mem.pos_cnt.shape

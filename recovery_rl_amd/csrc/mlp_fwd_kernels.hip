@@ -7,6 +7,7 @@
 // streams its 16 rows of W2 straight from L2 into MFMA operands), layer 3 by 16-lane dot products.
 // No intermediate activation touches HBM unless the caller asks for h1 / h2 (needed by backward).
 #include "mlp_common.hpp"
+#include "replay_draw.hpp"
 
 namespace {
 
@@ -204,9 +205,20 @@ constexpr int kSplitPad = 20;   // pad floats per row of the h1 tile: rows 16-by
 // run under v_mfma_f32_16x16x4_f32 -- neither a partner wave's nor the wave's own (profiles/mfma_valu_overlap.hip,
 // mfma_valu_inwave.hip) -- so in the throughput regime a SIMD's time is the SUM of its waves' MFMA and VALU cycles and every
 // instruction removed counts.  Per output element the arithmetic is the one-block form's.
-template <int R, int HC, bool LOOP = false>
+// KEYED (the forward that opens an iteration with its batch's keys drawn ahead, mlp3_fwd_split_riders_kernel): row m of the
+// input is not read from a.x but from the replay ring -- row keys[m] of `lo` for m < B, row keys[m - B] of `hi` above (the
+// batch's s' stacked over its s, rrl_fwd_riders_t.gather) -- the values the gather writes to a.x in the same launch.
+struct RowKeys {
+    const uint32_t* keys;     // null: a.x is read as in every other kernel
+    const float* lo; const float* hi;   // [cap, 2]
+    int B;
+    uint32_t last;            // cap - 1
+};
+
+template <int R, int HC, bool LOOP = false, bool KEYED = false>
 __device__ __forceinline__ void mlp3_fwd_split_body(const StackArgs& a, float* partial, int bx, int g, int z, int G,
-                                                    float* h1s, float* h2s, int nb = 1, int tiles = 1, float* xs_own = nullptr) {
+                                                    float* h1s, float* h2s, int nb = 1, int tiles = 1, float* xs_own = nullptr,
+                                                    const RowKeys* rk = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (wave-uniform, and the compiler may know it)
     constexpr int kW = 4;                                // waves per workgroup
@@ -268,6 +280,20 @@ __device__ __forceinline__ void mlp3_fwd_split_body(const StackArgs& a, float* p
     // raw input of a block, lane (i, q): row 16 t + i, column min(q, din - 1) (lanes q >= din are zeroed behind the input head)
     const auto load_x = [&](int blk, float (&x)[R]) {
         const int i = lane & 15, q = lane >> 4, m0 = blk * (R * kStackRows);
+        if (KEYED && rk->keys) {
+            const float* lo = rk->lo;
+            const float* hi = rk->hi;
+            rrl_pack::to_global_all(lo, hi);
+#pragma unroll
+            for (int t = 0; t < R; ++t) {
+                const int m = m0 + min(16 * t + i, M - 1 - m0);
+                const bool upper = m >= rk->B;
+                const unsigned e = 2u * min(rk->keys[upper ? m - rk->B : m], rk->last) + unsigned(min(q, din - 1));
+                const float v_lo = lo[e], v_hi = hi[e];          // (both requested: a select of the two pointers is not global)
+                x[t] = upper ? v_hi : v_lo;
+            }
+            return;
+        }
         const float* const xblk = a.x + (long long)m0 * a.ldx;
 #pragma unroll
         for (int t = 0; t < R; ++t) x[t] = xblk[unsigned(min(16 * t + i, M - 1 - m0) * a.ldx + min(q, din - 1))];
@@ -589,6 +615,47 @@ __global__ __launch_bounds__(256, 4) void mlp3_fwd_split_flat_group_kernel(Stack
         mlp3_fwd_split_body<kBigR, 256>(a, partial, bx, rest % G, rest / G, G, lds, lds);
 }
 
+// ONE stack with rider workgroups in front of its tiles (rrl_mlp3_forward_riders): replay draws and the noise fill that
+// nothing in this launch waits for -- each rider is the body of the draw launch it replaces, on a workgroup of its own -- and,
+// with keys drawn ahead, the forward's rows read through them (RowKeys).  The riders come first on the grid: the index
+// selection is the longest dependent chain of the launch.
+struct FwdRiders {
+    DrawArgs sel;            // select half of a uniform draw, `rows_ahead` rows before they are pushed -> sel_keys
+    long long rows_ahead;
+    uint32_t* sel_keys;
+    DrawArgs gat;            // gather half for the keys gat_keys
+    const uint32_t* gat_keys;
+    DrawArgs second;         // a whole draw (any mode)
+    NoiseArgs nz;
+    int slot_sel, slot_gat, slot_second, slot_noise;      // first workgroup of each rider, -1: absent
+    int n;                   // rider workgroups
+};
+
+template <int R>
+__global__ __launch_bounds__(256, 4) void mlp3_fwd_split_riders_kernel(StackArgs a, float* partial, int G, int tiles, RowKeys rk,
+                                                                       FwdRiders rd) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int x = blockIdx.x;
+    if (x < rd.n) {
+        char* smem = reinterpret_cast<char*>(lds);
+        if (x == rd.slot_sel)
+            select_ahead_body(rd.sel.rb, rd.sel.B, rd.sel.seed, rd.sel.counter, rd.sel.counter_dev, rd.sel.table_mask,
+                              rd.rows_ahead, rd.sel_keys, smem);
+        else if (x == rd.slot_gat)
+            gather_ahead_body(rd.gat.rb, rd.gat.B, rd.gat.counter, rd.gat.counter_dev, rd.gat.counter_inc, rd.gat_keys,
+                              rd.gat.out);
+        else if (x == rd.slot_second) draw_body(rd.second, smem);
+        else noise_body(rd.nz, x - rd.slot_noise);
+        return;
+    }
+    arrive_together(a.M, a.H, a.din, a.dout, a.ldx, a.use_in_head, a.in_head.kind, a.in_head.n_part, a.in_head.part_stride,
+                    a.in_head.ld_action, a.in_head.min_log_std, G, tiles, rk.B, rk.last);
+    const int local = x - rd.n;
+    const int bx = local % tiles, rest = local / tiles;
+    float* h2s = R > 1 ? lds : lds + R * kStackRows * (kStackMaxH + kSplitPad);
+    mlp3_fwd_split_body<R, 256, false, true>(a, partial, bx, rest % G, rest / G, G, lds, h2s, 1, 1, nullptr, &rk);
+}
+
 // the same launch for S seeds (pack.hpp): grid (workgroups of the seeds' largest members under the XCD-aware placement,
 // members) -- blockIdx.y IS the member and the seed follows from blockIdx.x by arithmetic, so the member's argument block
 // sits at an address known at wave start: one batch of scalar loads from the plan's device copy, as in the solo launch
@@ -802,6 +869,66 @@ int rrl_mlp3_forward_multi(int n, const rrl_stack_t* st, void* stream) {
         hipLaunchKernelGGL(mlp3_fwd_split_flat_group_kernel, dim3(sg.first[n]), dim3(256), lds_floats * 4, s, sg);
     } else if (path == 1) hipLaunchKernelGGL((mlp3_fwd_group_kernel<1>), dim3(sg.first[n]), dim3(1024), 0, s, sg);
     else hipLaunchKernelGGL((mlp3_fwd_group_kernel<2>), dim3(sg.first[n]), dim3(1024), 0, s, sg);
+    return check_launch();
+}
+
+int rrl_mlp3_forward_riders(const rrl_stack_t* stack, const rrl_fwd_riders_t* riders, void* stream) {
+    if (!stack || !riders) return RRL_EINVAL;
+    StackGroup sg;
+    int path;
+    int rc = build_stack_group(1, stack, sg, path);
+    if (rc != RRL_OK) return rc;
+    if ((path != 0 && path != 3) || stack->H != 256) return RRL_EINVAL;      // the column-split kernels at hidden width 256
+    FwdRiders rd{};
+    RowKeys rk{};
+    rd.slot_sel = rd.slot_gat = rd.slot_second = rd.slot_noise = -1;
+    size_t lds = split_lds_floats(path == 0 ? 1 : kBigR) * 4;
+    // every rider runs on the forward's 256-thread workgroups (a draw's results do not depend on the workgroup size)
+    const auto rider = [&](const rrl_draw_t* d, DrawArgs& a, int& slot) {
+        int threads = 0;
+        size_t l = 0;
+        const int r = draw_setup(*d, a, threads, l);
+        if (r != RRL_OK) return r;
+        if (threads > 256) return int(RRL_ERANGE);
+        lds = l > lds ? l : lds;
+        slot = rd.n++;
+        return int(RRL_OK);
+    };
+    if (riders->select) {
+        const rrl_draw_ahead_t& s = *riders->select;
+        if (!s.draw || !s.keys || s.rows_ahead < 0 || s.draw->stratified != RRL_DRAW_UNIFORM) return RRL_EINVAL;
+        if ((rc = rider(s.draw, rd.sel, rd.slot_sel)) != RRL_OK) return rc;
+        rd.rows_ahead = s.rows_ahead;
+        rd.sel_keys = s.keys;
+    }
+    if (riders->gather) {
+        const rrl_draw_ahead_t& s = *riders->gather;
+        if (!s.draw || !s.keys || s.draw->stratified != RRL_DRAW_UNIFORM) return RRL_EINVAL;
+        if ((rc = rider(s.draw, rd.gat, rd.slot_gat)) != RRL_OK) return rc;
+        rd.gat_keys = s.keys;
+        // the stack's rows are the batch's s' over its s, read from the ring through the keys
+        if (stack->M != 2 * rd.gat.B || stack->din != 2 || stack->use_in_head) return RRL_EINVAL;
+        rk = RowKeys{s.keys, rd.gat.rb.s2, rd.gat.rb.s, rd.gat.B, uint32_t(rd.gat.rb.cap - 1)};
+    }
+    if (riders->second && (rc = rider(riders->second, rd.second, rd.slot_second)) != RRL_OK) return rc;
+    if (riders->noise_pairs < 0 || riders->noise_pairs >= (1LL << 32) || (riders->noise_pairs > 0 && !riders->noise_out))
+        return RRL_EINVAL;
+    if (riders->noise_pairs > 0) {
+        rd.nz = NoiseArgs{riders->noise_pairs, riders->noise_seed, riders->noise_counter, riders->noise_counter_dev,
+                          riders->noise_counter_inc, riders->noise_out, 0};
+        noise_blocks(rd.nz, 256);
+        rd.slot_noise = rd.n;
+        rd.n += rd.nz.blocks;
+    }
+    if (lds > 64 * 1024) return RRL_ERANGE;          // (a stratified rider's tables at the largest capacity are 18 KB)
+    const dim3 grid(unsigned(rd.n + sg.first[1]));
+    hipStream_t s = (hipStream_t)stream;
+    if (path == 0)
+        hipLaunchKernelGGL(mlp3_fwd_split_riders_kernel<1>, grid, dim3(256), lds, s, sg.a[0], sg.partial[0], sg.G[0],
+                           sg.tiles[0], rk, rd);
+    else
+        hipLaunchKernelGGL(mlp3_fwd_split_riders_kernel<kBigR>, grid, dim3(256), lds, s, sg.a[0], sg.partial[0], sg.G[0],
+                           sg.tiles[0], rk, rd);
     return check_launch();
 }
 

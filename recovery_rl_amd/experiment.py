@@ -72,6 +72,9 @@ class VectorLoop:
         self._graph_updates = (0, 0)
         self._actor = None
         self.carry_actor = os.environ.get("RRL_CARRY_ACTOR", "1") != "0"
+        # the task batch's keys selected one step ahead, no draw launch (FastUpdater.update_pair); RRL_DRAW_AHEAD=0: off
+        self.draw_ahead = os.environ.get("RRL_DRAW_AHEAD", "1") != "0"
+        self._graph_ahead = False
         # vectorisation rule 5: at N > 1 an env's CEM warm start does not survive its episode (MPC.forget_plans)
         self.forget_plans = bool(recovery_policy is not None and self.n > 1 and hasattr(recovery_policy, "forget_plans")
                                  and not getattr(cfg, "keep_plan_warm_start", False))
@@ -109,7 +112,8 @@ class VectorLoop:
                 with trace_range("sample+sac_update+qrisk_update"):
                     fast.update_pair(self.memory, self.recovery_memory if online_qrisk else None,
                                      rider=rider if u == cfg.updates_per_step - 1 else None,
-                                     nu=self.nu_schedule(i_episode))
+                                     nu=self.nu_schedule(i_episode),
+                                     draw_ahead=self.draw_ahead and cfg.updates_per_step == 1)
                 self.host_updates[0] += 1
                 if online_qrisk:
                     qr.updates += 1
@@ -308,6 +312,7 @@ class VectorLoop:
             rc = env.lib.rrl_nav_step_push_x(env.kind, C.byref(a), _lib.current_stream())
         _lib.check(rc, "rrl_step_push_x")
         mem._len = min(mem._len + self.n, mem.capacity)
+        mem.ahead.stepped(self.n)              # keys drawn ahead were drawn for exactly this push
         if use_rmem:
             rmem._len = min(rmem._len + self.n, rmem.capacity)
         if self.forget_plans:
@@ -374,6 +379,10 @@ class VectorLoop:
                     self.vector_step(True, False, online_qrisk)
             return g
         g = record(1)
+        # the captured iteration takes its task batch through keys drawn ahead and leaves the next one's (replay needs them)
+        fast = getattr(self.agent, "fast", None)
+        self._graph_ahead = bool(fast is not None and fast.keyed)
+        self._graph_online_qrisk = online_qrisk
         # which of the env's two state representations (status word / t + flag arrays) the captured kernels read and write
         self._graph_status_live = getattr(self.env, "_status_live", None)
         self._graph_updates = (self.host_updates[0] - saved[2][0], self.host_updates[1] - saved[2][1])
@@ -403,10 +412,25 @@ class VectorLoop:
             raise RuntimeError("the env's live state representation changed since the graph was captured "
                                "(status word live: %r at capture, %r now); capture again"
                                % (self._graph_status_live, getattr(self.env, "_status_live", None)))
+        if self._eager_for_keys():
+            return self.vector_step(True, False, self._graph_online_qrisk)
         self.graph.replay()
         self.obs, self._last_recovery, self._last_real_action = self._graph_out
         self._advance_mirrors(1)
         return self.obs
+
+    def _eager_for_keys(self):
+        """Keys drawn ahead are device state the captured iteration consumes and renews.  Something outside the loop
+        dropped them since the last iteration (an eager push / sample, a checkpoint load: replay_memory.DrawAhead): this
+        iteration runs eagerly -- stand-alone draw, keys for the next one -- and the graphs take over again.  A graph
+        captured without them leaves none behind either."""
+        ahead = getattr(self.memory, "ahead", None)
+        if ahead is None:
+            return False
+        if not self._graph_ahead:
+            ahead.drop()
+            return False
+        return not ahead.ready(self.cfg.batch_size)
 
     def _advance_mirrors(self, iterations):
         self.total_numsteps += self.n * iterations
@@ -423,6 +447,9 @@ class VectorLoop:
         """`iterations` steady-state iterations from the captured graphs: the many-iteration graph while that many remain, single
         iterations for the rest.  The same launches in the same order as `iterations` calls of replay()."""
         k = self.graph_many_iters if self.graph_many is not None else 0
+        if iterations > 0 and self._eager_for_keys():
+            self.vector_step(True, False, self._graph_online_qrisk)
+            iterations -= 1
         while k > 1 and iterations >= k:
             if getattr(self.env, "_status_live", None) != self._graph_status_live:
                 break                                      # replay() raises with the explanation

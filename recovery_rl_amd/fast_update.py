@@ -480,6 +480,7 @@ class FastUpdater:
         self.sync_world, self._avg, self.sac_bucket = 1, None, None
         self.fuse_loss = True      # loss gradients computed inside the head-backward kernels (no grad launches)
         self._noise = None
+        self.keyed = False         # the last update pair took its task batch through keys drawn ahead (update_pair)
         self._noise_buf, self._actor_noise, self._actor_noise_fresh = None, None, False
         self.actor_rows = 0
         self.noise_seed = (int(getattr(agent, "seed", 0)) ^ 0x6E6F697365) & 0xFFFFFFFFFFFFFFFF
@@ -717,14 +718,43 @@ class FastUpdater:
                                       p(self.rbias), p(action_view), action_view.stride(0), None, None, None, None,
                                       p(self.recpolicy.p["log_std"]), float(self.qr.policy.min_log_std))
 
-    def update_pair(self, memory, recovery_memory, rider=None, nu=None):
+    def can_draw_ahead(self):
+        """The task batch's keys can be selected one env step ahead and the draw launch dissolved into the first policy
+        forward's (rrl_mlp3_forward_riders): solo launches (no tape: the seed packer records the stand-alone launches), the
+        column-split kernels at hidden width 256, batches that fit the forward's 256-thread workgroups."""
+        return bool(_TAPE is None and self.grouped and self.sync_world == 1 and self.B <= 256 and self.pol_ab.split
+                    and self.policy.H == 256 and self.recpolicy.H == 256)
+
+    def select_ahead(self, desc, memory, rows):
+        """The forward `desc` (the acting pass's recovery-policy forward, which precedes the env step) with the select half
+        of the NEXT iteration's task-batch draw as a rider workgroup: the keys for the ring as it will be once the step has
+        pushed its `rows` rows.  Nothing observable moves (the tick advances with the gather half)."""
+        d, _ = memory.draw_desc(self.B, rows=self.rows, ahead=rows)
+        sel = _lib.rrl_draw_ahead_t(C.pointer(d), rows, _lib.ptr(memory.ahead_keys(self.B)))
+        riders = _lib.rrl_fwd_riders_t(C.pointer(sel), None, None, 0, 0, 0, None, 0, None)
+        self._check(self.lib.rrl_mlp3_forward_riders(C.byref(desc), C.byref(riders), _lib.current_stream()),
+                    "rrl_mlp3_forward_riders")
+        memory.ahead.selected(self.B, rows)
+
+    def update_pair(self, memory, recovery_memory, rider=None, nu=None, draw_ahead=False):
         """One SAC update and (recovery_memory not None) one Q_risk + recovery-policy update of a lock-step iteration
         (experiment.py:397-416): both replay draws and the iteration's policy noise in ONE launch, then the two
         updates on the grouped kernels.  Same draws, same arithmetic, same parameters as the separate calls.
         `rider` = (FastActor, obs): the acting pass that follows this update takes two of its three forwards along in the
         Q_risk update's launches (FastActor.ride_*; the LAST update pair of an iteration only).
-        `nu`: the multiplier of the Lagrangian term (--DGD_constraints), the value SAC.update_parameters is passed."""
+        `nu`: the multiplier of the Lagrangian term (--DGD_constraints), the value SAC.update_parameters is passed.
+        `draw_ahead` (one update pair per iteration, VectorLoop.draw_ahead): with the task batch's keys selected ahead
+        and still valid (replay_memory.DrawAhead) there is no draw launch -- the first policy forward reads its rows
+        through the keys and takes the gather, the safety buffer's draw and the noise fill along as rider workgroups
+        -- and the acting pass of `rider` selects the next iteration's keys.  Same keys, same rows, same ticks."""
         B, qr = self.B, self.qr
+        ahead_ok = bool(draw_ahead and rider is not None and self.can_draw_ahead())
+        keyed = memory.ahead.take(B) and ahead_ok
+        # a captured iteration is replayed as it is: it selects ahead only if it also consumed keys
+        rider_selects = ahead_ok and (keyed or not torch.cuda.is_current_stream_capturing())
+        if rider is not None:
+            rider[0].select_for = (memory, rider[0].n) if rider_selects and len(memory) + rider[0].n >= B else None
+        self.keyed = keyed
         d1, batch = memory.draw_desc(B, rows=self.rows)
         d2 = batch_q = None
         if recovery_memory is not None:
@@ -734,31 +764,41 @@ class FastUpdater:
         need = 4 * B * 2 + 2 * n_act * 2
         if self._noise_buf is None or self._noise_buf.numel() != need:
             self._noise_buf = torch.zeros(need, dtype=torch.float32, device=self.dev)
-        record("sample", _lib.rrl_sample_args_t(C.pointer(d1), C.pointer(d2) if d2 is not None else None, need // 2,
-                                                self.noise_seed, 0, _lib.ptr(self.noise_tick), 1,
-                                                _lib.ptr(self._noise_buf)), d1, d2)
-        self._check(self.lib.rrl_sample_multi(C.byref(d1), C.byref(d2) if d2 is not None else None, need // 2,
-                                              self.noise_seed, 0, _lib.ptr(self.noise_tick), 1,
-                                              _lib.ptr(self._noise_buf), _lib.current_stream()), "rrl_sample_multi")
+        if keyed:
+            gat = _lib.rrl_draw_ahead_t(C.pointer(d1), 0, _lib.ptr(memory.ahead_keys(B)))
+            riders = _lib.rrl_fwd_riders_t(None, C.pointer(gat), C.pointer(d2) if d2 is not None else None, need // 2,
+                                           self.noise_seed, 0, _lib.ptr(self.noise_tick), 1, _lib.ptr(self._noise_buf))
+            desc = self.pol_ab.forward_desc(self.x_pol[:, 0:2])
+            self._check(self.lib.rrl_mlp3_forward_riders(C.byref(desc), C.byref(riders), _lib.current_stream()),
+                        "rrl_mlp3_forward_riders")
+        else:
+            record("sample", _lib.rrl_sample_args_t(C.pointer(d1), C.pointer(d2) if d2 is not None else None, need // 2,
+                                                    self.noise_seed, 0, _lib.ptr(self.noise_tick), 1,
+                                                    _lib.ptr(self._noise_buf)), d1, d2)
+            self._check(self.lib.rrl_sample_multi(C.byref(d1), C.byref(d2) if d2 is not None else None, need // 2,
+                                                  self.noise_seed, 0, _lib.ptr(self.noise_tick), 1,
+                                                  _lib.ptr(self._noise_buf), _lib.current_stream()), "rrl_sample_multi")
         self._noise = self._noise_buf[:4 * B * 2].view(4, B, 2)
         self._actor_noise = self._noise_buf[4 * B * 2:].view(2, n_act, 2) if n_act else None
         self._actor_noise_fresh = n_act > 0
         n = self._noise
-        self.sac_update_grouped(batch, n[0], n[1], nu=nu)
+        self.sac_update_grouped(batch, n[0], n[1], nu=nu, policy_forwarded=keyed)
         if recovery_memory is not None:
             self.qrisk_update_grouped(batch_q, n[2], n[3], rider=rider)
         return self.losses
 
-    def sac_update_grouped(self, batch, eps_next, eps_pi, nu=None):
+    def sac_update_grouped(self, batch, eps_next, eps_pi, nu=None, policy_forwarded=False):
         """sac_update with 11 launches instead of 17 (rows already written by the draw).  The comparison algorithms'
         Q_risk forwards join the critic forwards' launch (a second one when both (s, pi) and (s, a) are needed: four
         members at most), their backward the critic backwards' launch, the duals the optimiser launch; the RCPO
-        penalty is one launch more."""
+        penalty is one launch more.  `policy_forwarded`: the policy forward on (s', s) ran in the caller's launch."""
         ag, B = self.agent, self.B
         nu = self._nu(nu)
         s, a, r, s2, m = batch
         r, m = r.reshape(-1), m.reshape(-1)
-        if self.pol_ab.split:      # one-member group: the stand-alone launch's kernel body, and a launch the tape can pack
+        if policy_forwarded:
+            pass
+        elif self.pol_ab.split:    # one-member group: the stand-alone launch's kernel body, and a launch the tape can pack
             forward_multi([self.pol_ab.forward_desc(self.x_pol[:, 0:2])])
         else:
             self.pol_ab.forward(self.x_pol[:, 0:2])
@@ -1009,6 +1049,7 @@ class FastActor:
         self.task_action, self.rec_action, self.real_action = z(n, 2), z(n, 2), z(n, 2)
         self.recovery = torch.zeros(n, dtype=torch.uint8, device=dev)
         self._ride = None
+        self.select_for = None          # (task buffer, rows): the next draw's keys are selected in this pass's last forward
 
     # -- two of the three forwards of act(defer_select=True) as riders of the Q_risk update's launches -----------------------
     def ride_policy(self, obs):
@@ -1034,7 +1075,11 @@ class FastActor:
         f, r = self.f, self._ride
         self._ride = None
         assert r["qrisk"] and obs is r["obs"], "the acting pass of a ride must follow its two riders, on the same observations"
-        forward_multi([self.rec.forward_desc(obs, save=False)])
+        sel, self.select_for = self.select_for, None
+        if sel is not None:
+            f.select_ahead(self.rec.forward_desc(obs, save=False), *sel)
+        else:
+            forward_multi([self.rec.forward_desc(obs, save=False)])
         rec_head = f._stoch_desc(self.rec.parts, r["noise"][1], self.rec_action, n=self.n)
         zq, zn, zs = self.qr.parts
         self.pending_select = (zq, zn, zs, float(eps_safe), None, rec_head)

@@ -13,6 +13,42 @@ import torch
 from . import _lib
 
 
+class DrawAhead:
+    """Host-side validity of keys drawn ahead for a ring (rrl_draw_select / rrl_fwd_riders_t.select): the keys of the next
+    uniform draw of B rows, selected BEFORE the env step whose `rows` rows that draw will see.  They fit exactly one
+    situation -- the tick they were drawn at, the ring after exactly that step -- so they are usable only when that one step
+    (`stepped`) and nothing else happened to the ring since `selected`; everything else that touches the ring or its tick
+    (push, sample, a draw, a checkpoint load: `drop`) discards them, which costs nothing: selecting advances no tick and
+    raises no flag, the next draw is simply the stand-alone launch.  No device state: exercised on the CPU."""
+
+    def __init__(self):
+        self.pending = None               # [B, rows, stepped]
+
+    def selected(self, B, rows):
+        self.pending = [int(B), int(rows), False]
+
+    def stepped(self, rows):
+        """The fused env step pushed `rows` rows: the one event the pending keys were drawn for, once."""
+        p = self.pending
+        if p is not None and not p[2] and p[1] == int(rows):
+            p[2] = True
+        else:
+            self.pending = None
+
+    def drop(self):
+        self.pending = None
+
+    def ready(self, B):
+        p = self.pending
+        return p is not None and p[2] and p[0] == int(B)
+
+    def take(self, B):
+        """True if the draw of B rows that starts now may use the pending keys; none are pending afterwards."""
+        ok = self.ready(B)
+        self.pending = None
+        return ok
+
+
 class ReplayMemory:
     """Ring buffer for the SAC task policy (replay_memory.py:11-33)."""
 
@@ -48,6 +84,8 @@ class ReplayMemory:
         self._len_exact = True
         self._scratch = None
         self._out = {}
+        self.ahead = DrawAhead()
+        self._keys = {}
 
     def pin(self, rows=None):
         """Never overwrite rows [0, rows) (default: everything stored so far): past the last slot the ring continues at
@@ -84,6 +122,7 @@ class ReplayMemory:
         """Append N rows (row i = env i). `done` is the reference's 5th tuple field: the
         bootstrap mask float(not done) (experiment.py:434,439)."""
         n = int(reward.shape[0])
+        self.ahead.drop()
         for x in (state, action, reward, next_state, done):
             assert x.dtype == torch.float32 and x.is_contiguous() and x.device == self.s.device
         scratch = None
@@ -136,6 +175,7 @@ class ReplayMemory:
         Returns persistent batch tensors (overwritten by the next sample of the same size).
         `rows` = (xu, x2u, xpu) [B,4] buffers that additionally receive (s,a), (s',-,-), (s,-,-)."""
         B = int(batch_size)
+        self.ahead.drop()
         if self._len_exact and B > self._len:
             raise ValueError("Sample larger than population or is negative")
         s, a, r, s2, m, idx = out if out is not None else self._batch(B)
@@ -149,14 +189,16 @@ class ReplayMemory:
         return s, a, r, s2, m
 
 
-    def draw_desc(self, batch_size, pos_fraction=None, out=None, rows=None, demo_share=None):
+    def draw_desc(self, batch_size, pos_fraction=None, out=None, rows=None, demo_share=None, ahead=0):
         """The arguments of sample() as an rrl_draw_t for rrl_sample_multi (several draws in one launch) and the batch
-        tensors it fills.  Same checks, same tick, same rows as sample()."""
+        tensors it fills.  Same checks, same tick, same rows as sample().  `ahead`: the draw's select half runs now, for
+        the ring as it will be `ahead` pushed rows from now (select_ahead); its population check is the gather half's."""
         B = int(batch_size)
+        self.ahead.drop()
         s, a, r, s2, m, idx = out if out is not None else self._batch(B)
         xu, x2u, xpu = rows if rows is not None else (None, None, None)
         if pos_fraction is None:
-            if self._len_exact and B > self._len:
+            if self._len_exact and B > min(self._len + ahead, self.capacity):
                 raise ValueError("Sample larger than population or is negative")
             if demo_share:
                 stratified, n_pos = _lib.DRAW_DEMO_SHARE, int(B * demo_share)
@@ -170,6 +212,13 @@ class ReplayMemory:
         d = _lib.rrl_draw_t(C.pointer(self._desc), stratified, n_pos, n_neg, self.seed, 0, p(self.tick), 1, p(s), p(a),
                             p(r), p(s2), p(m), p(idx), p(xu), p(x2u), p(xpu))
         return d, (s, a, r, s2, m)
+
+    def ahead_keys(self, batch_size):
+        """The device buffer of the keys drawn ahead for batches of this size (B keys + RRL_AHEAD_META words)."""
+        B = int(batch_size)
+        if B not in self._keys:
+            self._keys[B] = torch.zeros(B + _lib.AHEAD_META, dtype=torch.int32, device=self.device)
+        return self._keys[B]
 
 
 class ConstraintReplayMemory(ReplayMemory):
@@ -199,6 +248,7 @@ class ConstraintReplayMemory(ReplayMemory):
         if pos_fraction is None:
             return super().sample(batch_size, out=out, rows=rows)
         B = int(batch_size)
+        self.ahead.drop()
         n_pos = int(B * pos_fraction)          # replay_memory.py:56-57
         n_neg = B - n_pos
         s, a, r, s2, m, idx = out if out is not None else self._batch(B)
@@ -213,6 +263,7 @@ class ConstraintReplayMemory(ReplayMemory):
 
     def _sample_split(self, batch_size, demo_share, out, rows):
         B = int(batch_size)
+        self.ahead.drop()
         if self._len_exact and B > self._len:
             raise ValueError("Sample larger than population or is negative")
         n_demo = int(B * demo_share)
