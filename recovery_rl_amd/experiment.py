@@ -324,7 +324,7 @@ class VectorLoop:
     # -- whole iteration -----------------------------------------------------------------------
     def actor_rider(self, do_update, random_actions, online_qrisk):
         """(FastActor, obs) when the acting pass that follows this iteration's updates can take its task-policy and Q_risk
-        forwards along in the Q_risk update's launches (FastUpdater.qrisk_update_grouped): the grouped fused updates with an
+        forwards along in the Q_risk update's launches (FastUpdater.qrisk_update, grouped): the grouped fused updates with an
         online Q_risk update, the fused acting pass with the gate in the step kernel, on the loop's own observations.
         `carry_actor = False` (or RRL_CARRY_ACTOR=0) keeps the acting pass's own two launches (A/B and the bit-identity test)."""
         cfg = self.cfg

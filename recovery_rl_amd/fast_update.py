@@ -225,6 +225,7 @@ class Stack:
         z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         self.h1, self.h2, self.out = z(G, B, H), z(G, B, H), z(G, B, net.dout)
         self.dh1, self.dh2, self.dx = z(G, B, H), z(G, B, H), z(G, B, net.din)
+        self.dOut = z(G, B, net.dout)               # a loss gradient that comes from a launch of its own (loss_dout)
         # partial last-layer sums of the small-batch forward: rrl_mlp3_is_split = number of parts (0: not split)
         self.nsplit = int(_lib.load().rrl_mlp3_is_split(B, H)) if mlp3_supported(H, net.din, net.dout) else 0
         self.split = self.nsplit > 0
@@ -335,10 +336,13 @@ class Stack:
                                    p(self.dx) if input_grad else None)
         return head, hidden, inp
 
-    def backward(self, dout, weight_grads=True, input_grad=False):
+    def backward(self, dout, weight_grads=True, input_grad=False, fuse_loss=True):
         """dout: [G, B, dout] tensor, or an rrl_loss_t describing how the kernel computes it itself
-        (rrl_mlp_head_backward_loss).  Writes parameter gradients into net.g (weight_grads) and/or returns
-        dL/dx per head [G, B, din] (input_grad)."""
+        (rrl_mlp_head_backward_loss; fuse_loss = False: how the stand-alone launch of its kind computes it first,
+        loss_dout).  Writes parameter gradients into net.g (weight_grads) and/or returns dL/dx per head [G, B, din]
+        (input_grad)."""
+        if not fuse_loss and isinstance(dout, _lib.rrl_loss_t):
+            dout = loss_dout(dout, self.B, self.dOut)
         if self.fuse_first:             # head backward, then hidden + first layer in one launch (rrl_first_layer_t)
             backward_multi([self.backward_descs(dout, weight_grads, input_grad)])
             return self.dx_part if input_grad else None
@@ -408,6 +412,50 @@ def heads_multi(heads):
                "rrl_policy_heads_fwd_multi")
 
 
+# -- the stand-alone launch of a descriptor: the same operands field for field, the same bits (include/rrl_hip.h) -----
+def head_forward(hd):
+    """One rrl_policy_head_t as a launch of its own (rrl_gauss_head_fwd / rrl_stoch_head_fwd)."""
+    lib, st = _lib.load(), _lib.current_stream()
+    if hd.kind == _lib.HEAD_GAUSS:
+        _lib.check(lib.rrl_gauss_head_fwd(hd.B, hd.head, hd.n_part, hd.part_stride, hd.eps, hd.scale, hd.bias, hd.action,
+                                          hd.ld_action, hd.logp, hd.mean_out, hd.obs_in, hd.obs_out, st),
+                   "rrl_gauss_head_fwd")
+    else:
+        _lib.check(lib.rrl_stoch_head_fwd(hd.B, hd.head, hd.n_part, hd.part_stride, hd.eps, hd.log_std, hd.min_log_std,
+                                          hd.scale, hd.bias, hd.action, hd.ld_action, hd.mean_out, st),
+                   "rrl_stoch_head_fwd")
+
+
+def loss_dout(loss, B, dout):
+    """The gradient an rrl_loss_t describes, written into the tensor `dout` [G, B, dout] by the stand-alone launch of its
+    kind (rrl_*_grad for the critic-loss kinds, rrl_*_head_bwd for the policy-head kinds) instead of inside the
+    head-backward kernel: what FastUpdater.fuse_loss = False runs.  -> dout, for Stack.backward to read."""
+    lib, st, L, d = _lib.load(), _lib.current_stream(), loss, dout.data_ptr()
+    out = (L.out, L.n_part, L.part_stride)
+    if L.kind == _lib.LOSS_SAC_CRITIC:
+        rc, what = lib.rrl_sac_critic_grad(B, L.out, L.out_t, L.n_part, L.part_stride, L.v0, L.v1, L.v2, L.f0, L.alpha,
+                                           L.v3, d, L.loss, st), "rrl_sac_critic_grad"
+    elif L.kind == _lib.LOSS_SAC_POLICY:
+        rc, what = lib.rrl_sac_policy_grad(B, *out, L.v0, L.alpha, d, L.loss, st), "rrl_sac_policy_grad"
+    elif L.kind == _lib.LOSS_QRISK_CRITIC:
+        rc, what = lib.rrl_qrisk_critic_grad(B, L.out, L.out_t, L.n_part, L.part_stride, L.v0, L.v1, L.f0, d, L.loss,
+                                             st), "rrl_qrisk_critic_grad"
+    elif L.kind == _lib.LOSS_QRISK_POLICY:
+        rc, what = lib.rrl_qrisk_policy_grad(B, *out, d, L.loss, st), "rrl_qrisk_policy_grad"
+    elif L.kind == _lib.LOSS_DGD_QRISK:
+        rc, what = lib.rrl_dgd_qrisk_grad(B, *out, L.f0, d, L.loss, st), "rrl_dgd_qrisk_grad"
+    else:
+        # the head kernels read d_action as a plain tensor: the producing backward must have written dx, not partials
+        assert L.da_parts <= 1, "fuse_loss = False needs set_fuse_first(False)"
+        da = (L.d_action, L.ld, L.n_heads, L.head_stride)
+        if L.kind == _lib.LOSS_GAUSS_HEAD:
+            rc, what = lib.rrl_gauss_head_bwd(B, *out, L.v0, L.v1, *da, L.f0, d, st), "rrl_gauss_head_bwd"
+        else:
+            rc, what = lib.rrl_stoch_head_bwd(B, *out, L.v0, L.v1, L.f0, L.v2, *da, d, L.loss, st), "rrl_stoch_head_bwd"
+    _lib.check(rc, what)
+    return dout
+
+
 class StackRows(Stack):
     """Rows [lo, hi) of a single-head Stack whose forward ran on a taller batch (several inputs of the SAME
     network stacked along the batch: one launch instead of one per input).  Shares the parent's activations and
@@ -421,6 +469,7 @@ class StackRows(Stack):
         z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         self.h1, self.h2 = parent.h1[:, lo:hi], parent.h2[:, lo:hi]
         self.dh1, self.dh2, self.dx = z(1, self.B, H), z(1, self.B, H), z(1, self.B, parent.net.din)
+        self.dOut = z(1, self.B, parent.net.dout)
         self.pair_hidden = True
         self._folded = False
         self._init_first(dev, 1, self.B, H, parent.net.din)
@@ -461,7 +510,7 @@ class FastUpdater:
         self.cri_a, self.cri_b = Stack(self.critic, B), Stack(self.critic, B)
         self.qr_a, self.qr_b = Stack(self.qrisk, B), Stack(self.qrisk, B)
         self.rec_a = Stack(self.recpolicy, B)
-        # grouped launches evaluate the target networks in the same launch as the online ones: own workspaces
+        # the target networks are evaluated in the same set of forwards as the online ones: own workspaces
         self.cri_t, self.qr_t = Stack(self.critic, B), Stack(self.qrisk, B)
         # kernels that do not depend on each other share launches (rrl_*_multi): the grouped entry points exist for the
         # one-launch stack forward only (H % 16 == 0, H <= 256, <= 4 inputs / outputs); other widths (--hidden_size 512)
@@ -474,8 +523,6 @@ class FastUpdater:
         self.x_pol = z(2 * B, 4)                                    # [s' | a'] stacked on [s | pi]
         self.x2u, self.xpu = self.x_pol[:B], self.x_pol[B:]
         self.logp2, self.logp = z(B), z(B)
-        self.dq, self.dhead, self.draw = z(2, B, 1), z(1, B, 4), z(1, B, 2)
-        self.dact = z(B, 2)
         self.losses = z(8)   # q1, q2, policy, (pad) | qr1, qr2, recpolicy, (pad)
         self.sync_world, self._avg, self.sac_bucket = 1, None, None
         self.fuse_loss = True      # loss gradients computed inside the head-backward kernels (no grad launches)
@@ -503,7 +550,6 @@ class FastUpdater:
         self.qr_p, self.qr_sa = Stack(self.qrisk, B), Stack(self.qrisk, B)
         self.penalty = z(B)
         self.dual_stats = z(4)          # mean max sigmoid(z) at (s, pi) | at (s, a) | Lagrangian policy loss | (pad)
-        self.dq_r = z(2, B, 1)
         # the multipliers the kernels read and the dual step writes: persistent float32 device scalars (SAC._set_dual keeps
         # writing them in place)
         if self.update_nu and not torch.is_tensor(agent.nu):
@@ -570,9 +616,9 @@ class FastUpdater:
         t, n_part, ps = z
         record("unsupported", "rrl_rcpo_penalty")
         p = _lib.ptr
-        self._check(self.lib.rrl_rcpo_penalty(self.B, p(t), n_part, ps, p(self.agent.lambda_RCPO) if want_penalty else None,
-                                              p(self.penalty) if want_penalty else None, p(mean), _lib.current_stream()),
-                    "rrl_rcpo_penalty")
+        _lib.check(self.lib.rrl_rcpo_penalty(self.B, p(t), n_part, ps, p(self.agent.lambda_RCPO) if want_penalty else None,
+                                             p(self.penalty) if want_penalty else None, p(mean), _lib.current_stream()),
+                   "rrl_rcpo_penalty")
 
     def policy_loss(self):
         """The SAC policy loss statistic of the last update (with the Lagrangian term under --DGD_constraints, put together
@@ -643,35 +689,43 @@ class FastUpdater:
         return _lib.rrl_loss_t(kind, n_part, part_stride, p(out), p(out_t), p(v0), p(v1), p(v2), p(v3), p(alpha),
                                float(f0), ld, n_heads, hs, da, p(loss), parts, ps, group)
 
-    def _check(self, rc, what):
-        _lib.check(rc, what)
-
-    def _load_batch(self, batch, rows_loaded=False):
+    def _load_batch(self, batch, rows_loaded=False, rows=None):
         s, a, r, s2, m = batch
         if not rows_loaded:       # the sample-gather kernel normally writes these rows itself
-            self.xu[:, 0:2] = s
-            self.xu[:, 2:4] = a
-            self.x2u[:, 0:2] = s2
-            self.xpu[:, 0:2] = s
+            xu, x2u, xpu = rows or self.rows
+            xu[:, 0:2] = s
+            xu[:, 2:4] = a
+            x2u[:, 0:2] = s2
+            xpu[:, 0:2] = s
         return s, a, r.reshape(-1), s2, m.reshape(-1)
 
     @property
     def rows(self):
         return (self.xu, self.x2u, self.xpu)
 
-    def _fill_noise(self):
-        """ONE rrl_normal_fill launch per lock-step iteration: the 4 [B,2] draws of the two updates followed
-        by the 2 [N,2] draws of the acting pass (Philox stream RRL_STREAM_NOISE, device-side tick)."""
-        n_act = self.actor_rows
-        need = 4 * self.B * 2 + 2 * n_act * 2
+    @property
+    def rows_q(self):
+        return (self.xu_q, self.x2u_q, self.xpu_q)
+
+    def _noise_pairs(self):
+        """The noise buffer of one lock-step iteration: the 4 [B,2] draws of the two updates followed by the 2 [N,2]
+        draws of the acting pass.  Hands out its views for the fill the caller is about to launch; -> the number of
+        normal pairs that fill writes."""
+        n_act, n_upd = self.actor_rows, 4 * self.B * 2
+        need = n_upd + 2 * n_act * 2
         if self._noise_buf is None or self._noise_buf.numel() != need:
             self._noise_buf = torch.zeros(need, dtype=torch.float32, device=self.dev)
-        record("unsupported", "rrl_normal_fill")
-        self._check(self.lib.rrl_normal_fill(need // 2, self.noise_seed, 0, _lib.ptr(self.noise_tick), 1,
-                                             _lib.ptr(self._noise_buf), _lib.current_stream()), "rrl_normal_fill")
-        self._noise = self._noise_buf[:4 * self.B * 2].view(4, self.B, 2)
-        self._actor_noise = self._noise_buf[4 * self.B * 2:].view(2, n_act, 2) if n_act else None
+        self._noise = self._noise_buf[:n_upd].view(4, self.B, 2)
+        self._actor_noise = self._noise_buf[n_upd:].view(2, n_act, 2) if n_act else None
         self._actor_noise_fresh = n_act > 0
+        return need // 2
+
+    def _fill_noise(self):
+        """ONE rrl_normal_fill launch per lock-step iteration (Philox stream RRL_STREAM_NOISE, device-side tick)."""
+        pairs = self._noise_pairs()
+        record("unsupported", "rrl_normal_fill")
+        _lib.check(self.lib.rrl_normal_fill(pairs, self.noise_seed, 0, _lib.ptr(self.noise_tick), 1,
+                                            _lib.ptr(self._noise_buf), _lib.current_stream()), "rrl_normal_fill")
 
     def noise(self, which):
         """Policy noise for the two updates of one iteration (which = 0: the SAC update draws fresh noise for
@@ -691,18 +745,6 @@ class FastUpdater:
             self._fill_noise()
         self._actor_noise_fresh = False
         return self._actor_noise
-
-    def _gauss_fwd(self, head, eps, action_view, logp):
-        t, n_part, ps = head
-        self._check(self.lib.rrl_gauss_head_fwd(self.B, t.data_ptr(), n_part, ps, eps.data_ptr(),
-                                                self.scale.data_ptr(), self.bias.data_ptr(),
-                                                action_view.data_ptr(), action_view.stride(0), logp.data_ptr(),
-                                                None, None, None, _lib.current_stream()), "rrl_gauss_head_fwd")
-
-    # -- grouped path: the same kernels, independent ones sharing a launch ------------------------------------------
-    @property
-    def rows_q(self):
-        return (self.xu_q, self.x2u_q, self.xpu_q)
 
     def _gauss_desc(self, head, eps, action_view, logp, n=None, obs_in=None, obs_out=None):
         t, n_part, ps = head
@@ -732,8 +774,8 @@ class FastUpdater:
         d, _ = memory.draw_desc(self.B, rows=self.rows, ahead=rows)
         sel = _lib.rrl_draw_ahead_t(C.pointer(d), rows, _lib.ptr(memory.ahead_keys(self.B)))
         riders = _lib.rrl_fwd_riders_t(C.pointer(sel), None, None, 0, 0, 0, None, 0, None)
-        self._check(self.lib.rrl_mlp3_forward_riders(C.byref(desc), C.byref(riders), _lib.current_stream()),
-                    "rrl_mlp3_forward_riders")
+        _lib.check(self.lib.rrl_mlp3_forward_riders(C.byref(desc), C.byref(riders), _lib.current_stream()),
+                   "rrl_mlp3_forward_riders")
         memory.ahead.selected(self.B, rows)
 
     def update_pair(self, memory, recovery_memory, rider=None, nu=None, draw_ahead=False):
@@ -760,97 +802,68 @@ class FastUpdater:
         if recovery_memory is not None:
             d2, batch_q = recovery_memory.draw_desc(B, pos_fraction=qr.pos_fraction, rows=self.rows_q,
                                                     demo_share=qr.demo_share)
-        n_act = self.actor_rows
-        need = 4 * B * 2 + 2 * n_act * 2
-        if self._noise_buf is None or self._noise_buf.numel() != need:
-            self._noise_buf = torch.zeros(need, dtype=torch.float32, device=self.dev)
+        pairs = self._noise_pairs()
         if keyed:
             gat = _lib.rrl_draw_ahead_t(C.pointer(d1), 0, _lib.ptr(memory.ahead_keys(B)))
-            riders = _lib.rrl_fwd_riders_t(None, C.pointer(gat), C.pointer(d2) if d2 is not None else None, need // 2,
+            riders = _lib.rrl_fwd_riders_t(None, C.pointer(gat), C.pointer(d2) if d2 is not None else None, pairs,
                                            self.noise_seed, 0, _lib.ptr(self.noise_tick), 1, _lib.ptr(self._noise_buf))
             desc = self.pol_ab.forward_desc(self.x_pol[:, 0:2])
-            self._check(self.lib.rrl_mlp3_forward_riders(C.byref(desc), C.byref(riders), _lib.current_stream()),
-                        "rrl_mlp3_forward_riders")
+            _lib.check(self.lib.rrl_mlp3_forward_riders(C.byref(desc), C.byref(riders), _lib.current_stream()),
+                       "rrl_mlp3_forward_riders")
         else:
-            record("sample", _lib.rrl_sample_args_t(C.pointer(d1), C.pointer(d2) if d2 is not None else None, need // 2,
+            record("sample", _lib.rrl_sample_args_t(C.pointer(d1), C.pointer(d2) if d2 is not None else None, pairs,
                                                     self.noise_seed, 0, _lib.ptr(self.noise_tick), 1,
                                                     _lib.ptr(self._noise_buf)), d1, d2)
-            self._check(self.lib.rrl_sample_multi(C.byref(d1), C.byref(d2) if d2 is not None else None, need // 2,
-                                                  self.noise_seed, 0, _lib.ptr(self.noise_tick), 1,
-                                                  _lib.ptr(self._noise_buf), _lib.current_stream()), "rrl_sample_multi")
-        self._noise = self._noise_buf[:4 * B * 2].view(4, B, 2)
-        self._actor_noise = self._noise_buf[4 * B * 2:].view(2, n_act, 2) if n_act else None
-        self._actor_noise_fresh = n_act > 0
+            _lib.check(self.lib.rrl_sample_multi(C.byref(d1), C.byref(d2) if d2 is not None else None, pairs,
+                                                 self.noise_seed, 0, _lib.ptr(self.noise_tick), 1,
+                                                 _lib.ptr(self._noise_buf), _lib.current_stream()), "rrl_sample_multi")
         n = self._noise
-        self.sac_update_grouped(batch, n[0], n[1], nu=nu, policy_forwarded=keyed)
+        self.sac_update(batch, n[0], n[1], rows_loaded=True, nu=nu, grouped=True, policy_forwarded=keyed)
         if recovery_memory is not None:
-            self.qrisk_update_grouped(batch_q, n[2], n[3], rider=rider)
+            self.qrisk_update(batch_q, n[2], n[3], rows_loaded=True, rows=self.rows_q, grouped=True, rider=rider)
         return self.losses
 
-    def sac_update_grouped(self, batch, eps_next, eps_pi, nu=None, policy_forwarded=False):
-        """sac_update with 11 launches instead of 17 (rows already written by the draw).  The comparison algorithms'
-        Q_risk forwards join the critic forwards' launch (a second one when both (s, pi) and (s, a) are needed: four
-        members at most), their backward the critic backwards' launch, the duals the optimiser launch; the RCPO
-        penalty is one launch more.  `policy_forwarded`: the policy forward on (s', s) ran in the caller's launch."""
-        ag, B = self.agent, self.B
-        nu = self._nu(nu)
-        s, a, r, s2, m = batch
-        r, m = r.reshape(-1), m.reshape(-1)
-        if policy_forwarded:
-            pass
-        elif self.pol_ab.split:    # one-member group: the stand-alone launch's kernel body, and a launch the tape can pack
-            forward_multi([self.pol_ab.forward_desc(self.x_pol[:, 0:2])])
+    # -- the sets of independent launches an update is made of: ONE rrl_*_multi launch each (grouped), or member by member
+    #    through the stand-alone entry points -- the same kernels on the same inputs, the same bits either way ------------
+    def _forwards(self, members, grouped, riders=()):
+        """Independent stack forwards: members = [(stack, x, options of Stack.forward_desc)]; `riders`: rrl_stack_t of
+        another pass's forwards, in front of them in the same launch (FastActor.ride_*).  Grouped: one launch per four
+        -- a lone member too where it runs the column-split kernels (the stand-alone launch's kernel body, and a launch
+        the tape can pack); otherwise every member through Stack.forward."""
+        if grouped and (len(members) + len(riders) > 1 or members[0][0].split):
+            descs = list(riders) + [st.forward_desc(x, **opt) for st, x, opt in members]
+            for k in range(0, len(descs), 4):
+                forward_multi(descs[k:k + 4])
+            return
+        assert not riders
+        for st, x, opt in members:
+            assert opt.get("in_head") is None, "a policy head rides in the grouped column-split launches only"
+            st.forward(x, params=opt.get("params"), save=opt.get("save", True))
+
+    def _heads(self, heads, consumer, grouped):
+        """Policy heads (rrl_policy_head_t, or None for one that is not needed) whose actions stacks like `consumer` read
+        next.  Grouped on the column-split kernels nothing goes out: the heads are handed back, for the consuming stacks
+        to evaluate them (in_head of _forwards).  Otherwise they are launched here -- together, or one by one -- and None
+        is handed back for each."""
+        if grouped and self.fuse_heads and consumer.split:
+            return heads
+        live = [hd for hd in heads if hd is not None]
+        if grouped:
+            heads_multi(live)
         else:
-            self.pol_ab.forward(self.x_pol[:, 0:2])
-        head2, head = self.pol_next.after_forward(), self.pol_b.after_forward()
-        hd2 = self._gauss_desc(head2, eps_next, self.x2u[:, 2:4], self.logp2)
-        hd1 = self._gauss_desc(head, eps_pi, self.xpu[:, 2:4], self.logp)
-        fuse = self.fuse_heads and self.cri_t.split
-        if not fuse:
-            heads_multi([hd2, hd1])
-            hd2 = hd1 = None
-        # critic_target(s', a'), critic(s, a), critic(s, pi): three independent forwards (sac.py:192-218); a' and pi are
-        # evaluated by the stacks that consume them
-        fwd = [self.cri_t.forward_desc(self.x2u, params=self.critic_target, save=False, in_head=hd2),
-               self.cri_a.forward_desc(self.xu), self.cri_b.forward_desc(self.xpu, in_head=hd1)]
-        if self.dgd or self.update_nu:      # Q_risk(s, pi): pi evaluated by this stack too, written by the critic's only
-            hq = None
-            if hd1 is not None:
-                hq = _lib.rrl_policy_head_t.from_buffer_copy(hd1)
-                hq.action, hq.logp = None, None
-            fwd.append(self.qr_p.forward_desc(self.xpu, save=self.dgd, in_head=hq))
-        if self.rcpo:
-            fwd.append(self.qr_sa.forward_desc(self.xu, save=False))
-        forward_multi(fwd[:4])
-        if len(fwd) > 4:
-            forward_multi(fwd[4:])
-        qt, n_part, ps = self.cri_t.parts
-        q, qp = self.cri_a.parts[0], self.cri_b.parts[0]
-        if self.rcpo:
-            self._penalty(self.qr_sa.parts, mean=self.dual_stats[1:2])
-        if self.update_nu and not self.dgd:
-            self._penalty(self.qr_p.parts, want_penalty=False, mean=self.dual_stats[0:1])
-        # the critic's backward for its own loss (weight gradients) and for the policy loss (input gradient)
-        members = [
-            self.cri_a.backward_descs(self._loss(_lib.LOSS_SAC_CRITIC, q, n_part, ps, out_t=qt, v0=self.logp2, v1=r,
-                                                 v2=m, v3=self.penalty if self.rcpo else None, alpha=self.alpha,
-                                                 f0=ag.gamma, loss=self.losses)),
-            self.cri_b.backward_descs(self._loss(_lib.LOSS_SAC_POLICY, qp, n_part, ps, v0=self.logp, alpha=self.alpha,
-                                                 loss=self.losses[2:]), weight_grads=False, input_grad=True)]
-        if self.dgd:
-            zp, zn, zs = self.qr_p.parts
-            members.append(self.qr_p.backward_descs(self._loss(_lib.LOSS_DGD_QRISK, zp, zn, zs, f0=nu,
-                                                               loss=self.dual_stats[0:1]), weight_grads=False, input_grad=True))
-        backward_multi(members)
-        ht, hn, hs = head
-        da, dh = self.joint_d_action() if self.dgd else (self.cri_b.dx_parts(), None)
-        self.pol_b.backward(self._loss(_lib.LOSS_GAUSS_HEAD, ht, hn, hs, v0=eps_pi, v1=self.scale,
-                                       f0=float(ag.alpha) / B, d_action=da, d_heads=dh))
-        if self.sync_world > 1:
-            self._sync(self.sac_bucket)
-        adam_multi(ag.lr, [(self.critic, self.critic_target, ag.tau, self.cri_a.grad_part),
-                           (self.policy, None, 0.0, self.pol_b.grad_part)], duals=self._duals(nu))
-        return self.losses
+            for hd in live:
+                head_forward(hd)
+        return [None] * len(heads)
+
+    def _backwards(self, members, grouped):
+        """Independent stack backwards with their loss descriptions: members = [(stack, rrl_loss_t, weight_grads,
+        input_grad)].  Grouped: one launch per stage for all of them; a lone member, or member by member: Stack.backward
+        (which is where fuse_loss = False takes the loss gradient from a launch of its own)."""
+        if grouped and len(members) > 1:
+            backward_multi([st.backward_descs(loss, wg, ig) for st, loss, wg, ig in members])
+            return
+        for st, loss, wg, ig in members:
+            st.backward(loss, weight_grads=wg, input_grad=ig, fuse_loss=self.fuse_loss or grouped)
 
     def _nu(self, nu):
         """The multiplier of the Lagrangian term as a host float: the value passed in (the reference's nu_schedule), else
@@ -860,128 +873,59 @@ class FastUpdater:
         nu = self.agent.nu if nu is None else nu
         return float(nu)
 
-    def can_carry_actor(self):
-        """The acting pass's task-policy and Q_risk forwards can ride in this update's forward launches (qrisk_update_grouped):
-        model-free recovery, policy heads evaluated by the consuming stacks, every stack on the column-split kernels."""
-        return bool(self.grouped and self.qr.MF_recovery and self.fuse_heads and self.qr_t.split and self.qr_b.split
-                    and self.pol_a.split and self.rec_a.split and self.sync_world == 1)
-
-    def qrisk_update_grouped(self, batch, eps_next, eps_pi, rider=None):
-        """qrisk_update with 15 launches instead of 19: the task policy on s' and the recovery policy on s in one
-        forward launch (the recovery policy does not depend on the critic step in between), their heads in one, the
-        target and online critics in one.
-        rider = (FastActor, obs) (can_carry_actor()): the acting pass that follows needs the task policy on the N observations
-        -- final since the SAC step -- and Q_risk(obs, a_task) -- final since this update's critic step: the first rides in
-        this update's first forward launch, the second in its forward at the updated critic.  The acting pass is left with
-        the recovery policy's forward (final only after this update's last step): 17 -> 16 launches per iteration, and the
-        two 256-row launches that waited alone on the chip run under the 4096-row ones.  Same kernels, same inputs: same bits."""
-        qr, B = self.qr, self.B
-        s, a, c, s2, m = batch
-        c, m = c.reshape(-1), m.reshape(-1)
-        xu, x2u, xpu = self.rows_q
-        mf = bool(qr.MF_recovery)
-        fwd = [self.pol_a.forward_desc(x2u[:, 0:2], save=False)]          # a' from the TASK policy (qrisk.py:119-120)
-        if mf:
-            fwd.append(self.rec_a.forward_desc(xpu[:, 0:2]))
-        fuse = self.fuse_heads and self.qr_t.split
-        if rider is not None:
-            assert self.can_carry_actor()
-            fwd.insert(0, rider[0].ride_policy(rider[1]))       # the large member first (mlp_fwd_kernels.hip: measured forms)
-        forward_multi(fwd)
-        hd_next = self._gauss_desc(self.pol_a.parts, eps_next, x2u[:, 2:4], self.logp2)
-        hd_rec = self._stoch_desc(self.rec_a.parts, eps_pi, xpu[:, 2:4]) if mf else None
-        if not fuse:
-            heads_multi([hd_next] + ([hd_rec] if mf else []))
-            hd_next = hd_rec = None
-        forward_multi([self.qr_t.forward_desc(x2u, params=self.qrisk_target, save=False, in_head=hd_next),
-                       self.qr_a.forward_desc(xu)])
-        zt, n_part, ps = self.qr_t.parts
-        z = self.qr_a.parts[0]
-        self.qr_a.backward(self._loss(_lib.LOSS_QRISK_CRITIC, z, n_part, ps, out_t=zt, v0=c, v1=m,
-                                      f0=qr.gamma_safe, loss=self.losses[4:]))
-        self._sync(self.qrisk.grad)
-        self.qrisk.adam(qr.lr, target=self.qrisk_target, tau=qr.tau, part=self.qr_a.grad_part)
-        if mf:                                                             # qrisk.py:150-158, at the UPDATED critic
-            raw, rn, rs = self.rec_a.parts
-            ls = self.recpolicy.p["log_std"]
-            if hd_rec is not None:         # the recovery action is evaluated by the critic stack that consumes it
-                forward_multi(([rider[0].ride_qrisk()] if rider else []) + [self.qr_b.forward_desc(xpu, in_head=hd_rec)])
-                zp, n_part, ps = self.qr_b.parts
-            else:
-                zp, n_part, ps = self.qr_b.forward(xpu)
-            self.qr_b.backward(self._loss(_lib.LOSS_QRISK_POLICY, zp, n_part, ps, loss=self.losses[6:]),
-                               weight_grads=False, input_grad=True)
-            self.rec_a.backward(self._loss(_lib.LOSS_STOCH_HEAD, raw, rn, rs, v0=eps_pi, v1=ls, v2=self.rscale,
-                                           f0=qr.policy.min_log_std, d_action=self.qr_b.dx_parts(),
-                                           loss=self.recpolicy.g["log_std"]))
-            self._sync(self.recpolicy.grad)
-            self.recpolicy.adam(qr.lr, part=self.rec_a.grad_part)
-        return self.losses
-
     # -- SAC -------------------------------------------------------------------------------------
-    def sac_update(self, batch, eps_next, eps_pi, rows_loaded=False, nu=None):
-        ag, B, lib, st = self.agent, self.B, self.lib, _lib.current_stream()
+    def sac_update(self, batch, eps_next, eps_pi, rows_loaded=False, nu=None, grouped=False, policy_forwarded=False):
+        """One SAC step (sac.py:170-277): at hidden 256 / batch 256 ten launches member by member, five grouped
+        (update_pair; tests/test_launch_plan_cpu.py).  The comparison algorithms' Q_risk forwards join the critic forwards'
+        set (a second launch when both (s, pi) and (s, a) are needed: four members at most), their backward the critic
+        backwards' set, the duals the optimiser launch; the RCPO penalty is one launch more.
+        `policy_forwarded`: the policy forward on (s', s) ran in the caller's launch."""
+        ag, B = self.agent, self.B
         nu = self._nu(nu)
         s, a, r, s2, m = self._load_batch(batch, rows_loaded)
         # pi(s') and pi(s) share the weights (both gradients are taken before either step): ONE policy forward
-        self.pol_ab.forward(self.x_pol[:, 0:2])
-        # target: a' ~ pi(s'), min Q_target(s', a') - alpha log pi  (sac.py:192-201)
-        head2 = self.pol_next.after_forward()
-        self._gauss_fwd(head2, eps_next, self.x2u[:, 2:4], self.logp2)
-        qt, n_part, ps = self.cri_b.forward(self.x2u, params=self.critic_target, save=False)
-        q, _, _ = self.cri_a.forward(self.xu)
-        pen = None
+        if not policy_forwarded:
+            self._forwards([(self.pol_ab, self.x_pol[:, 0:2], {})], grouped)
+        head2, head = self.pol_next.after_forward(), self.pol_b.after_forward()
+        # a' ~ pi(s') for the target min Q_target(s', a') - alpha log pi (sac.py:192-201) and pi(s) for the policy loss
+        hd2, hd1 = self._heads([self._gauss_desc(head2, eps_next, self.x2u[:, 2:4], self.logp2),
+                                self._gauss_desc(head, eps_pi, self.xpu[:, 2:4], self.logp)], self.cri_t, grouped)
+        # critic_target(s', a'), critic(s, a), critic(s, pi): three independent forwards (sac.py:192-218); the policy loss is
+        # taken at the PRE-update critic (both gradients before either step)
+        fwd = [(self.cri_t, self.x2u, dict(params=self.critic_target, save=False, in_head=hd2)),
+               (self.cri_a, self.xu, {}), (self.cri_b, self.xpu, dict(in_head=hd1))]
+        if self.dgd or self.update_nu:      # Q_risk(s, pi) at its pre-update weights: pi evaluated by this stack too, written
+            hq = None                       # by the critic's only
+            if hd1 is not None:
+                hq = _lib.rrl_policy_head_t.from_buffer_copy(hd1)
+                hq.action, hq.logp = None, None
+            fwd.append((self.qr_p, self.xpu, dict(save=self.dgd, in_head=hq)))
+        if self.rcpo:
+            fwd.append((self.qr_sa, self.xu, dict(save=False)))
+        self._forwards(fwd, grouped)
+        qt, n_part, ps = self.cri_t.parts
+        q, qp = self.cri_a.parts[0], self.cri_b.parts[0]
         if self.rcpo:                                                  # lambda max sigmoid(Q_risk(s, a)) (sac.py:202-205)
-            self._penalty(self.qr_sa.forward(self.xu, save=False), mean=self.dual_stats[1:2])
-            pen = self.penalty
-        if self.fuse_loss:                                             # critic gradients (sac.py:233-235)
-            self.cri_a.backward(self._loss(_lib.LOSS_SAC_CRITIC, q, n_part, ps, out_t=qt, v0=self.logp2, v1=r, v2=m,
-                                           v3=pen, alpha=self.alpha, f0=ag.gamma, loss=self.losses))
-        else:
-            self._check(lib.rrl_sac_critic_grad(B, q.data_ptr(), qt.data_ptr(), n_part, ps, self.logp2.data_ptr(),
-                                                r.data_ptr(), m.data_ptr(), ag.gamma, self.alpha.data_ptr(), _lib.ptr(pen),
-                                                self.dq.data_ptr(), self.losses.data_ptr(), st),
-                        "rrl_sac_critic_grad")
-            self.cri_a.backward(self.dq)
-        # policy loss at the PRE-update critic (both gradients before either step)
-        head = self.pol_b.after_forward()
-        self._gauss_fwd(head, eps_pi, self.xpu[:, 2:4], self.logp)
-        qp, n_part, ps = self.cri_b.forward(self.xpu)
-        zp = None
-        if self.dgd or self.update_nu:                                 # Q_risk(s, pi) at its pre-update weights
-            zp = self.qr_p.forward(self.xpu, save=self.dgd)
-            if not self.dgd:
-                self._penalty(zp, want_penalty=False, mean=self.dual_stats[0:1])
+            self._penalty(self.qr_sa.parts, mean=self.dual_stats[1:2])
+        if self.update_nu and not self.dgd:
+            self._penalty(self.qr_p.parts, want_penalty=False, mean=self.dual_stats[0:1])
+        # the critic's backward for its own loss (weight gradients, sac.py:233-235) and for the policy loss (input gradient)
+        members = [
+            (self.cri_a, self._loss(_lib.LOSS_SAC_CRITIC, q, n_part, ps, out_t=qt, v0=self.logp2, v1=r, v2=m,
+                                    v3=self.penalty if self.rcpo else None, alpha=self.alpha, f0=ag.gamma,
+                                    loss=self.losses), True, False),
+            (self.cri_b, self._loss(_lib.LOSS_SAC_POLICY, qp, n_part, ps, v0=self.logp, alpha=self.alpha,
+                                    loss=self.losses[2:]), False, True)]
+        if self.dgd:
+            members.append((self.qr_p, self._loss(_lib.LOSS_DGD_QRISK, *self.qr_p.parts, f0=nu, loss=self.dual_stats[0:1]),
+                            False, True))
+        self._backwards(members, grouped)
+        # d pi = action columns of dx [2,B,4], summed over the two critic heads inside the policy's head backward
+        # (and over Q_risk's two after them: joint_d_action)
         ht, hn, hs = head
-        if self.fuse_loss:
-            self.cri_b.backward(self._loss(_lib.LOSS_SAC_POLICY, qp, n_part, ps, v0=self.logp, alpha=self.alpha,
-                                           loss=self.losses[2:]), weight_grads=False, input_grad=True)
-            if self.dgd:
-                self.qr_p.backward(self._loss(_lib.LOSS_DGD_QRISK, *zp, f0=nu, loss=self.dual_stats[0:1]),
-                                   weight_grads=False, input_grad=True)
-            # d pi = action columns of dx [2,B,4], summed over the two critic heads inside the policy's head backward
-            # (and over Q_risk's two after them: joint_d_action)
-            da, dh = self.joint_d_action() if self.dgd else (self.cri_b.dx_parts(), None)
-            self.pol_b.backward(self._loss(_lib.LOSS_GAUSS_HEAD, ht, hn, hs, v0=eps_pi, v1=self.scale,
-                                           f0=float(ag.alpha) / B, d_action=da, d_heads=dh))
-        else:
-            assert not self.cri_b.fuse_first, "fuse_loss = False needs set_fuse_first(False)"
-            self._check(lib.rrl_sac_policy_grad(B, qp.data_ptr(), n_part, ps, self.logp.data_ptr(),
-                                                self.alpha.data_ptr(), self.dq.data_ptr(),
-                                                self.losses[2:].data_ptr(), st), "rrl_sac_policy_grad")
-            dx = self.cri_b.backward(self.dq, weight_grads=False, input_grad=True)      # [2,B,4]
-            heads = 2
-            if self.dgd:
-                zt, zn, zs = zp
-                self._check(lib.rrl_dgd_qrisk_grad(B, zt.data_ptr(), zn, zs, nu, self.dq_r.data_ptr(),
-                                                   self.dual_stats.data_ptr(), st), "rrl_dgd_qrisk_grad")
-                self.qr_p.backward(self.dq_r, weight_grads=False, input_grad=True)     # into dx's second half
-                heads = 4
-            self._check(lib.rrl_gauss_head_bwd(B, ht.data_ptr(), hn, hs, eps_pi.data_ptr(), self.scale.data_ptr(),
-                                               dx[0, :, 2:4].data_ptr(), dx.stride(1), heads, dx.stride(0),
-                                               float(ag.alpha) / B, self.dhead.data_ptr(), st),
-                        "rrl_gauss_head_bwd")
-            self.pol_b.backward(self.dhead)
+        da, dh = self.joint_d_action() if self.dgd else (self.cri_b.dx_parts(), None)
+        self._backwards([(self.pol_b, self._loss(_lib.LOSS_GAUSS_HEAD, ht, hn, hs, v0=eps_pi, v1=self.scale,
+                                                 f0=float(ag.alpha) / B, d_action=da, d_heads=dh), True, False)], grouped)
         if self.sync_world > 1:
             self._sync(self.sac_bucket)
         # both optimiser steps + the soft target update (:273-274) in one launch (+ the duals)
@@ -989,47 +933,57 @@ class FastUpdater:
                            (self.policy, None, 0.0, self.pol_b.grad_part)], duals=self._duals(nu))
         return self.losses
 
+    def can_carry_actor(self):
+        """The acting pass's task-policy and Q_risk forwards can ride in the grouped Q_risk update's forward launches
+        (qrisk_update): model-free recovery, policy heads evaluated by the consuming stacks, every stack on the column-split
+        kernels."""
+        return bool(self.grouped and self.qr.MF_recovery and self.fuse_heads and self.qr_t.split and self.qr_b.split
+                    and self.pol_a.split and self.rec_a.split and self.sync_world == 1)
+
     # -- Q_risk ------------------------------------------------------------------------------------
-    def qrisk_update(self, batch, eps_next, eps_pi, rows_loaded=False):
-        qr, B, lib, st = self.qr, self.B, self.lib, _lib.current_stream()
-        s, a, c, s2, m = self._load_batch(batch, rows_loaded)
-        head2 = self.pol_a.forward(s2, save=False)                     # a' from the TASK policy (qrisk.py:119-120)
-        self._gauss_fwd(head2, eps_next, self.x2u[:, 2:4], self.logp2)
-        zt, n_part, ps = self.qr_b.forward(self.x2u, params=self.qrisk_target, save=False)
-        z, _, _ = self.qr_a.forward(self.xu)
-        if self.fuse_loss:
-            self.qr_a.backward(self._loss(_lib.LOSS_QRISK_CRITIC, z, n_part, ps, out_t=zt, v0=c, v1=m,
-                                          f0=qr.gamma_safe, loss=self.losses[4:]))
-        else:
-            self._check(lib.rrl_qrisk_critic_grad(B, z.data_ptr(), zt.data_ptr(), n_part, ps, c.data_ptr(),
-                                                  m.data_ptr(), qr.gamma_safe, self.dq.data_ptr(),
-                                                  self.losses[4:].data_ptr(), st), "rrl_qrisk_critic_grad")
-            self.qr_a.backward(self.dq)
+    def qrisk_update(self, batch, eps_next, eps_pi, rows_loaded=False, rows=None, grouped=False, rider=None):
+        """One Q_risk step and (MF_recovery) one recovery-policy step (qrisk.py:86-163) on the row buffers `rows` (default:
+        the ones the SAC update works on): at hidden 256 / batch 256 twelve launches member by member, eight grouped -- the
+        task policy on s' and the recovery policy on s in one forward launch (the recovery policy does not depend on the
+        critic step in between), the target and online critics in one, the heads inside the stacks that read their actions.
+        rider = (FastActor, obs) (grouped, can_carry_actor()): the acting pass that follows needs the task policy on the N
+        observations -- final since the SAC step -- and Q_risk(obs, a_task) -- final since this update's critic step: the
+        first rides in this update's first forward launch, the second in its forward at the updated critic.  The acting pass
+        is left with the recovery policy's forward (final only after this update's last step): 17 -> 16 launches per
+        iteration, and the two 256-row launches that waited alone on the chip run under the 4096-row ones.  Same kernels,
+        same inputs: same bits."""
+        qr = self.qr
+        xu, x2u, xpu = rows = rows or self.rows
+        s, a, c, s2, m = self._load_batch(batch, rows_loaded, rows)
+        mf = bool(qr.MF_recovery)
+        assert rider is None or self.can_carry_actor()
+        fwd = [(self.pol_a, x2u[:, 0:2], dict(save=False))]                # a' from the TASK policy (qrisk.py:119-120)
+        if mf:
+            fwd.append((self.rec_a, xpu[:, 0:2], {}))
+        # the rider: the large member first (mlp_fwd_kernels.hip: measured forms)
+        self._forwards(fwd, grouped, riders=[rider[0].ride_policy(rider[1])] if rider else ())
+        hd_next, hd_rec = self._heads([self._gauss_desc(self.pol_a.parts, eps_next, x2u[:, 2:4], self.logp2),
+                                       self._stoch_desc(self.rec_a.parts, eps_pi, xpu[:, 2:4]) if mf else None],
+                                      self.qr_t, grouped)
+        self._forwards([(self.qr_t, x2u, dict(params=self.qrisk_target, save=False, in_head=hd_next)),
+                        (self.qr_a, xu, {})], grouped)
+        zt, n_part, ps = self.qr_t.parts
+        z = self.qr_a.parts[0]
+        self._backwards([(self.qr_a, self._loss(_lib.LOSS_QRISK_CRITIC, z, n_part, ps, out_t=zt, v0=c, v1=m,
+                                                f0=qr.gamma_safe, loss=self.losses[4:]), True, False)], grouped)
         self._sync(self.qrisk.grad)
         self.qrisk.adam(qr.lr, target=self.qrisk_target, tau=qr.tau, part=self.qr_a.grad_part)
-        if qr.MF_recovery:                                              # qrisk.py:150-158, at the UPDATED critic
-            raw, rn, rs = self.rec_a.forward(s)
+        if mf:                                                             # qrisk.py:150-158, at the UPDATED critic
+            raw, rn, rs = self.rec_a.parts
             ls = self.recpolicy.p["log_std"]
-            self._check(lib.rrl_stoch_head_fwd(B, raw.data_ptr(), rn, rs, eps_pi.data_ptr(), ls.data_ptr(),
-                                               qr.policy.min_log_std, self.rscale.data_ptr(), self.rbias.data_ptr(),
-                                               self.xpu[:, 2:4].data_ptr(), 4, None, st), "rrl_stoch_head_fwd")
-            zp, n_part, ps = self.qr_b.forward(self.xpu)
-            if self.fuse_loss:
-                self.qr_b.backward(self._loss(_lib.LOSS_QRISK_POLICY, zp, n_part, ps, loss=self.losses[6:]),
-                                   weight_grads=False, input_grad=True)
-                self.rec_a.backward(self._loss(_lib.LOSS_STOCH_HEAD, raw, rn, rs, v0=eps_pi, v1=ls, v2=self.rscale,
-                                               f0=qr.policy.min_log_std, d_action=self.qr_b.dx_parts(),
-                                               loss=self.recpolicy.g["log_std"]))
-            else:
-                self._check(lib.rrl_qrisk_policy_grad(B, zp.data_ptr(), n_part, ps, self.dq.data_ptr(),
-                                                      self.losses[6:].data_ptr(), st), "rrl_qrisk_policy_grad")
-                dx = self.qr_b.backward(self.dq, weight_grads=False, input_grad=True)
-                self._check(lib.rrl_stoch_head_bwd(B, raw.data_ptr(), rn, rs, eps_pi.data_ptr(), ls.data_ptr(),
-                                                   qr.policy.min_log_std, self.rscale.data_ptr(),
-                                                   dx[0, :, 2:4].data_ptr(), dx.stride(1), 2, dx.stride(0),
-                                                   self.draw.data_ptr(), self.recpolicy.g["log_std"].data_ptr(),
-                                                   st), "rrl_stoch_head_bwd")
-                self.rec_a.backward(self.draw)
+            self._forwards([(self.qr_b, xpu, dict(in_head=hd_rec))], grouped,
+                           riders=[rider[0].ride_qrisk()] if rider else ())
+            zp, n_part, ps = self.qr_b.parts
+            self._backwards([(self.qr_b, self._loss(_lib.LOSS_QRISK_POLICY, zp, n_part, ps, loss=self.losses[6:]),
+                              False, True)], grouped)
+            self._backwards([(self.rec_a, self._loss(_lib.LOSS_STOCH_HEAD, raw, rn, rs, v0=eps_pi, v1=ls, v2=self.rscale,
+                                                     f0=qr.policy.min_log_std, d_action=self.qr_b.dx_parts(),
+                                                     loss=self.recpolicy.g["log_std"]), True, False)], grouped)
             self._sync(self.recpolicy.grad)
             self.recpolicy.adam(qr.lr, part=self.rec_a.grad_part)
         return self.losses
@@ -1062,12 +1016,10 @@ class FastActor:
     def ride_qrisk(self):
         """rrl_stack_t of Q_risk(obs, a_task) with the task head evaluated by the stack (it stores the action in xa for the
         step kernel), for a launch the caller issues after the policy rider's launch and the safety critic's step."""
-        f, r = self.f, self._ride
-        task_head = f._gauss_desc(self.pol.parts, r["noise"][0], self.xa[:, 2:4], None, n=self.n, obs_in=r["obs"],
-                                  obs_out=self.xa)
+        r = self._ride
         self.qr.finalize = False
         r["qrisk"] = True
-        return self.qr.forward_desc(self.xa, save=False, in_head=task_head)
+        return self.qr.forward_desc(self.xa, save=False, in_head=self._task_head(r["noise"][0], r["obs"]))
 
     def _finish_ride(self, obs, eps_safe):
         """What is left of act(defer_select=True) after both riders: the recovery policy's forward (its step is the last of
@@ -1080,97 +1032,79 @@ class FastActor:
             f.select_ahead(self.rec.forward_desc(obs, save=False), *sel)
         else:
             forward_multi([self.rec.forward_desc(obs, save=False)])
-        rec_head = f._stoch_desc(self.rec.parts, r["noise"][1], self.rec_action, n=self.n)
-        zq, zn, zs = self.qr.parts
-        self.pending_select = (zq, zn, zs, float(eps_safe), None, rec_head)
+        return self._deferred(eps_safe, rec_head=f._stoch_desc(self.rec.parts, r["noise"][1], self.rec_action, n=self.n))
+
+    def _deferred(self, eps_safe, rec_action=None, rec_head=None):
+        """The gate left to the env-step kernel: its inputs -- Q_risk(s, a_task) as the last forward left it, the recovery
+        action or the head that yields it -- in `pending_select`, the buffers that kernel fills as the result."""
+        self.pending_select = (*self.qr.parts, float(eps_safe), rec_action, rec_head)
         return self.xa[:, 2:4], self.real_action, self.recovery
+
+    def _task_head(self, eps, obs):
+        """The task policy's head on this pass's forward.  It also copies obs into columns 0..1 of xa: [s | a_task] is
+        assembled without a copy launch."""
+        return self.f._gauss_desc(self.pol.parts, eps, self.xa[:, 2:4], None, n=self.n, obs_in=obs, obs_out=self.xa)
+
+    def _gate(self, eps_safe):
+        """Q_risk(s, a_task) on xa, then recovery[i] = max(sigmoid(z1), sigmoid(z2)) > eps_safe and the action select
+        (experiment.py:566-571) -> (task action, executed action, recovery)."""
+        self.qr.finalize = True                  # recovery_select reads a plain [2,n] tensor
+        zq, _, _ = self.qr.forward(self.xa, save=False)
+        _lib.check(self.f.lib.rrl_recovery_select(self.n, zq.data_ptr(), eps_safe, self.xa[:, 2:4].data_ptr(), 4,
+                                                  self.rec_action.data_ptr(), self.real_action.data_ptr(),
+                                                  self.recovery.data_ptr(), self.task_action.data_ptr(),
+                                                  _lib.current_stream()), "rrl_recovery_select")
+        return self.task_action, self.real_action, self.recovery
 
     def act(self, obs, eps_safe, use_recovery, mf_recovery, noise=None, defer_select=False):
         """-> (task action [n,2], executed action [n,2], recovery u8[n] or None); persistent buffers.
         defer_select: the recovery gate is left to the env-step kernel (rrl_*_step_push_select); `pending_select` then
         holds its inputs, the task action is the strided view xa[:, 2:4] and the other two are filled by that kernel."""
-        f, n, lib, st = self.f, self.n, self.f.lib, _lib.current_stream()
+        f, n = self.f, self.n
         self.pending_select = None
         if self._ride is not None:
             assert noise is None and defer_select and use_recovery and mf_recovery
             return self._finish_ride(obs, eps_safe)
         if noise is None:
             noise = f.actor_noise(n)
-        if f.grouped and use_recovery and mf_recovery:
-            # task policy and recovery policy on the same observations: one forward launch, one head launch
-            forward_multi([self.pol.forward_desc(obs, save=False), self.rec.forward_desc(obs, save=False)])
-            task_head = f._gauss_desc(self.pol.parts, noise[0], self.xa[:, 2:4], None, n=n, obs_in=obs, obs_out=self.xa)
-            rec_head = f._stoch_desc(self.rec.parts, noise[1], self.rec_action, n=n)
-            if defer_select and f.fuse_heads and self.qr.split:
-                # no head launch: the task action is evaluated by the Q_risk stack that consumes it (and stored in xa
-                # for the step kernel), the recovery action by the step kernel itself
-                self.qr.finalize = False
-                forward_multi([self.qr.forward_desc(self.xa, save=False, in_head=task_head)])
-                zq, zn, zs = self.qr.parts
-                self.pending_select = (zq, zn, zs, float(eps_safe), None, rec_head)
-                return self.xa[:, 2:4], self.real_action, self.recovery
-            heads_multi([task_head, rec_head])
-            if defer_select:
-                self.qr.finalize = False            # the step kernel adds the partial last-layer sums itself
-                zq, zn, zs = self.qr.forward(self.xa, save=False)
-                self.pending_select = (zq, zn, zs, float(eps_safe), self.rec_action, None)
-                return self.xa[:, 2:4], self.real_action, self.recovery
-            self.qr.finalize = True
-            zq, _, _ = self.qr.forward(self.xa, save=False)
-            _lib.check(lib.rrl_recovery_select(n, zq.data_ptr(), eps_safe, self.xa[:, 2:4].data_ptr(), 4,
-                                               self.rec_action.data_ptr(), self.real_action.data_ptr(),
-                                               self.recovery.data_ptr(), self.task_action.data_ptr(), st),
-                       "rrl_recovery_select")
-            return self.task_action, self.real_action, self.recovery
-        head, hn, hs = self.pol.forward(obs, save=False)
         if not use_recovery:
-            _lib.check(lib.rrl_gauss_head_fwd(n, head.data_ptr(), hn, hs, noise[0].data_ptr(), f.scale.data_ptr(),
-                                              f.bias.data_ptr(), self.task_action.data_ptr(), 2, None, None, None,
-                                              None, st), "rrl_gauss_head_fwd")
+            self.pol.forward(obs, save=False)
+            head_forward(f._gauss_desc(self.pol.parts, noise[0], self.task_action, None, n=n))
             return self.task_action, self.task_action, None
-        # the head kernel also copies obs into columns 0..1 of xa: [s | a_task] is assembled without a copy launch
-        _lib.check(lib.rrl_gauss_head_fwd(n, head.data_ptr(), hn, hs, noise[0].data_ptr(), f.scale.data_ptr(),
-                                          f.bias.data_ptr(), self.xa[:, 2:4].data_ptr(), 4, None, None,
-                                          obs.data_ptr(), self.xa.data_ptr(), st), "rrl_gauss_head_fwd")
-        self.qr.finalize = True                  # recovery_select reads a plain [2,n] tensor
-        zq, _, _ = self.qr.forward(self.xa, save=False)
         assert mf_recovery, "FastActor covers the model-free recovery policy"
-        raw, rn, rs = self.rec.forward(obs, save=False)
-        _lib.check(lib.rrl_stoch_head_fwd(n, raw.data_ptr(), rn, rs, noise[1].data_ptr(),
-                                          f.recpolicy.p["log_std"].data_ptr(), f.qr.policy.min_log_std,
-                                          f.rscale.data_ptr(), f.rbias.data_ptr(), self.rec_action.data_ptr(), 2,
-                                          None, st), "rrl_stoch_head_fwd")
-        _lib.check(lib.rrl_recovery_select(n, zq.data_ptr(), eps_safe, self.xa[:, 2:4].data_ptr(), 4,
-                                           self.rec_action.data_ptr(), self.real_action.data_ptr(),
-                                           self.recovery.data_ptr(), self.task_action.data_ptr(), st),
-                   "rrl_recovery_select")
-        return self.task_action, self.real_action, self.recovery
+        grouped = f.grouped
+        # task policy and recovery policy on the same observations: one forward launch, one head launch (grouped)
+        f._forwards([(self.pol, obs, dict(save=False)), (self.rec, obs, dict(save=False))], grouped)
+        task_head = self._task_head(noise[0], obs)
+        rec_head = f._stoch_desc(self.rec.parts, noise[1], self.rec_action, n=n)
+        defer_select = defer_select and grouped
+        if defer_select and f.fuse_heads and self.qr.split:
+            # no head launch: the task action is evaluated by the Q_risk stack that consumes it (and stored in xa
+            # for the step kernel), the recovery action by the step kernel itself
+            self.qr.finalize = False
+            forward_multi([self.qr.forward_desc(self.xa, save=False, in_head=task_head)])
+            return self._deferred(eps_safe, rec_head=rec_head)
+        if grouped:
+            heads_multi([task_head, rec_head])
+        else:
+            head_forward(task_head), head_forward(rec_head)
+        if defer_select:
+            self.qr.finalize = False            # the step kernel adds the partial last-layer sums itself
+            self.qr.forward(self.xa, save=False)
+            return self._deferred(eps_safe, rec_action=self.rec_action)
+        return self._gate(eps_safe)
 
-
-    def _act_gate(self, obs, eps_safe, noise=None):
+    def act_gate(self, obs, eps_safe, noise=None):
         """Task action + recovery gate for a controller that acts elsewhere (model-based recovery: MPC.act on the gated rows):
         -> (task action [n,2], recovery u8[n]); persistent buffers."""
-        f, n, lib, st = self.f, self.n, self.f.lib, _lib.current_stream()
         if noise is None:
-            noise = f.actor_noise(n)
+            noise = self.f.actor_noise(self.n)
         self.pending_select = None
-        head, hn, hs = self.pol.forward(obs, save=False)
-        # the head kernel also copies obs into columns 0..1 of xa: [s | a_task] is assembled without a copy launch
-        _lib.check(lib.rrl_gauss_head_fwd(n, head.data_ptr(), hn, hs, noise[0].data_ptr(), f.scale.data_ptr(),
-                                          f.bias.data_ptr(), self.xa[:, 2:4].data_ptr(), 4, None, None,
-                                          obs.data_ptr(), self.xa.data_ptr(), st), "rrl_gauss_head_fwd")
-        self.qr.finalize = True                  # recovery_select reads a plain [2,n] tensor
-        zq, _, _ = self.qr.forward(self.xa, save=False)
-        # recovery[i] = max(sigmoid(z1), sigmoid(z2)) > eps_safe (experiment.py:566-571); the kernel's action selection runs
-        # on a dummy recovery action: the planner's action is merged in by the caller
-        _lib.check(lib.rrl_recovery_select(n, zq.data_ptr(), eps_safe, self.xa[:, 2:4].data_ptr(), 4,
-                                           self.rec_action.data_ptr(), self.real_action.data_ptr(),
-                                           self.recovery.data_ptr(), self.task_action.data_ptr(), st),
-                   "rrl_recovery_select")
-        return self.task_action, self.recovery
-
-
-FastActor.act_gate = FastActor._act_gate
+        self.pol.forward(obs, save=False)
+        head_forward(self._task_head(noise[0], obs))
+        # the kernel's action selection runs on a dummy recovery action: the planner's action is merged in by the caller
+        task, _, recovery = self._gate(eps_safe)
+        return task, recovery
 
 
 def dual_state(opt, param):

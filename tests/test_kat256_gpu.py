@@ -25,7 +25,7 @@ def test_fused_updates_match_the_reference_at_hidden_256_batch_256(path):
     s, a, r, s2, m = batch
     if path == "grouped":
         fast._load_batch(batch)                       # the rows the replay draw writes (rrl_sample_multi)
-        losses = fast.sac_update_grouped(batch, e1, e2).clone()
+        losses = fast.sac_update(batch, e1, e2, rows_loaded=True, grouped=True).clone()
     else:
         res = agent.update_parameters(None, KAT.K.B, 0, safety_critic=qr, batch=batch, eps_next=e1, eps_pi=e2, as_floats=True)
         assert np.allclose(res, G["sac.returns"], rtol=KAT.REL, atol=2e-6), (res, G["sac.returns"])
@@ -42,7 +42,7 @@ def test_fused_updates_match_the_reference_at_hidden_256_batch_256(path):
     if path == "grouped":
         xu, x2u, xpu = fast.rows_q
         xu[:, 0:2], xu[:, 2:4], x2u[:, 0:2], xpu[:, 0:2] = s, a, s2, s
-        fast.qrisk_update_grouped(q_batch, e1, e2)
+        fast.qrisk_update(q_batch, e1, e2, rows_loaded=True, rows=fast.rows_q, grouped=True)
     else:
         qr.update_parameters(policy=agent.policy, batch=q_batch, eps_next=e1, eps_pi=e2)
     fast.gather_first_grads()
