@@ -222,7 +222,7 @@ int rrl_replay_sample_gather_split(const rrl_replay_t* rb, int32_t n_demo, int32
                                    void* stream);
 
 /* Description of one policy-head evaluation (used by rrl_policy_heads_fwd_multi, by the input head of rrl_stack_t and
- * by the recovery action of rrl_*_step_push_select). */
+ * by the recovery action of the fused env step, rrl_step_push_t.sel_rec_head). */
 /* rrl_gauss_head_fwd / rrl_stoch_head_fwd calls that do not depend on each other in ONE launch (n <= 4): a' = pi(s')
  * and pi(s) of one SAC step (sac.py:192-218), the task action and the recovery action of the acting pass
  * (experiment.py:546-577).  kind RRL_HEAD_GAUSS: fields of rrl_gauss_head_fwd (mean_out = mean_action);
@@ -280,98 +280,56 @@ typedef struct {
 } rrl_draw_ahead_t;
 int rrl_draw_select(const rrl_draw_ahead_t* sel, void* stream);
 
-/* Fused lock-step iteration tail: env step + reward penalty + bootstrap mask + memory.push +
- * recovery_memory.push + episode counters in ONE launch (the body of recovery_rl/experiment.py:420-461
- * for n navigation envs).  `obs` holds the current observation on entry (it is the stored `state`) and
- * the next observation on return.  Rows stored: memory <- (obs, task_action or real_action if
- * push_real_action, reward - penalty*constraint, next_obs, 1-done); recovery_memory (nullable) <- (obs,
- * real_action, constraint, next_obs, 1-done).  stats = uint64[8] {env_steps, episodes, num_viols,
- * viol_and_recovery, viol_and_no_recovery, num_successes, recovery_steps, constraint_steps};
- * reward_sums = double[2] {sum of rewards, sum of finished-episode returns}; ep_reward = float[n].
- * next_obs, reward, done, constraint, success, ep_done are per-env outputs of the step for callers that read them
- * (episode log, online model re-fit): each may be NULL (17 of the 171 B the kernel moves per env-step are theirs). */
-int rrl_nav_step_push(int env_kind, int64_t n, double* pos, int32_t* t, float* obs,
-                      const float* task_action, const float* real_action, const uint8_t* recovery,
-                      uint64_t seed, uint64_t counter, uint64_t* counter_dev, uint64_t counter_inc,
-                      int32_t horizon, int auto_reset, float reward_penalty, int push_real_action,
-                      const rrl_replay_t* memory, const rrl_replay_t* recovery_memory, float* next_obs,
-                      float* reward, uint8_t* done, uint8_t* constraint, uint8_t* success, uint8_t* ep_done,
-                      uint64_t* stats, double* reward_sums, float* ep_reward, void* stream);
-/* the same fused tail for the Maze env (env/maze.py:139-213 + experiment.py:420-461) */
-int rrl_maze_step_push(int64_t n, double* pos, int32_t* t, float* obs,
-                      const float* task_action, const float* real_action, const uint8_t* recovery,
-                      uint64_t seed, uint64_t counter, uint64_t* counter_dev, uint64_t counter_inc,
-                      int32_t horizon, int auto_reset, float reward_penalty, int push_real_action,
-                      const rrl_replay_t* memory, const rrl_replay_t* recovery_memory, float* next_obs,
-                      float* reward, uint8_t* done, uint8_t* constraint, uint8_t* success, uint8_t* ep_done,
-                      uint64_t* stats, double* reward_sums, float* ep_reward, void* stream);
-
-/* The same fused tails with the recovery gate of Experiment.get_action (experiment.py:546-577) evaluated inside:
- * recovery[i] = max(sigmoid(z[i]), sigmoid(z[n + i])) > eps_safe (z = pre-sigmoid twin Q_risk(s, a_task), [2,n], given
- * as z_n_part partial sums z_part_stride floats apart like every stack output: rrl_mlp3_forward with scratch);
- * executed action = recovery ? rec_action[i] : task_action[i]; with rec_action = NULL the recovery action is evaluated in
- * the kernel from rec_head (an RRL_HEAD_STOCH description, rrl_stoch_head_fwd's formula on the recovery policy's stack
- * output).  real_action [n,2] and recovery [n] are OUTPUTS here
- * (what rrl_recovery_select would have written); task_action rows are ld_task floats apart (the [s | a] input
- * of the safety critic, ld_task = 4, can be passed as it is).  One launch less per lock-step iteration. */
-int rrl_nav_step_push_select(int env_kind, int64_t n, double* pos, int32_t* t, float* obs, const float* task_action,
-                             int ld_task, const float* z, int z_n_part, long long z_part_stride,
-                             float eps_safe, const float* rec_action, const rrl_policy_head_t* rec_head,
-                             float* real_action,
-                             uint8_t* recovery, uint64_t seed, uint64_t counter, uint64_t* counter_dev,
-                             uint64_t counter_inc, int32_t horizon, int auto_reset, float reward_penalty,
-                             int push_real_action, const rrl_replay_t* memory, const rrl_replay_t* recovery_memory,
-                             float* next_obs, float* reward, uint8_t* done, uint8_t* constraint, uint8_t* success,
-                             uint8_t* ep_done, uint64_t* stats, double* reward_sums, float* ep_reward, void* stream);
-int rrl_maze_step_push_select(int64_t n, double* pos, int32_t* t, float* obs, const float* task_action, int ld_task,
-                              const float* z, int z_n_part, long long z_part_stride, float eps_safe, const float* rec_action, const rrl_policy_head_t* rec_head,
-                             float* real_action,
-                              uint8_t* recovery, uint64_t seed, uint64_t counter, uint64_t* counter_dev,
-                              uint64_t counter_inc, int32_t horizon, int auto_reset, float reward_penalty,
-                              int push_real_action, const rrl_replay_t* memory, const rrl_replay_t* recovery_memory,
-                              float* next_obs, float* reward, uint8_t* done, uint8_t* constraint, uint8_t* success,
-                              uint8_t* ep_done, uint64_t* stats, double* reward_sums, float* ep_reward, void* stream);
-
-/* The same kernel through ONE argument struct, which also carries the COMPACT per-env state: `status` (nullable) is
- * one u16 word per env -- step count in bits 0-11 (horizon <= 4095), done / constraint / success / ep_done of the last
- * step in bits 12-15 -- and replaces `t` (then nullable) and the four u8 flag arrays; with it the stored `state` of the
- * replay rows is float(pos), so `obs` is written only (8 B less read, 8 + 4 B less written per env-step than t + flags).
- * next_obs / reward / done / constraint / success / ep_done stay optional outputs (NULL: not written).  The recovery gate
- * (rrl_*_step_push_select) is selected by sel_z != NULL; otherwise real_action (+ recovery, nullable) are read.
- * Replay rows, counters and env state equal the entries above bit for bit.
- * log_state != NULL: the per-episode log (rrl_episode_log_append, the fields of rrl_episode_log_t + its four per-env
- * accumulators) is advanced by this launch as well, from the values the step holds in registers -- the same records, the
- * same accumulator values as the stand-alone launch fed with this step's per-env outputs, without writing those outputs. */
+/* Fused lock-step iteration tail: env step + reward penalty + bootstrap mask + memory.push + recovery_memory.push +
+ * episode counters in ONE launch (the body of recovery_rl/experiment.py:420-461 for n envs in lock-step; Maze:
+ * env/maze.py:139-213), optionally with the recovery gate of Experiment.get_action (experiment.py:546-577) in front and
+ * the per-episode log behind.  Rows stored: memory <- (state, task_action or the executed action if push_real_action,
+ * reward - reward_penalty * constraint, next_obs, 1 - done); recovery_memory (nullable) <- (state, executed action,
+ * constraint, next_obs, 1 - done).  Every field is described here once; a zero-initialised struct has every option off. */
 typedef struct {
     int64_t n;
-    double* pos;
-    int32_t* t;
-    uint16_t* status;
-    float* obs;
-    const float* task_action;
+    double* pos;             /* [n,2] in/out  env state (as rrl_nav_step / rrl_maze_step) */
+    int32_t* t;              /* [n]   in/out  per-env step count; may be NULL when `status` is given */
+    uint16_t* status;        /* [n]   in/out  nullable: the COMPACT per-env state, one u16 word per env (RRL_STATUS_*: step
+                              * count in bits 0-11, so 1 <= horizon <= 4095, done / constraint / success / ep_done of the last
+                              * step in bits 12-15).  It replaces `t` and the four u8 flag arrays, and with it the stored
+                              * `state` of the replay rows is float(pos), so `obs` is written only (8 B less read, 8 + 4 B
+                              * less written per env-step than t + flags).  Rows, counters and env state are the same bits. */
+    float* obs;              /* [n,2] in/out  the current observation on entry (the stored `state`), the next one on return */
+    const float* task_action;/* [n,2] in      the task policy's action; rows are ld_task floats apart (even, >= 2: the
+                              * [s | a] input of the safety critic, ld_task = 4, can be passed as it is) */
     int32_t ld_task;
-    const float* real_action;
-    const uint8_t* recovery;
-    const float* sel_z;
-    int32_t sel_n_part;
+    const float* real_action;/* [n,2] in      the executed action, and (nullable) whether it is a recovery action: */
+    const uint8_t* recovery; /* [n]   in      both read when sel_z == NULL, ignored otherwise */
+    /* sel_z != NULL: the recovery gate is evaluated in the kernel, one launch less per lock-step iteration.
+     * recovery[i] = max(sigmoid(z[i]), sigmoid(z[n + i])) > sel_eps_safe; executed action = recovery ? rec : task. */
+    const float* sel_z;      /* [2,n] pre-sigmoid twin Q_risk(s, a_task), given as sel_n_part (1..4) partial sums */
+    int32_t sel_n_part;      /* sel_part_stride floats apart, like every stack output (rrl_mlp3_forward with scratch) */
     long long sel_part_stride;
     float sel_eps_safe;
-    const float* sel_rec_action;
-    const rrl_policy_head_t* sel_rec_head;
-    float* real_action_out;
-    uint8_t* recovery_out;
-    uint64_t seed, counter;
+    const float* sel_rec_action;            /* [n,2] the recovery action, or NULL: it is evaluated in the kernel from */
+    const rrl_policy_head_t* sel_rec_head;  /* this RRL_HEAD_STOCH description (rrl_stoch_head_fwd's formula on the
+                                             * recovery policy's stack output) */
+    float* real_action_out;  /* [n,2] out     with the gate: the executed action and the flag, */
+    uint8_t* recovery_out;   /* [n]   out     what rrl_recovery_select would have written */
+    uint64_t seed, counter;  /* Philox stream position, as rrl_nav_step */
     uint64_t* counter_dev;
     uint64_t counter_inc;
     int32_t horizon, auto_reset;
     float reward_penalty;
-    int32_t push_real_action;
-    const rrl_replay_t *memory, *recovery_memory;
+    int32_t push_real_action;                       /* disable_action_relabeling (experiment.py:437-441) */
+    const rrl_replay_t *memory, *recovery_memory;   /* n <= cap - pinned of each; recovery_memory nullable */
+    /* per-env outputs of the step for callers that read them (the `info` fields of env.step: episode log, online model
+     * re-fit): each may be NULL = not written (17 of the 171 B the kernel moves per env-step are theirs) */
     float *next_obs, *reward;
     uint8_t *done, *constraint, *success, *ep_done;
-    uint64_t* stats;
-    double* reward_sums;
-    float* ep_reward;
+    uint64_t* stats;         /* uint64[8] += {env_steps, episodes, num_viols, viol_and_recovery, viol_and_no_recovery,
+                              * num_successes, recovery_steps, constraint_steps} */
+    double* reward_sums;     /* double[2] += {sum of rewards, sum of finished-episode returns} */
+    float* ep_reward;        /* [n]   in/out  running episode return */
+    /* log_state != NULL: the per-episode log (rrl_episode_log_append) is advanced by this launch as well, from the values
+     * the step holds in registers -- the same records and accumulator values as the stand-alone launch fed with this
+     * step's per-env outputs, without writing those outputs.  The other log_* fields are then required. */
     int32_t* log_rec_i32;    /* rrl_episode_log_t.rec_i32 / rec_f64 / cap / state */
     double* log_rec_f64;
     int64_t log_cap;
@@ -380,6 +338,7 @@ typedef struct {
     double* log_ret;
     int32_t *log_viol, *log_rec;
 } rrl_step_push_t;
+/* RRL_EINVAL / RRL_ERANGE before any launch when a required field is missing or a size is out of range; n == 0: RRL_OK. */
 int rrl_nav_step_push_x(int env_kind, const rrl_step_push_t* a, void* stream);
 int rrl_maze_step_push_x(const rrl_step_push_t* a, void* stream);
 

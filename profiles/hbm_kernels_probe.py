@@ -78,13 +78,20 @@ for nenv in (4096, 1 << 20):
     rec = torch.zeros(nenv, dtype=torch.uint8, device=dev)
     lib = _lib.load()
 
-    def fused():
-        return lib.rrl_nav_step_push(0, nenv, _lib.ptr(env.pos), _lib.ptr(env.t), _lib.ptr(env.obs), _lib.ptr(a), _lib.ptr(a),
-                                     _lib.ptr(rec), 1, 0, _lib.ptr(env.tick), 1, 100, 1, 0.0, 0, C.byref(m1._desc),
-                                     C.byref(m2._desc), _lib.ptr(env.next_obs), _lib.ptr(env.reward), _lib.ptr(env.done),
-                                     _lib.ptr(env.constraint), _lib.ptr(env.success), _lib.ptr(env.ep_done),
-                                     _lib.ptr(stats), _lib.ptr(sums), _lib.ptr(epr), _lib.current_stream())
-    out.append(entry("step_push_kernel<Nav1> (rrl_nav_step_push), %d envs" % nenv, timed(fused), nenv, 39 + 64, "env-step"))
+    p = _lib.ptr
+    sp = _lib.rrl_step_push_t()
+    sp.n, sp.pos, sp.t, sp.obs = nenv, p(env.pos), p(env.t), p(env.obs)
+    sp.task_action, sp.ld_task, sp.real_action, sp.recovery = p(a), 2, p(a), p(rec)
+    sp.seed, sp.counter, sp.counter_dev, sp.counter_inc = 1, 0, p(env.tick), 1
+    sp.horizon, sp.auto_reset, sp.reward_penalty, sp.push_real_action = 100, 1, 0.0, 0
+    sp.memory, sp.recovery_memory = C.pointer(m1._desc), C.pointer(m2._desc)
+    sp.next_obs, sp.reward = p(env.next_obs), p(env.reward)
+    sp.done, sp.constraint, sp.success, sp.ep_done = p(env.done), p(env.constraint), p(env.success), p(env.ep_done)
+    sp.stats, sp.reward_sums, sp.ep_reward = p(stats), p(sums), p(epr)
+
+    def fused(sp=sp):
+        return lib.rrl_nav_step_push_x(0, C.byref(sp), _lib.current_stream())
+    out.append(entry("step_push_kernel<Nav1> (rrl_nav_step_push_x), %d envs" % nenv, timed(fused), nenv, 39 + 64, "env-step"))
 # CEM bookkeeping: M problems x 400 candidates x 10 dims
 M = 4096
 opt = CEMOptimizer(10, 1, 400, 40, lambda s: (s ** 2).sum(-1), np.ones(10), -np.ones(10), alpha=0.1, device=dev, seed=1)

@@ -30,17 +30,21 @@ def time_case(env_name, auto_reset, zero_action, with_rmem=True):
     stats = torch.zeros(10, dtype=torch.int64, device=dev)
     sums = torch.zeros(2, dtype=torch.float64, device=dev)
     ep_reward = torch.zeros(n, device=dev)
-    if env_name == "maze":
-        entry, head = lib.rrl_maze_step_push, ()
-    else:
-        entry, head = lib.rrl_nav_step_push, (env.kind,)
+    p = _lib.ptr
+    a = _lib.rrl_step_push_t()
+    a.n, a.pos, a.t, a.obs = n, p(env.pos), p(env.t), p(env.obs)
+    a.task_action, a.ld_task, a.real_action, a.recovery = p(act), 2, p(real), p(rec)
+    a.seed, a.counter, a.counter_dev, a.counter_inc = env.seed_value, 0, p(env.tick), 1
+    a.horizon, a.auto_reset, a.reward_penalty, a.push_real_action = env.horizon, int(auto_reset), 0.0, 0
+    a.memory, a.recovery_memory = C.pointer(mem._desc), C.pointer(rmem._desc) if with_rmem else None
+    a.next_obs, a.reward = p(env.next_obs), p(env.reward)
+    a.done, a.constraint, a.success, a.ep_done = p(env.done), p(env.constraint), p(env.success), p(env.ep_done)
+    a.stats, a.reward_sums, a.ep_reward = p(stats), p(sums), p(ep_reward)
 
     def launch():
-        return entry(*head, n, _lib.ptr(env.pos), _lib.ptr(env.t), _lib.ptr(env.obs), _lib.ptr(act), _lib.ptr(real),
-                     _lib.ptr(rec), env.seed_value, 0, _lib.ptr(env.tick), 1, env.horizon, int(auto_reset), 0.0, 0,
-                     C.byref(mem._desc), C.byref(rmem._desc) if with_rmem else None, _lib.ptr(env.next_obs),
-                     _lib.ptr(env.reward), _lib.ptr(env.done), _lib.ptr(env.constraint), _lib.ptr(env.success),
-                     _lib.ptr(env.ep_done), _lib.ptr(stats), _lib.ptr(sums), _lib.ptr(ep_reward), _lib.current_stream())
+        if env_name == "maze":
+            return lib.rrl_maze_step_push_x(C.byref(a), _lib.current_stream())
+        return lib.rrl_nav_step_push_x(env.kind, C.byref(a), _lib.current_stream())
     for _ in range(10):
         assert launch() == 0
     torch.cuda.synchronize()

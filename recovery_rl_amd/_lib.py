@@ -38,7 +38,6 @@ EXPORTS = [
     "rrl_maze_step", "rrl_maze_reset", "rrl_maze_offline",
     "rrl_replay_push", "rrl_replay_sample_gather", "rrl_creplay_sample_gather", "rrl_replay_sample_gather_split",
     "rrl_sample_multi", "rrl_draw_select", "rrl_mlp3_forward_riders",
-    "rrl_nav_step_push", "rrl_maze_step_push", "rrl_nav_step_push_select", "rrl_maze_step_push_select",
     "rrl_nav_step_push_x", "rrl_maze_step_push_x",
     "rrl_sample_multi_packed", "rrl_pack_clear", "rrl_mlp3_forward_multi_packed", "rrl_mlp_head_backward_multi_packed",
     "rrl_mlp_hidden_backward_multi_packed", "rrl_mlp_backward_pair_multi_packed", "rrl_adam_step_multi_packed", "rrl_nav_step_push_packed",
@@ -289,16 +288,6 @@ def _declare(lib):
                                            vp, vp, vp, vp, vp]),
         "rrl_replay_sample_gather_split": (ci, [rp, i32, i32, u64, u64, vp, u64, vp, vp, vp, vp, vp,
                                                 vp, vp, vp, vp, vp]),
-        "rrl_nav_step_push": (ci, [ci, i64, vp, vp, vp, vp, vp, vp, u64, u64, vp, u64, i32, ci, f32, ci, rp, rp,
-                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "rrl_maze_step_push": (ci, [i64, vp, vp, vp, vp, vp, vp, u64, u64, vp, u64, i32, ci, f32, ci, rp, rp,
-                                    vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "rrl_nav_step_push_select": (ci, [ci, i64, vp, vp, vp, vp, ci, vp, ci, ll, f32, vp, C.POINTER(rrl_policy_head_t), vp, vp,
-                                          u64, u64, vp, u64, i32, ci,
-                                          f32, ci, rp, rp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "rrl_maze_step_push_select": (ci, [i64, vp, vp, vp, vp, ci, vp, ci, ll, f32, vp, C.POINTER(rrl_policy_head_t), vp, vp,
-                                           u64, u64, vp, u64, i32, ci,
-                                           f32, ci, rp, rp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "rrl_sample_multi": (ci, [C.POINTER(rrl_draw_t), C.POINTER(rrl_draw_t), ll, u64, u64, vp, u64, vp, vp]),
         "rrl_mlp3_forward_multi": (ci, [ci, C.POINTER(rrl_stack_t), vp]),
         "rrl_draw_select": (ci, [C.POINTER(rrl_draw_ahead_t), vp]),

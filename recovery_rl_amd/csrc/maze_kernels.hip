@@ -196,43 +196,15 @@ int rrl_maze_offline(int64_t num_transitions, uint64_t seed, float* s, float* a,
     return check_launch();
 }
 
-int rrl_maze_step_push(int64_t n, double* pos, int32_t* t, float* obs, const float* task_action,
-                       const float* real_action, const uint8_t* recovery, uint64_t seed, uint64_t counter,
-                       uint64_t* counter_dev, uint64_t counter_inc, int32_t horizon, int auto_reset,
-                       float reward_penalty, int push_real_action, const rrl_replay_t* memory,
-                       const rrl_replay_t* recovery_memory, float* next_obs, float* reward, uint8_t* done,
-                       uint8_t* constraint, uint8_t* success, uint8_t* ep_done, uint64_t* stats, double* reward_sums,
-                       float* ep_reward, void* stream) {
+// (the solo entry stays in front of the packed one: the compiler emits the kernels in the order their launches are
+// instantiated, and advance_cursors_kernel comes out an instruction longer in the other order)
+int rrl_maze_step_push_x(const rrl_step_push_t* a, void* stream) {
     rrl_step::StepPushArgs p;
-    const int rc = rrl_step::fill_args(p, n, pos, t, obs, task_action, 2, real_action, recovery, nullptr, seed, counter,
-                                       counter_dev, counter_inc, horizon, auto_reset, reward_penalty, push_real_action,
-                                       memory, recovery_memory, next_obs, reward, done, constraint, success, ep_done,
-                                       stats, reward_sums, ep_reward);
-    if (rc != RRL_OK || n == 0) return rc;
+    const int rc = rrl_step::fill_args(p, a);
+    if (rc != RRL_OK || a->n == 0) return rc;
     // latency regime: the reset draw (one Philox call + the contact test of the candidate; the start region is clear of
     // the walls, so the rejection loop runs once) beside the move instead of after it, and the early cursor ticket
-    rrl_step::launch<MazeEnv>(p, n, (hipStream_t)stream);
-    return check_launch();
-}
-
-int rrl_maze_step_push_select(int64_t n, double* pos, int32_t* t, float* obs, const float* task_action, int ld_task,
-                              const float* z, int z_n_part, long long z_part_stride, float eps_safe, const float* rec_action, const rrl_policy_head_t* rec_head,
-                             float* real_action,
-                              uint8_t* recovery, uint64_t seed, uint64_t counter, uint64_t* counter_dev,
-                              uint64_t counter_inc, int32_t horizon, int auto_reset, float reward_penalty,
-                              int push_real_action, const rrl_replay_t* memory, const rrl_replay_t* recovery_memory,
-                              float* next_obs, float* reward, uint8_t* done, uint8_t* constraint, uint8_t* success,
-                              uint8_t* ep_done, uint64_t* stats, double* reward_sums, float* ep_reward, void* stream) {
-    rrl_step::StepPushArgs p;
-    const rrl_step::SelectIn sel{z, z_n_part, z_part_stride, eps_safe, rec_action, rec_head, real_action, recovery};
-    const int rc = rrl_step::fill_args(p, n, pos, t, obs, task_action, ld_task, nullptr, nullptr, &sel, seed, counter,
-                                       counter_dev, counter_inc, horizon, auto_reset, reward_penalty, push_real_action,
-                                       memory, recovery_memory, next_obs, reward, done, constraint, success, ep_done,
-                                       stats, reward_sums, ep_reward);
-    if (rc != RRL_OK || n == 0) return rc;
-    // latency regime: the reset draw (one Philox call + the contact test of the candidate; the start region is clear of
-    // the walls, so the rejection loop runs once) beside the move instead of after it, and the early cursor ticket
-    rrl_step::launch<MazeEnv>(p, n, (hipStream_t)stream);
+    rrl_step::launch<MazeEnv>(p, a->n, (hipStream_t)stream);
     return check_launch();
 }
 
@@ -243,44 +215,7 @@ int rrl_maze_step_push_packed(int S, const rrl_step_push_t* a, void* stream) {
     rrl_pack::Key key;
     key.pod(7);
     key.pod(S);
-    for (int s = 0; s < S; ++s) {
-        key.pod(a[s]);
-        if (a[s].memory) key.pod(*a[s].memory);
-        if (a[s].recovery_memory) key.pod(*a[s].recovery_memory);
-        if (a[s].sel_rec_head) key.pod(*a[s].sel_rec_head);
-    }
-    hipStream_t st = (hipStream_t)stream;
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
-    if (!plan) {
-        std::vector<rrl_step::StepPushArgs> ps(S);
-        rrl_pack::Idx ix;
-        ix.S = S;
-        ix.first[0] = 0;
-        const int regime = rrl_step::regime_of(a[0].n);
-        for (int s = 0; s < S; ++s) {
-            const int rc = rrl_step::fill_args(ps[s], &a[s]);
-            if (rc != RRL_OK) return rc;
-            if (a[s].n <= 0 || rrl_step::regime_of(a[s].n) != regime) return RRL_EINVAL;
-            ix.first[s + 1] = ix.first[s] + rrl_step::grid_cover(a[s].n);
-        }
-        for (int s = S; s < rrl_pack::kMaxSeeds; ++s) ix.first[s + 1] = ix.first[S];
-        plan = rrl_pack::store(key, ps.data(), sizeof(rrl_step::StepPushArgs) * S, st);
-        if (!plan) return rrl_pack::store_error();
-        plan->grid = rrl_pack::finish(ix);
-        plan->ix = ix;
-        plan->i0 = regime;
-    }
-    const auto* dev = (const rrl_step::StepPushArgs*)plan->dev;
-    rrl_step::launch_pack<MazeEnv>(dev, plan->ix, plan->grid, plan->i0, st);
-    return check_launch();
-}
-
-int rrl_maze_step_push_x(const rrl_step_push_t* a, void* stream) {
-    rrl_step::StepPushArgs p;
-    const int rc = rrl_step::fill_args(p, a);
-    if (rc != RRL_OK || a->n == 0) return rc;
-    rrl_step::launch<MazeEnv>(p, a->n, (hipStream_t)stream);
-    return check_launch();
+    return rrl_step::launch_packed<MazeEnv>(key, S, a, (hipStream_t)stream);
 }
 
 }  // extern "C"

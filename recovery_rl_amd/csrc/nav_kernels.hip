@@ -870,7 +870,9 @@ extern "C" {
 
 int rrl_pack_clear(void) { return rrl_pack::clear(); }
 
-int rrl_abi_version(void) { return 4; }   // 2: pos_cnt carries a second count level (RRL_POS_CNT_LEN); 3: rrl_replay_t.pinned; 4: RRL_DRAW_DEMO_SHARE
+// 2: pos_cnt carries a second count level (RRL_POS_CNT_LEN); 3: rrl_replay_t.pinned; 4: RRL_DRAW_DEMO_SHARE;
+// 5: the positional forms of the fused env step (plain and with the recovery gate) are gone: rrl_step_push_t is its one form
+int rrl_abi_version(void) { return 5; }
 
 int rrl_last_hip_error(void) { return rrl_host::last_hip_error; }
 
@@ -1053,41 +1055,12 @@ static int nav_step_push_launch(int env_kind, const rrl_step::StepPushArgs& p, i
     return check_launch();
 }
 
-int rrl_nav_step_push(int env_kind, int64_t n, double* pos, int32_t* t, float* obs,
-                      const float* task_action, const float* real_action, const uint8_t* recovery,
-                      uint64_t seed, uint64_t counter, uint64_t* counter_dev, uint64_t counter_inc,
-                      int32_t horizon, int auto_reset, float reward_penalty, int push_real_action,
-                      const rrl_replay_t* memory, const rrl_replay_t* recovery_memory, float* next_obs,
-                      float* reward, uint8_t* done, uint8_t* constraint, uint8_t* success, uint8_t* ep_done,
-                      uint64_t* stats, double* reward_sums, float* ep_reward, void* stream) {
+int rrl_nav_step_push_x(int env_kind, const rrl_step_push_t* a, void* stream) {
     if (env_kind != RRL_ENV_NAV1 && env_kind != RRL_ENV_NAV2) return RRL_EINVAL;
     rrl_step::StepPushArgs p;
-    const int rc = rrl_step::fill_args(p, n, pos, t, obs, task_action, 2, real_action, recovery, nullptr, seed, counter,
-                                       counter_dev, counter_inc, horizon, auto_reset, reward_penalty, push_real_action,
-                                       memory, recovery_memory, next_obs, reward, done, constraint, success, ep_done,
-                                       stats, reward_sums, ep_reward);
-    if (rc != RRL_OK || n == 0) return rc;
-    return nav_step_push_launch(env_kind, p, n, stream);
-}
-
-int rrl_nav_step_push_select(int env_kind, int64_t n, double* pos, int32_t* t, float* obs, const float* task_action,
-                             int ld_task, const float* z, int z_n_part, long long z_part_stride,
-                             float eps_safe, const float* rec_action, const rrl_policy_head_t* rec_head,
-                             float* real_action,
-                             uint8_t* recovery, uint64_t seed, uint64_t counter, uint64_t* counter_dev,
-                             uint64_t counter_inc, int32_t horizon, int auto_reset, float reward_penalty,
-                             int push_real_action, const rrl_replay_t* memory, const rrl_replay_t* recovery_memory,
-                             float* next_obs, float* reward, uint8_t* done, uint8_t* constraint, uint8_t* success,
-                             uint8_t* ep_done, uint64_t* stats, double* reward_sums, float* ep_reward, void* stream) {
-    if (env_kind != RRL_ENV_NAV1 && env_kind != RRL_ENV_NAV2) return RRL_EINVAL;
-    rrl_step::StepPushArgs p;
-    const rrl_step::SelectIn sel{z, z_n_part, z_part_stride, eps_safe, rec_action, rec_head, real_action, recovery};
-    const int rc = rrl_step::fill_args(p, n, pos, t, obs, task_action, ld_task, nullptr, nullptr, &sel, seed, counter,
-                                       counter_dev, counter_inc, horizon, auto_reset, reward_penalty, push_real_action,
-                                       memory, recovery_memory, next_obs, reward, done, constraint, success, ep_done,
-                                       stats, reward_sums, ep_reward);
-    if (rc != RRL_OK || n == 0) return rc;
-    return nav_step_push_launch(env_kind, p, n, stream);
+    const int rc = rrl_step::fill_args(p, a);
+    if (rc != RRL_OK || a->n == 0) return rc;
+    return nav_step_push_launch(env_kind, p, a->n, stream);
 }
 
 int rrl_nav_step_push_packed(int S, int env_kind, const rrl_step_push_t* a, void* stream) {
@@ -1098,45 +1071,8 @@ int rrl_nav_step_push_packed(int S, int env_kind, const rrl_step_push_t* a, void
     key.pod(6);
     key.pod(S);
     key.pod(env_kind);
-    for (int s = 0; s < S; ++s) {
-        key.pod(a[s]);
-        if (a[s].memory) key.pod(*a[s].memory);
-        if (a[s].recovery_memory) key.pod(*a[s].recovery_memory);
-        if (a[s].sel_rec_head) key.pod(*a[s].sel_rec_head);
-    }
-    hipStream_t st = (hipStream_t)stream;
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
-    if (!plan) {
-        std::vector<rrl_step::StepPushArgs> ps(S);
-        rrl_pack::Idx ix;
-        ix.S = S;
-        ix.first[0] = 0;
-        const int regime = rrl_step::regime_of(a[0].n);
-        for (int s = 0; s < S; ++s) {
-            const int rc = rrl_step::fill_args(ps[s], &a[s]);
-            if (rc != RRL_OK) return rc;
-            if (a[s].n <= 0 || rrl_step::regime_of(a[s].n) != regime) return RRL_EINVAL;
-            ix.first[s + 1] = ix.first[s] + rrl_step::grid_cover(a[s].n);
-        }
-        for (int s = S; s < rrl_pack::kMaxSeeds; ++s) ix.first[s + 1] = ix.first[S];
-        plan = rrl_pack::store(key, ps.data(), sizeof(rrl_step::StepPushArgs) * S, st);
-        if (!plan) return rrl_pack::store_error();
-        plan->grid = rrl_pack::finish(ix);
-        plan->ix = ix;
-        plan->i0 = regime;
-    }
-    const auto* dev = (const rrl_step::StepPushArgs*)plan->dev;
-    if (env_kind == RRL_ENV_NAV1) rrl_step::launch_pack<NavEnv<0>>(dev, plan->ix, plan->grid, plan->i0, st);
-    else rrl_step::launch_pack<NavEnv<1>>(dev, plan->ix, plan->grid, plan->i0, st);
-    return check_launch();
-}
-
-int rrl_nav_step_push_x(int env_kind, const rrl_step_push_t* a, void* stream) {
-    if (env_kind != RRL_ENV_NAV1 && env_kind != RRL_ENV_NAV2) return RRL_EINVAL;
-    rrl_step::StepPushArgs p;
-    const int rc = rrl_step::fill_args(p, a);
-    if (rc != RRL_OK || a->n == 0) return rc;
-    return nav_step_push_launch(env_kind, p, a->n, stream);
+    if (env_kind == RRL_ENV_NAV1) return rrl_step::launch_packed<NavEnv<0>>(key, S, a, (hipStream_t)stream);
+    return rrl_step::launch_packed<NavEnv<1>>(key, S, a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -595,97 +595,95 @@ inline void launch_pack(const StepPushArgs* dev, const rrl_pack::Idx& ix, int gr
     hipLaunchKernelGGL((advance_cursors_pack_kernel<ENV>), dim3(ix.S), dim3(1), 0, st, dev);
 }
 
-// host side: argument block shared by the navigation and maze entry points
-struct SelectIn {
-    const float* z;
-    int n_part;
-    long long part_stride;
-    float eps_safe;
-    const float* rec_action;
-    const rrl_policy_head_t* rec_head;
-    float* real_out;
-    uint8_t* recovery_out;
-};
-
-inline int fill_args(StepPushArgs& p, int64_t n, double* pos, int32_t* t, float* obs, const float* task_action,
-                     int ld_task, const float* real_action, const uint8_t* recovery, const SelectIn* sel, uint64_t seed,
-                     uint64_t counter, uint64_t* counter_dev, uint64_t counter_inc, int32_t horizon, int auto_reset,
-                     float reward_penalty, int push_real_action, const rrl_replay_t* memory,
-                     const rrl_replay_t* recovery_memory, float* next_obs, float* reward, uint8_t* done,
-                     uint8_t* constraint, uint8_t* success, uint8_t* ep_done, uint64_t* stats, double* reward_sums,
-                     float* ep_reward, uint16_t* status = nullptr) {
-    if (n < 0 || n > 0xffffffffLL) return RRL_ERANGE;
-    if (status && (horizon < 1 || horizon > 4095)) return RRL_ERANGE;      // 12 bits of step count
-    if (!pos || !(t || status) || !obs || !task_action || !memory || !stats || !reward_sums || !ep_reward || ld_task < 2 ||
-        (ld_task & 1))
+// host side: rrl_step_push_t (include/rrl_hip.h) -> the kernel's argument block, for the navigation and maze entry points
+inline int fill_args(StepPushArgs& p, const rrl_step_push_t* a) {
+    if (!a) return RRL_EINVAL;
+    const bool sel = a->sel_z != nullptr;      // the recovery gate runs in the kernel: real_action / recovery are not read
+    if (a->n < 0 || a->n > 0xffffffffLL) return RRL_ERANGE;
+    if (a->status && (a->horizon < 1 || a->horizon > 4095)) return RRL_ERANGE;      // 12 bits of step count
+    if (!a->pos || !(a->t || a->status) || !a->obs || !a->task_action || !a->memory || !a->stats || !a->reward_sums ||
+        !a->ep_reward || a->ld_task < 2 || (a->ld_task & 1))
         return RRL_EINVAL;
-    if (sel ? (!sel->z || (!sel->rec_action && !sel->rec_head) || !sel->real_out || !sel->recovery_out ||
-               sel->n_part <= 0 || sel->n_part > 4) : !real_action)
+    if (sel ? ((!a->sel_rec_action && !a->sel_rec_head) || !a->real_action_out || !a->recovery_out || a->sel_n_part <= 0 ||
+               a->sel_n_part > 4) : !a->real_action)
         return RRL_EINVAL;
-    if (sel && !sel->rec_action) {
-        const rrl_policy_head_t& h = *sel->rec_head;
+    const bool from_head = sel && !a->sel_rec_action;
+    if (from_head) {
+        const rrl_policy_head_t& h = *a->sel_rec_head;
         if (h.kind != RRL_HEAD_STOCH || !h.head || !h.scale || !h.bias || !h.log_std || h.n_part <= 0 || h.n_part > 4)
             return RRL_EINVAL;
     }
-    if (memory->pinned < 0 || n > memory->cap - memory->pinned ||
-        (recovery_memory && (recovery_memory->pinned < 0 || n > recovery_memory->cap - recovery_memory->pinned)))
-        return RRL_ERANGE;
-    p.step = StepArgs{n, (double2*)pos, (const float2*)real_action, nullptr, seed, counter, counter_dev,
-                      counter_inc, (float2*)next_obs, (float2*)obs, reward, done, constraint, success, ep_done,
-                      t, horizon, auto_reset, status};
-    p.task_action = task_action;
-    p.ld_task = ld_task;
-    p.recovery = recovery;
-    p.sel_z = sel ? sel->z : nullptr;
-    p.sel_np = sel ? sel->n_part : 1;
-    p.sel_ps = sel ? sel->part_stride : 0;
-    p.sel_eps = sel ? sel->eps_safe : 0.f;
-    p.sel_rec_action = sel ? (const float2*)sel->rec_action : nullptr;
-    p.sel_rec_head = (sel && !sel->rec_action) ? *sel->rec_head : rrl_policy_head_t{};
-    p.sel_real_out = sel ? (float2*)sel->real_out : nullptr;
-    p.sel_recovery_out = sel ? sel->recovery_out : nullptr;
-    p.reward_penalty = reward_penalty;
-    p.push_real_action = push_real_action;
-    p.memory = *memory;
-    p.use_recovery_memory = recovery_memory != nullptr;
-    p.recovery_memory = recovery_memory ? *recovery_memory : *memory;
-    p.stats = (unsigned long long*)stats;
-    p.reward_sums = reward_sums;
-    p.ep_reward = ep_reward;
-    p.log_rec_i32 = nullptr; p.log_rec_f64 = nullptr; p.log_cap = 0; p.log_state = nullptr;
-    p.log_len = nullptr; p.log_ret = nullptr; p.log_viol = p.log_rec = nullptr;
-    return RRL_OK;
-}
-
-// rrl_step_push_t (the struct entry points rrl_nav_step_push_x / rrl_maze_step_push_x) -> kernel arguments
-inline int fill_step(StepPushArgs& p, const rrl_step_push_t* a);
-inline int fill_log(StepPushArgs& p, const rrl_step_push_t* a, int rc) {
-    if (rc != RRL_OK || !a->log_state) return rc;
-    if (!a->log_rec_i32 || !a->log_rec_f64 || a->log_cap <= 0 || !a->log_len || !a->log_ret || !a->log_viol || !a->log_rec)
+    const rrl_replay_t *m = a->memory, *r = a->recovery_memory;
+    if (m->pinned < 0 || a->n > m->cap - m->pinned || (r && (r->pinned < 0 || a->n > r->cap - r->pinned))) return RRL_ERANGE;
+    const bool lg = a->log_state != nullptr;
+    if (lg && (!a->log_rec_i32 || !a->log_rec_f64 || a->log_cap <= 0 || !a->log_len || !a->log_ret || !a->log_viol ||
+                !a->log_rec))
         return RRL_EINVAL;
-    p.log_rec_i32 = a->log_rec_i32; p.log_rec_f64 = a->log_rec_f64; p.log_cap = a->log_cap; p.log_state = a->log_state;
-    p.log_len = a->log_len; p.log_ret = a->log_ret; p.log_viol = a->log_viol; p.log_rec = a->log_rec;
+    p.step = StepArgs{a->n, (double2*)a->pos, sel ? nullptr : (const float2*)a->real_action, nullptr, a->seed, a->counter,
+                      a->counter_dev, a->counter_inc, (float2*)a->next_obs, (float2*)a->obs, a->reward, a->done,
+                      a->constraint, a->success, a->ep_done, a->t, a->horizon, a->auto_reset, a->status};
+    p.task_action = a->task_action;
+    p.ld_task = a->ld_task;
+    p.recovery = sel ? nullptr : a->recovery;
+    p.sel_z = a->sel_z;
+    p.sel_np = sel ? a->sel_n_part : 1;
+    p.sel_ps = sel ? a->sel_part_stride : 0;
+    p.sel_eps = sel ? a->sel_eps_safe : 0.f;
+    p.sel_rec_action = sel ? (const float2*)a->sel_rec_action : nullptr;
+    p.sel_rec_head = from_head ? *a->sel_rec_head : rrl_policy_head_t{};
+    p.sel_real_out = sel ? (float2*)a->real_action_out : nullptr;
+    p.sel_recovery_out = sel ? a->recovery_out : nullptr;
+    p.reward_penalty = a->reward_penalty;
+    p.push_real_action = a->push_real_action;
+    p.memory = *m;
+    p.use_recovery_memory = r != nullptr;
+    p.recovery_memory = r ? *r : *m;
+    p.stats = (unsigned long long*)a->stats;
+    p.reward_sums = a->reward_sums;
+    p.ep_reward = a->ep_reward;
+    p.log_rec_i32 = lg ? a->log_rec_i32 : nullptr;
+    p.log_rec_f64 = lg ? a->log_rec_f64 : nullptr;
+    p.log_cap = lg ? a->log_cap : 0;
+    p.log_state = a->log_state;
+    p.log_len = lg ? a->log_len : nullptr;
+    p.log_ret = lg ? a->log_ret : nullptr;
+    p.log_viol = lg ? a->log_viol : nullptr;
+    p.log_rec = lg ? a->log_rec : nullptr;
     return RRL_OK;
 }
 
-inline int fill_args(StepPushArgs& p, const rrl_step_push_t* a) {
-    if (!a) return RRL_EINVAL;
-    return fill_log(p, a, fill_step(p, a));
-}
-
-inline int fill_step(StepPushArgs& p, const rrl_step_push_t* a) {
-    if (a->sel_z) {
-        const SelectIn sel{a->sel_z, a->sel_n_part, a->sel_part_stride, a->sel_eps_safe, a->sel_rec_action, a->sel_rec_head,
-                           a->real_action_out, a->recovery_out};
-        return fill_args(p, a->n, a->pos, a->t, a->obs, a->task_action, a->ld_task, nullptr, nullptr, &sel, a->seed,
-                         a->counter, a->counter_dev, a->counter_inc, a->horizon, a->auto_reset, a->reward_penalty,
-                         a->push_real_action, a->memory, a->recovery_memory, a->next_obs, a->reward, a->done, a->constraint,
-                         a->success, a->ep_done, a->stats, a->reward_sums, a->ep_reward, a->status);
+// rrl_*_step_push_packed: the steps of S seeds in one launch (pack.hpp).  `key` arrives holding what the entry point puts
+// in front (its tag, S, and the navigation entry's env kind); the plan is the seeds' argument blocks in device memory.
+template <class ENV>
+inline int launch_packed(rrl_pack::Key& key, int S, const rrl_step_push_t* a, hipStream_t st) {
+    for (int s = 0; s < S; ++s) {
+        key.pod(a[s]);
+        if (a[s].memory) key.pod(*a[s].memory);
+        if (a[s].recovery_memory) key.pod(*a[s].recovery_memory);
+        if (a[s].sel_rec_head) key.pod(*a[s].sel_rec_head);
     }
-    return fill_args(p, a->n, a->pos, a->t, a->obs, a->task_action, a->ld_task, a->real_action, a->recovery, nullptr, a->seed,
-                     a->counter, a->counter_dev, a->counter_inc, a->horizon, a->auto_reset, a->reward_penalty,
-                     a->push_real_action, a->memory, a->recovery_memory, a->next_obs, a->reward, a->done, a->constraint,
-                     a->success, a->ep_done, a->stats, a->reward_sums, a->ep_reward, a->status);
+    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    if (!plan) {
+        std::vector<StepPushArgs> ps(S);
+        rrl_pack::Idx ix;
+        ix.S = S;
+        ix.first[0] = 0;
+        const int regime = regime_of(a[0].n);
+        for (int s = 0; s < S; ++s) {
+            const int rc = fill_args(ps[s], &a[s]);
+            if (rc != RRL_OK) return rc;
+            if (a[s].n <= 0 || regime_of(a[s].n) != regime) return RRL_EINVAL;
+            ix.first[s + 1] = ix.first[s] + grid_cover(a[s].n);
+        }
+        for (int s = S; s < rrl_pack::kMaxSeeds; ++s) ix.first[s + 1] = ix.first[S];
+        plan = rrl_pack::store(key, ps.data(), sizeof(StepPushArgs) * S, st);
+        if (!plan) return rrl_pack::store_error();
+        plan->grid = rrl_pack::finish(ix);
+        plan->ix = ix;
+        plan->i0 = regime;
+    }
+    launch_pack<ENV>((const StepPushArgs*)plan->dev, plan->ix, plan->grid, plan->i0, st);
+    return rrl_host::check_launch();
 }
 
 }  // namespace rrl_step

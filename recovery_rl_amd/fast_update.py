@@ -1058,7 +1058,7 @@ class FastActor:
 
     def act(self, obs, eps_safe, use_recovery, mf_recovery, noise=None, defer_select=False):
         """-> (task action [n,2], executed action [n,2], recovery u8[n] or None); persistent buffers.
-        defer_select: the recovery gate is left to the env-step kernel (rrl_*_step_push_select); `pending_select` then
+        defer_select: the recovery gate is left to the env-step kernel (rrl_step_push_t.sel_*); `pending_select` then
         holds its inputs, the task action is the strided view xa[:, 2:4] and the other two are filled by that kernel."""
         f, n = self.f, self.n
         self.pending_select = None

@@ -44,6 +44,116 @@ def test_argument_validation_without_gpu():
     assert lib.rrl_counter_add(None, 1, None) == -1
 
 
+def _step_push_struct(gate=False, log=False, **fields):
+    """A well-formed rrl_step_push_t whose device pointers are dummy non-null integers (validation never follows them; the
+    two ring descriptions and the head description are host structs and real), then `fields` on top."""
+    d = 0x1000
+    a = _lib.rrl_step_push_t()
+    a.n, a.pos, a.t, a.obs, a.task_action, a.ld_task, a.real_action, a.recovery = 8, d, d, d, d, 2, d, d
+    a.horizon, a.auto_reset, a.stats, a.reward_sums, a.ep_reward = 100, 1, d, d, d
+    a.memory = ctypes.pointer(_lib.rrl_replay_t(s=d, a=d, r=d, s2=d, m=d, cap=100, state=d))
+    a.recovery_memory = ctypes.pointer(_lib.rrl_replay_t(s=d, a=d, r=d, s2=d, m=d, cap=100, state=d, pos_cnt=d))
+    if gate:
+        a.sel_z, a.sel_n_part, a.sel_part_stride, a.sel_eps_safe, a.sel_rec_action = d, 1, 0, 0.3, d
+        a.real_action_out, a.recovery_out = d, d
+    if log:
+        a.log_rec_i32, a.log_rec_f64, a.log_cap, a.log_state = d, d, 64, d
+        a.log_len, a.log_ret, a.log_viol, a.log_rec = d, d, d, d
+    for k, v in fields.items():
+        setattr(a, k, v)
+    return a
+
+
+def _stoch_head(**fields):
+    d = 0x1000
+    h = _lib.rrl_policy_head_t(kind=_lib.HEAD_STOCH, B=8, head=d, n_part=1, scale=d, bias=d, log_std=d)
+    for k, v in fields.items():
+        setattr(h, k, v)
+    return ctypes.pointer(h)
+
+
+def _ring(cap, pinned):
+    d = 0x1000
+    return ctypes.pointer(_lib.rrl_replay_t(s=d, a=d, r=d, s2=d, m=d, cap=cap, state=d, pinned=pinned))
+
+
+def test_step_push_struct_validation_without_gpu():
+    """What rrl_nav_step_push_x / rrl_maze_step_push_x (and the packed entry points with one seed, which forward to them)
+    answer to a malformed rrl_step_push_t: every call returns before any launch.  The codes, and which of RRL_ERANGE /
+    RRL_EINVAL wins when several things are wrong (sizes of n and of the status word's horizon, then required fields, then
+    the gate, then the rings, then the episode log), are those of ABI version 4, recorded from that library."""
+    lib = _lib.load()
+    OK, EINVAL, ERANGE = 0, -1, -3
+    S = _step_push_struct
+    table = [
+        ("NULL struct", None, EINVAL),
+        ("n < 0", S(n=-1), ERANGE),
+        ("n > 2^32 - 1", S(n=1 << 32), ERANGE),
+        ("pos missing", S(pos=None), EINVAL),
+        ("obs missing", S(obs=None), EINVAL),
+        ("task_action missing", S(task_action=None), EINVAL),
+        ("memory missing", S(memory=None), EINVAL),
+        ("stats missing", S(stats=None), EINVAL),
+        ("reward_sums missing", S(reward_sums=None), EINVAL),
+        ("ep_reward missing", S(ep_reward=None), EINVAL),
+        ("neither t nor status", S(t=None), EINVAL),
+        ("status, horizon 0", S(status=0x1000, horizon=0), ERANGE),
+        ("status, horizon 4096", S(status=0x1000, horizon=4096), ERANGE),
+        ("status without t, horizon 4096", S(t=None, status=0x1000, horizon=4096), ERANGE),
+        ("ld_task odd", S(ld_task=3), EINVAL),
+        ("ld_task 1", S(ld_task=1), EINVAL),
+        ("ld_task 0", S(ld_task=0), EINVAL),
+        ("real_action missing, no gate", S(real_action=None), EINVAL),
+        ("gate, real_action_out missing", S(gate=True, real_action_out=None), EINVAL),
+        ("gate, recovery_out missing", S(gate=True, recovery_out=None), EINVAL),
+        ("gate, sel_n_part 0", S(gate=True, sel_n_part=0), EINVAL),
+        ("gate, sel_n_part 5", S(gate=True, sel_n_part=5), EINVAL),
+        ("gate, neither sel_rec_action nor sel_rec_head", S(gate=True, sel_rec_action=None), EINVAL),
+        ("gate, sel_rec_head of the wrong kind", S(gate=True, sel_rec_action=None,
+                                                   sel_rec_head=_stoch_head(kind=_lib.HEAD_GAUSS)), EINVAL),
+        ("gate, sel_rec_head without log_std", S(gate=True, sel_rec_action=None, sel_rec_head=_stoch_head(log_std=None)), EINVAL),
+        ("gate, sel_rec_head with n_part 5", S(gate=True, sel_rec_action=None, sel_rec_head=_stoch_head(n_part=5)), EINVAL),
+        ("n > cap - pinned of memory", S(memory=_ring(100, 93)), ERANGE),
+        ("n > cap - pinned of recovery_memory", S(recovery_memory=_ring(7, 0)), ERANGE),
+        ("pinned < 0 in memory", S(memory=_ring(100, -1)), ERANGE),
+        ("pinned < 0 in recovery_memory", S(recovery_memory=_ring(100, -1)), ERANGE),
+        ("log_state, log_rec_i32 missing", S(log=True, log_rec_i32=None), EINVAL),
+        ("log_state, log_rec_f64 missing", S(log=True, log_rec_f64=None), EINVAL),
+        ("log_state, log_cap 0", S(log=True, log_cap=0), EINVAL),
+        ("log_state, log_len missing", S(log=True, log_len=None), EINVAL),
+        ("log_state, log_ret missing", S(log=True, log_ret=None), EINVAL),
+        ("log_state, log_viol missing", S(log=True, log_viol=None), EINVAL),
+        ("log_state, log_rec missing", S(log=True, log_rec=None), EINVAL),
+        # several things wrong: the first check in the order above answers
+        ("n < 0 and pos missing", S(n=-1, pos=None), ERANGE),
+        ("horizon 0 with status and pos missing", S(status=0x1000, horizon=0, pos=None), ERANGE),
+        ("pos missing and ring too small", S(pos=None, memory=_ring(4, 0)), EINVAL),
+        ("gate incomplete and ring too small", S(gate=True, sel_n_part=0, memory=_ring(4, 0)), EINVAL),
+        ("ring too small and log companion missing", S(log=True, log_len=None, memory=_ring(4, 0)), ERANGE),
+        ("n == 0 does not excuse a missing field", S(n=0, pos=None), EINVAL),
+        # n == 0 with everything valid: nothing to do, no launch
+        ("n == 0", S(n=0), OK),
+        ("n == 0, status instead of t", S(n=0, t=None, status=0x1000, horizon=4095), OK),
+        ("n == 0, gate with a recovery action", S(n=0, gate=True), OK),
+        ("n == 0, gate with a recovery head", S(n=0, gate=True, sel_rec_action=None, sel_rec_head=_stoch_head()), OK),
+        ("n == 0, episode log", S(n=0, log=True), OK),
+        ("n == 0, no recovery_memory", S(n=0, recovery_memory=None), OK),
+    ]
+    for what, a, want in table:
+        assert want != OK or a.n == 0, what          # only an empty step may pass: nothing here reaches a launch
+        arg = None if a is None else ctypes.byref(a)
+        for kind in (0, 1):                         # RRL_ENV_NAV1, RRL_ENV_NAV2
+            assert lib.rrl_nav_step_push_x(kind, arg, None) == want, ("nav", kind, what)
+            assert lib.rrl_nav_step_push_packed(1, kind, arg, None) == want, ("nav packed", kind, what)
+        assert lib.rrl_maze_step_push_x(arg, None) == want, ("maze", what)
+        assert lib.rrl_maze_step_push_packed(1, arg, None) == want, ("maze packed", what)
+    # the env kind is looked at before the struct
+    for kind in (-1, 2, 9):
+        assert lib.rrl_nav_step_push_x(kind, ctypes.byref(S(n=0)), None) == EINVAL
+        assert lib.rrl_nav_step_push_x(kind, ctypes.byref(S(n=-1)), None) == EINVAL
+        assert lib.rrl_nav_step_push_packed(1, kind, ctypes.byref(S(n=0)), None) == EINVAL
+
+
 def test_product_has_no_cpu_fallback():
     import pytest
     import torch

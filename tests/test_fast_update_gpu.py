@@ -274,7 +274,7 @@ def test_loss_fused_head_backward_is_bit_identical_to_the_separate_grad_kernels(
 ))
 def test_grouped_launches_equal_the_separate_ones(env_name, extra):
     """The lock-step iteration with independent kernels sharing launches (rrl_sample_multi, rrl_mlp3_forward_multi,
-    rrl_mlp_*_backward_multi, rrl_policy_heads_fwd_multi, rrl_*_step_push_select: ~30 launches) against the same
+    rrl_mlp_*_backward_multi, rrl_policy_heads_fwd_multi, rrl_*_step_push_x with rrl_step_push_t.sel_*: ~30 launches) against the same
     iteration issued kernel by kernel (~49 launches): after eager iterations AND hipGraph replays every parameter,
     Adam moment, replay row, env state and counter must be bit-identical."""
     import bench

@@ -175,9 +175,10 @@ def test_single_env_protocol():
 
 
 def test_fused_step_push_matches_oracle_step_plus_pushes():
-    """rrl_maze_step_push == checker maze_step + two checker replay pushes + counters, over a ring wrap-around."""
+    """rrl_maze_step_push_x == checker maze_step + two checker replay pushes + counters, over a ring wrap-around."""
     import ctypes as C
     from recovery_rl_amd.replay_memory import ConstraintReplayMemory, ReplayMemory
+    from test_nav_gpu import step_push_args
     lib = _lib.load()
     n, cap = 1500, 4000
     rng = np.random.RandomState(4)
@@ -197,12 +198,8 @@ def test_fused_step_push_matches_oracle_step_plus_pushes():
         task = torch.as_tensor(rng.uniform(-0.1, 0.1, (n, 2)).astype(np.float32), device=DEV)
         real = torch.as_tensor(rng.uniform(-0.13, 0.13, (n, 2)).astype(np.float32), device=DEV)
         rec = torch.as_tensor((rng.uniform(size=n) < 0.3).astype(np.uint8), device=DEV)
-        rc = lib.rrl_maze_step_push(
-            n, _lib.ptr(venv.pos), _lib.ptr(venv.t), _lib.ptr(venv.obs), _lib.ptr(task), _lib.ptr(real),
-            _lib.ptr(rec), venv.seed_value, 0, _lib.ptr(venv.tick), 1, 100, 1, 2.5, 0, C.byref(mem._desc),
-            C.byref(rmem._desc), _lib.ptr(venv.next_obs), _lib.ptr(venv.reward), _lib.ptr(venv.done),
-            _lib.ptr(venv.constraint), _lib.ptr(venv.success), _lib.ptr(venv.ep_done), _lib.ptr(stats),
-            _lib.ptr(sums), _lib.ptr(ep_reward), _lib.current_stream())
+        a = step_push_args(venv, task, real, rec, venv.seed_value, 1, 2.5, mem, rmem, stats, sums, ep_reward, True)
+        rc = lib.rrl_maze_step_push_x(C.byref(a), _lib.current_stream())
         assert rc == 0
         ref = co.maze_step(pos, real.cpu().numpy(), t, seed=venv.seed_value, counter=tick0 + k, auto_reset=True)
         pos, t = ref["pos"], ref["t"]

@@ -39,6 +39,25 @@ def hip_step(env_name, pos, action, t, noise=None, seed=0, counter=0, horizon=10
     return out
 
 
+def step_push_args(venv, task, real, rec, seed, auto_reset, reward_penalty, mem, rmem, stats, sums, ep_reward, with_outputs):
+    """rrl_step_push_t of one fused step of `venv` in the arrays layout (t set, status NULL), without the gate: contiguous
+    task action (ld_task = 2), real_action and recovery given, horizon 100, the tick advanced on the device; the six
+    per-env outputs are venv's arrays or NULL.  Shared with test_maze_gpu.py."""
+    import ctypes as C
+    a = _lib.rrl_step_push_t()
+    a.n, a.pos, a.t, a.obs = venv.num_envs, _lib.ptr(venv.pos), _lib.ptr(venv.t), _lib.ptr(venv.obs)
+    a.task_action, a.ld_task, a.real_action, a.recovery = _lib.ptr(task), 2, _lib.ptr(real), _lib.ptr(rec)
+    a.seed, a.counter, a.counter_dev, a.counter_inc = seed, 0, _lib.ptr(venv.tick), 1
+    a.horizon, a.auto_reset, a.reward_penalty, a.push_real_action = 100, auto_reset, reward_penalty, 0
+    a.memory, a.recovery_memory = C.pointer(mem._desc), C.pointer(rmem._desc)
+    if with_outputs:
+        a.next_obs, a.reward = _lib.ptr(venv.next_obs), _lib.ptr(venv.reward)
+        a.done, a.constraint = _lib.ptr(venv.done), _lib.ptr(venv.constraint)
+        a.success, a.ep_done = _lib.ptr(venv.success), _lib.ptr(venv.ep_done)
+    a.stats, a.reward_sums, a.ep_reward = _lib.ptr(stats), _lib.ptr(sums), _lib.ptr(ep_reward)
+    return a
+
+
 def assert_same(a, b, keys=("pos", "t", "next_obs", "obs", "reward", "done", "constraint", "success", "ep_done")):
     for k in keys:
         assert np.array_equal(a[k], b[k]), "%s differs in %d rows" % (k, int((a[k] != b[k]).sum()))
@@ -312,7 +331,7 @@ def test_full_size_properties_4096x100():
 @pytest.mark.parametrize("with_outputs,n,cap", [(True, 1500, 4000), (False, 1500, 4000), (True, 40000, 100000),
                                                 (False, 300000, 700000)])
 def test_fused_step_push_matches_oracle_step_plus_pushes(env, with_outputs, n, cap):
-    """rrl_nav_step_push == oracle nav_step + two oracle replay pushes + counters, over a wrap-around; with and without
+    """rrl_nav_step_push_x == oracle nav_step + two oracle replay pushes + counters, over a wrap-around; with and without
     the optional per-env output arrays (next_obs, reward, flags: NULL = not written, everything else unchanged)."""
     import ctypes as C
     from recovery_rl_amd.replay_memory import ConstraintReplayMemory, ReplayMemory
@@ -334,13 +353,8 @@ def test_fused_step_push_matches_oracle_step_plus_pushes(env, with_outputs, n, c
         task = torch.as_tensor(rng.uniform(-1, 1, (n, 2)).astype(np.float32), device=DEV)
         real = torch.as_tensor(rng.uniform(-1.3, 1.3, (n, 2)).astype(np.float32), device=DEV)
         rec = torch.as_tensor((rng.uniform(size=n) < 0.3).astype(np.uint8), device=DEV)
-        rc = lib.rrl_nav_step_push(
-            co.ENV_KIND[env], n, _lib.ptr(venv.pos), _lib.ptr(venv.t), _lib.ptr(venv.obs), _lib.ptr(task),
-            _lib.ptr(real), _lib.ptr(rec), 31, 0, _lib.ptr(venv.tick), 1, 100, 1, 2.5, 0, C.byref(mem._desc),
-            C.byref(rmem._desc), *([_lib.ptr(venv.next_obs), _lib.ptr(venv.reward), _lib.ptr(venv.done),
-                                    _lib.ptr(venv.constraint), _lib.ptr(venv.success), _lib.ptr(venv.ep_done)]
-                                   if with_outputs else [None] * 6), _lib.ptr(stats),
-            _lib.ptr(sums), _lib.ptr(ep_reward), _lib.current_stream())
+        a = step_push_args(venv, task, real, rec, 31, 1, 2.5, mem, rmem, stats, sums, ep_reward, with_outputs)
+        rc = lib.rrl_nav_step_push_x(co.ENV_KIND[env], C.byref(a), _lib.current_stream())
         assert rc == 0
         ref = co.nav_step(env, pos, real.cpu().numpy(), t, seed=31, counter=1 + k, auto_reset=True)
         if with_outputs:
@@ -407,10 +421,8 @@ def test_fused_step_push_counts_when_a_workgroup_wraps_over_three_super_chunks()
         obs_prev = venv.obs.cpu().numpy().copy()
         real = torch.as_tensor(rng.uniform(-1, 1, (n, 2)).astype(np.float32), device=DEV)
         rec = torch.zeros(n, dtype=torch.uint8, device=DEV)
-        rc = lib.rrl_nav_step_push(0, n, _lib.ptr(venv.pos), _lib.ptr(venv.t), _lib.ptr(venv.obs), _lib.ptr(real),
-                                   _lib.ptr(real), _lib.ptr(rec), 5, 0, _lib.ptr(venv.tick), 1, 100, 0, 0.0, 0,
-                                   C.byref(mem._desc), C.byref(rmem._desc), None, None, None, None, None, None,
-                                   _lib.ptr(stats), _lib.ptr(sums), _lib.ptr(ep_reward), _lib.current_stream())
+        a = step_push_args(venv, real, real, rec, 5, 0, 0.0, mem, rmem, stats, sums, ep_reward, False)
+        rc = lib.rrl_nav_step_push_x(0, C.byref(a), _lib.current_stream())
         assert rc == 0
         ref = co.nav_step("navigation1", pos, real.cpu().numpy(), t, seed=5, counter=1 + k, auto_reset=False)
         pos, t = ref["pos"], ref["t"]
