@@ -419,24 +419,12 @@ int rrl_mlp3_forward(int G, int M, int H, int din, int dout, const float* x, int
  * leaves that many partials in scratch), 0 otherwise */
 int rrl_mlp3_is_split(int M, int H);
 
-/* Thin ends of the stack backward (one side 1..4 wide, so no MFMA tile):
- *   rrl_mlp_head_backward : dW3 = dOut^T h2, db3 = sum_b dOut, dh2 = [h2 > 0] (dOut W3)   (dW3/db3 nullable)
- *   rrl_mlp_input_backward: dW1 = dh1^T x, db1 = sum_b dh1 (nullable pair), dx = dh1 W1    (dx nullable)
- * dOut [G,B,dout], h2/dh2/dh1 [G,B,H], W3 [G,dout,H], W1 [G,H,din], x [B,din] shared by the heads. */
-int rrl_mlp_head_backward(int G, int B, int H, int dout, const float* dOut, const float* h2, const float* W3,
-                          float* dW3, float* db3, float* dh2, void* stream);
-int rrl_mlp_input_backward(int G, int B, int H, int din, const float* dh1, const float* x, int ldx,
-                           const float* W1, float* dW1, float* db1, float* dx, void* stream);
-
-/* Hidden layer of the stack backward in ONE launch (both products read dh2 and are independent):
- *   dW2[g] = dh2[g]^T h1[g], db2[g] = column sums of dh2[g]   and   dh1[g] = (dh2[g] W2[g]) * [h1[g] > 0]
- * dh2, h1, dh1 [G,B,H]; W2, dW2 [G,H,H]; db2 [G,H]. */
-int rrl_mlp_hidden_backward(int G, int B, int H, const float* dh2, const float* h1, const float* W2, float* dW2,
-                            float* db2, float* dh1, void* stream);
-
-/* rrl_mlp_head_backward with dOut produced in the kernel from a loss description instead of read from memory:
- * saves the stand-alone rrl_*_grad / rrl_*_head_bwd launch in front of every stack backward (same formulas,
- * bit-identical dOut).  kind selects the formula and the meaning of the fields:
+/* Loss description of a stack backward (rrl_head_bwd_t.loss): where the last layer's backward takes dOut [G,B,dout], the
+ * gradient w.r.t. the stack's output, from.
+ *   kind = -1: `out` IS dOut, a plain contiguous tensor; no other field is read.
+ *   kind >= 0: dOut is produced in the kernel from the operands named below instead of read from memory, which saves
+ *              the stand-alone rrl_*_grad / rrl_*_head_bwd launch in front of every stack backward (same formulas,
+ *              bit-identical dOut).  kind selects the formula and the meaning of the fields:
  *   RRL_LOSS_SAC_CRITIC   (G=2,dout=1) out=q, out_t=qt, v0=logp2, v1=r, v2=m, v3=penalty (nullable), alpha,
  *                         f0=gamma; loss[2] = the two MSEs                              (sac.py:192-214)
  *   RRL_LOSS_SAC_POLICY   (G=2,dout=1) out=qp, v0=logp, alpha; loss[1]                  (sac.py:216-231)
@@ -450,7 +438,8 @@ int rrl_mlp_hidden_backward(int G, int B, int H, const float* dh2, const float* 
  *                         the Lagrangian policy loss nu (max sigmoid(zp) - eps_safe) of --DGD_constraints (sac.py:221-228),
  *                         dOut = nu w_g / B q_g (1 - q_g) -- RRL_LOSS_QRISK_POLICY scaled by nu, a critic-loss kind
  *                         wherever those are accepted (the paired launch included)
- * out / out_t take (n_part, part_stride) like the stand-alone kernels. */
+ * out / out_t take (n_part, part_stride) like the stand-alone kernels: 1 <= n_part <= 4.  G and dout of the stack must be
+ * the kind's (else RRL_EINVAL); an unknown kind, n_part, da_parts or da_group out of range: RRL_ERANGE. */
 enum { RRL_LOSS_SAC_CRITIC = 0, RRL_LOSS_SAC_POLICY = 1, RRL_LOSS_QRISK_CRITIC = 2, RRL_LOSS_QRISK_POLICY = 3,
        RRL_LOSS_GAUSS_HEAD = 4, RRL_LOSS_STOCH_HEAD = 5, RRL_LOSS_DGD_QRISK = 6 };
 typedef struct {
@@ -471,26 +460,24 @@ typedef struct {
                                   * four consecutive ones are summed first ((p0 + p1) + p2) + p3, then the group sums one
                                   * after the other -- the value a producer that folds (rrl_first_layer_t.dx_fold) stores */
 } rrl_loss_t;
-int rrl_mlp_head_backward_loss(const rrl_loss_t* loss, int G, int B, int H, int dout, const float* h2,
-                               const float* W3, float* dW3, float* db3, float* dh2, void* stream);
 
 /* --------------------------------------------------------------------------------------------
  * Grouped launches.  One SAC / Q_risk update is a chain of ~40 tiny DEPENDENT kernels whose cost is the launch
  * boundary and a few memory round trips each, not their arithmetic; kernels that do not depend on each other
  * (the three critic forwards of sac.py:192-218 once both actions are sampled; the critic's backward for the
  * critic loss and for the policy loss; the task policy and the recovery policy of the acting pass) share ONE
- * launch here, so the chain is as long as its dependency depth.  Every member runs the code of its stand-alone
- * entry point on its own workgroups: results are bit-identical to the separate launches.  n <= 4.
+ * launch here, so the chain is as long as its dependency depth.  Every member runs on its own workgroups: a launch of
+ * n members gives the bits of n launches of one member each.  1 <= n <= 4.  The three stages of a stack backward exist as
+ * descriptors only (one stack: n = 1); every descriptor is validated before anything is launched.
  *   rrl_mlp3_forward_multi        members = rrl_mlp3_forward calls; all members must take the same path (all with
  *                                 scratch on the split path -- partial sums stay in scratch, finalize = 0 -- or all
  *                                 on the same plain tiling), else RRL_EINVAL.  Split-path members of hidden width 256
  *                                 may differ in size (round 6: a 4096-row acting forward riding with an update's 256-row
  *                                 forwards): they then run on a flat grid of exactly the workgroups each member needs,
  *                                 every member on the tiles of its stand-alone launch -- list the large member first
- *   rrl_mlp_head_backward_multi   members = rrl_mlp_head_backward_loss calls (loss.kind = -1: loss.out is a plain
- *                                 dOut tensor as in rrl_mlp_head_backward)
- *   rrl_mlp_hidden_backward_multi members = rrl_mlp_hidden_backward calls; dW2 = db2 = NULL: only dh1
- *   rrl_mlp_input_backward_multi  members = rrl_mlp_input_backward calls
+ *   rrl_mlp_head_backward_multi   members = rrl_head_bwd_t: the last layer's backward of one stack each
+ *   rrl_mlp_hidden_backward_multi members = rrl_hidden_bwd_t: the two H x H products of one stack each (+ its first layer)
+ *   rrl_mlp_input_backward_multi  members = rrl_input_bwd_t: the first layer's backward of one stack each
  *   rrl_mlp_backward_pair_multi   = rrl_mlp_head_backward_multi(n, heads) followed by rrl_mlp_hidden_backward_multi(n, hidden),
  *                                 stack k's two stages linked by heads[k].dh2 == hidden[k].dh2.  When every member is a
  *                                 critic-loss kind (RRL_LOSS_SAC_CRITIC .. RRL_LOSS_QRISK_POLICY, one output) with full
@@ -515,13 +502,18 @@ typedef struct {
      * 16 x 16 half-used 128-byte lines: -15 % on every forward launch (profiles/round5_fwd_packed/).  Same values, same bits. */
     const float* W2p;
 } rrl_stack_t;
+/* Last layer of a stack backward (one side 1..4 wide, so no MFMA tile), given dOut [G,B,dout] as `loss` describes it:
+ *   dW3[g] = dOut[g]^T h2[g], db3[g] = sum_b dOut[g]      and      dh2[g] = [h2[g] > 0] (dOut[g] W3[g])
+ * Limits: B <= 1024, dout <= 4 (RRL_ERANGE). */
 typedef struct {
-    rrl_loss_t loss;
-    int G, B, H, dout;
-    const float *h2, *W3;
-    float *dW3, *db3, *dh2;
+    rrl_loss_t loss;          /* loss.out required (RRL_EINVAL) */
+    int G, B, H, dout;        /* heads, batch rows, hidden width, outputs per head */
+    const float *h2, *W3;     /* required: h2 [G,B,H] the saved activation, W3 [G,dout,H] */
+    float *dW3, *db3;         /* [G,dout,H], [G,dout]; nullable: no weight gradient unless both are given */
+    float* dh2;               /* [G,B,H]; nullable: weight gradients and loss scalars only.  In rrl_mlp_backward_pair_multi it
+                               * is the link to hidden[k].dh2 and is NOT written when the two stages go out as one launch */
 } rrl_head_bwd_t;
-/* First layer of the stack backward done by the hidden-layer launch itself (instead of rrl_mlp_input_backward as a
+/* First layer of the stack backward done by the hidden-layer launch itself (instead of an rrl_input_bwd_t in a
  * dependent launch): every 16 x 16 tile of dh1 = (dh2 W2) * [h1 > 0] also emits its share of
  *   dW1 = dh1^T x, db1 = column sums of dh1   -> first_part [B/16][first_stride]: row-tile t's partial of dW1[g][h][d] at
  *                                                 t*first_stride + (g*H + h)*din + d, of db1[g][h] at ... + G*H*din + g*H + h
@@ -533,7 +525,8 @@ typedef struct {
  *                                                 hidden backward; the one-tile-per-workgroup launches return RRL_ERANGE).
  * Consumers add the partials in a fixed order: rrl_adam_step_multi (g_part fields of the segment) and the policy-head
  * backward (da_parts / da_group of rrl_loss_t: 16 tile partials with da_group = 4 give the bits of 4 folded ones).
- * x = NULL: no first-layer work (then dh1 must be given).  Needs B, H % 128 == 0. */
+ * x = NULL: no first-layer work (then dh1 must be given).  With x: W1 and one of first_part / dx_part required, din <= 4
+ * (RRL_EINVAL); B, H % 128 == 0 and 16-byte aligned dh2, h1, W2 (RRL_ERANGE). */
 typedef struct {
     const float *x, *W1;
     int ldx, din;
@@ -542,16 +535,24 @@ typedef struct {
     float* dx_part;
     int dx_fold;
 } rrl_first_layer_t;
+/* Hidden layer of a stack backward: both products read dh2 and are independent, one launch on the MFMA tiles
+ *   dW2[g] = dh2[g]^T h1[g], db2[g] = column sums of dh2[g]      and      dh1[g] = (dh2[g] W2[g]) * [h1[g] > 0]
+ * Any B, H (ragged tiles are bounds-checked); G <= 65535. */
 typedef struct {
     int G, B, H;
-    const float *dh2, *h1, *W2;
-    float *dW2, *db2, *dh1;       /* dh1 nullable when `first` consumes it */
+    const float *dh2, *h1, *W2;   /* required: dh2, h1 [G,B,H]; W2 [G,H,H] */
+    float *dW2, *db2;             /* [G,H,H], [G,H]; both or neither (RRL_EINVAL); both NULL: the input gradient dh1 only */
+    float* dh1;                   /* [G,B,H]; nullable when `first` consumes it, else required (RRL_EINVAL) */
     rrl_first_layer_t first;
 } rrl_hidden_bwd_t;
+/* First layer of a stack backward as a launch of its own (one side 1..4 wide), dh1 [G,B,H] already masked by relu':
+ *   dW1[g] = dh1[g]^T x, db1[g] = sum_b dh1[g]      and      dx[g] = dh1[g] W1[g]
+ * din <= 4 (RRL_ERANGE). */
 typedef struct {
-    int G, B, H, din, ldx;
-    const float *dh1, *x, *W1;
-    float *dW1, *db1, *dx;
+    int G, B, H, din, ldx;        /* ldx: floats between rows of x */
+    const float *dh1, *x, *W1;    /* required: x [B,din] shared by the heads, W1 [G,H,din] */
+    float *dW1, *db1;             /* [G,H,din], [G,H]; nullable: no weight gradient unless both are given */
+    float* dx;                    /* [G,B,din]; nullable: no input gradient.  Neither wanted: the member is skipped */
 } rrl_input_bwd_t;
 int rrl_mlp3_forward_multi(int n, const rrl_stack_t* stacks, void* stream);
 /* ONE column-split stack (H = 256) with rider workgroups in front of its tiles: launches that nothing in this launch waits
@@ -595,9 +596,6 @@ int rrl_mlp_backward_pair_multi(int n, const rrl_head_bwd_t* heads, const rrl_hi
  *                            sac.py:202-205; lambda read from device memory) and mean[0] = the batch mean of max sigmoid(z)
  *                            (penalty = NULL: the mean only -- the nu step of --update_nu at (s, pi))
  *   rrl_stoch_head_fwd/bwd   StochasticPolicy.sample and its backward (model.py:511-525)
- *   rrl_adam_step            torch.optim.Adam step over one flat f32 buffer + optional Polyak update
- *                            of a target buffer (recovery_rl/utils.py:46-49); step_dev = uint64[2]
- *                            {t, ticket}, t is incremented by the kernel
  *   rrl_recovery_select      recovery gate max sigmoid(z) > eps_safe and action select
  *                            (recovery_rl/experiment.py:546-577)
  * Operands that are stack outputs (head, q, qt, qp, z, zt, zp, raw) take (n_part, part_stride): the value of
@@ -631,28 +629,32 @@ int rrl_stoch_head_bwd(int B, const float* raw, int n_part, long long part_strid
                        const float* log_std, float min_log_std, const float* scale, const float* d_action, int ld,
                        int n_heads, long long head_stride, float* draw, float* dlog_std, void* stream);
 int rrl_policy_heads_fwd_multi(int n, const rrl_policy_head_t* heads, void* stream);
-int rrl_adam_step(long long n, float* p, const float* g, float* m, float* v, uint64_t* step_dev, float lr,
-                  float beta1, float beta2, float eps, float* target, float tau, void* stream);
-/* rrl_adam_step for up to RRL_ADAM_MAX_SEGS flat buffers in one launch (e.g. critic + policy of one update);
- * every segment has its own step counter and optional Polyak target. */
+/* The optimiser step: torch.optim.Adam over up to RRL_ADAM_MAX_SEGS flat f32 buffers in one launch (e.g. critic + policy
+ * of one update; lr, betas and eps of the launch), every segment with its own step counter and optional Polyak target.
+ * Per element, with t = step_dev[0] + 1 and the bias corrections 1 - beta^t evaluated in double:
+ *   m <- beta1 m + (1 - beta1) g;  v <- beta2 v + (1 - beta2) g^2;  p <- p - lr / (1 - beta1^t) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ *   target <- (1 - tau) target + tau p     (soft_update, recovery_rl/utils.py:46-49, on the UPDATED p; target = NULL: none)
+ * and the segment's last workgroup stores t. */
 #define RRL_ADAM_MAX_SEGS 12
 typedef struct {
-    long long n;
-    float* p;
+    long long n;          /* elements, > 0 */
+    float* p;             /* required, like g, m (exp_avg), v (exp_avg_sq): n floats each */
     const float* g;
     float* m;
     float* v;
-    uint64_t* step_dev;
-    float* target;
+    uint64_t* step_dev;   /* required: uint64[2] {t, ticket}; t is incremented by the kernel, the ticket is left at 0 */
+    float* target;        /* nullable: Polyak target, n floats */
     float tau;
     float weight_decay;   /* g <- g + weight_decay * p before the moment updates (torch.optim.Adam weight_decay) */
     const float* g2;      /* nullable: second partial gradient, g <- g + g2 (rrl_ens_train_grad) */
     const float* g_part;  /* nullable: the first part_elems gradients are the sum of n_part partials part_stride apart */
-    int n_part;           /* (first_part of rrl_first_layer_t; added in a fixed order; n_part <= 64, part_elems % 4 == 0) */
+    int n_part;           /* (first_part of rrl_first_layer_t; added in a fixed order; 1 <= n_part <= 64, 0 < part_elems <= n,
+                           * part_elems % 4 == 0, part_stride % 4 == 0, g_part 16-byte aligned: else RRL_EINVAL) */
     long long part_stride, part_elems;
     /* nullable: fragment-order copies (rrl_w2_pack layout, hidden width 256) of the w2_heads [256, 256] matrices that start at
      * element w2_off of p (w2_off % 4 == 0, 16-byte aligned pointers): every updated parameter of that range is stored there
-     * too -- and the Polyak target's into target_w2p -- so that the forward kernels' rrl_stack_t.W2p stays current */
+     * too -- and the Polyak target's into target_w2p -- so that the forward kernels' rrl_stack_t.W2p stays current.  A captured
+     * iteration re-makes nothing between its launches: this is the only step that keeps the copies of a replayed forward current */
     float* w2p;
     float* target_w2p;
     long long w2_off;

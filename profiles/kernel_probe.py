@@ -46,9 +46,9 @@ p, g_, m, v = r(n), r(n), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
 tgt = r(n)
 step = torch.zeros(2, dtype=torch.int64, device=dev)
 lib = _lib.load()
-print("adam %d: %.2f us" % (n, bench(lambda: lib.rrl_adam_step(n, p.data_ptr(), g_.data_ptr(), m.data_ptr(), v.data_ptr(),
-                                                              step.data_ptr(), 3e-4, 0.9, 0.999, 1e-8, tgt.data_ptr(), 0.005,
-                                                              _lib.current_stream()))))
+seg = (_lib.rrl_adam_seg_t * 1)(_lib.rrl_adam_seg_t(n=n, p=p.data_ptr(), g=g_.data_ptr(), m=m.data_ptr(), v=v.data_ptr(),
+                                                   step_dev=step.data_ptr(), target=tgt.data_ptr(), tau=0.005))
+print("adam %d: %.2f us" % (n, bench(lambda: lib.rrl_adam_step_multi(1, seg, 3e-4, 0.9, 0.999, 1e-8, _lib.current_stream()))))
 for mode, name in ((fused.NT, "NT"), (fused.NN, "NN"), (fused.TN, "TN")):
     for G in (1, 2):
         A, B = r(G, 256, 256), r(G, 256, 256)
@@ -58,14 +58,17 @@ for G, dout, din in ((2, 1, 4), (1, 4, 2)):
     B, H = 256, 256
     dO, h2, W3 = r(G, B, dout), r(G, B, H), r(G, dout, H)
     dW3, db3, dh2 = torch.empty(G, dout, H, device=dev), torch.empty(G, dout, device=dev), torch.empty(G, B, H, device=dev)
-    print("head_bwd G=%d dout=%d: %.2f us" % (G, dout, bench(lambda: lib.rrl_mlp_head_backward(
-        G, B, H, dout, dO.data_ptr(), h2.data_ptr(), W3.data_ptr(), dW3.data_ptr(), db3.data_ptr(), dh2.data_ptr(),
-        _lib.current_stream()))))
+    head = (_lib.rrl_head_bwd_t * 1)(_lib.rrl_head_bwd_t(
+        _lib.rrl_loss_t(kind=-1, n_part=1, out=dO.data_ptr()), G, B, H, dout, h2.data_ptr(), W3.data_ptr(), dW3.data_ptr(),
+        db3.data_ptr(), dh2.data_ptr()))
+    print("head_bwd G=%d dout=%d: %.2f us" % (G, dout, bench(lambda: lib.rrl_mlp_head_backward_multi(
+        1, head, _lib.current_stream()))))
     x, W1 = r(B, din), r(G, H, din)
     dW1, db1, dx = torch.empty(G, H, din, device=dev), torch.empty(G, H, device=dev), torch.empty(G, B, din, device=dev)
-    print("input_bwd G=%d din=%d (w+x): %.2f us" % (G, din, bench(lambda: lib.rrl_mlp_input_backward(
-        G, B, H, din, dh2.data_ptr(), x.data_ptr(), din, W1.data_ptr(), dW1.data_ptr(), db1.data_ptr(), dx.data_ptr(),
-        _lib.current_stream()))))
+    inp = (_lib.rrl_input_bwd_t * 1)(_lib.rrl_input_bwd_t(G, B, H, din, din, dh2.data_ptr(), x.data_ptr(), W1.data_ptr(),
+                                                          dW1.data_ptr(), db1.data_ptr(), dx.data_ptr()))
+    print("input_bwd G=%d din=%d (w+x): %.2f us" % (G, din, bench(lambda: lib.rrl_mlp_input_backward_multi(
+        1, inp, _lib.current_stream()))))
 for H in (256, 128, 64, 32):
     M, din, dout, G = 256, 4, 1, 2
     x = r(M, din)

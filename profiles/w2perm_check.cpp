@@ -12,17 +12,27 @@
 #include <string>
 #include <vector>
 
+#include "../include/rrl_hip.h"
+
 typedef int (*fwd_t)(int, int, int, int, int, const float*, int, const float*, const float*, const float*, const float*,
                      const float*, const float*, float*, float*, float*, float*, int, void*);
-typedef int (*hid_t)(int, int, int, const float*, const float*, const float*, float*, float*, float*, void*);
+typedef int (*hid_t)(int, const rrl_hidden_bwd_t*, void*);
 typedef int (*gemm_t)(int, int, int, int, int, const float*, int, long long, const float*, int, long long, float*, int,
                       long long, const float*, long long, int, const float*, int, long long, float*, long long, int, void*);
 
 struct Lib {
     std::string name;
     fwd_t fwd;
-    hid_t hid;
+    hid_t hid_multi;
     gemm_t gemm;
+    // one stack's hidden-layer backward (dW2 + db2 and dh1) as a launch of its own
+    int hid(int G, int B, int H, const float* dh2, const float* h1, const float* W2, float* dW2, float* db2, float* dh1,
+            void* stream) const {
+        rrl_hidden_bwd_t d{};
+        d.G = G; d.B = B; d.H = H;
+        d.dh2 = dh2; d.h1 = h1; d.W2 = W2; d.dW2 = dW2; d.db2 = db2; d.dh1 = dh1;
+        return hid_multi(1, &d, stream);
+    }
 };
 
 #define HIP(x)                                                                          \
@@ -70,9 +80,9 @@ static bool load(const std::string& dir, const std::string& file, Lib& lib) {
     }
     lib.name = file;
     lib.fwd = (fwd_t)dlsym(h, "rrl_mlp3_forward");
-    lib.hid = (hid_t)dlsym(h, "rrl_mlp_hidden_backward");
+    lib.hid_multi = (hid_t)dlsym(h, "rrl_mlp_hidden_backward_multi");
     lib.gemm = (gemm_t)dlsym(h, "rrl_gemm_f32");
-    return lib.fwd && lib.hid && lib.gemm;
+    return lib.fwd && lib.hid_multi && lib.gemm;
 }
 
 typedef std::vector<std::vector<float>> Result;

@@ -45,7 +45,7 @@ struct GemmArgs {
     long long sA, sB, sC, sBias, sMask, sColsum;  // per-head strides (elements)
     int relu;
     int accumulate;       // C += result
-    // NN tiles of a stack backward can finish the FIRST layer's backward as well (rrl_mlp_input_backward), from the
+    // NN tiles of a stack backward can finish the FIRST layer's backward as well (rrl_first_layer_t), from the
     // 16 x 16 tile of dh1 they hold, instead of a dependent launch that re-reads dh1:
     //   first_part[by][g*H*din + col*din + d] = sum over the tile's 16 rows of dh1[row][col] x[row][d]   (dW1 partial)
     //   first_part[by][G*H*din + g*H + col]   = sum over the tile's 16 rows of dh1[row][col]             (db1 partial)
@@ -407,24 +407,9 @@ __global__ __launch_bounds__(64) void gemm16_kernel(GemmArgs a) {
 
 // The two H x H products of a stack backward share their left operand dh2 and do not depend on each other:
 //   dW2[g] = dh2[g]^T h1[g] (+ column sums = db2)   (TN)        dh1[g] = (dh2[g] W2[g]) * [h1[g] > 0]   (NN)
-// One launch: the first `tn_tiles` workgroups (per head) take the TN tiles, the rest the NN tiles.
-template <bool FAST>
-__global__ __launch_bounds__(64) void gemm16_pair_kernel(GemmArgs tn, GemmArgs nn, int tn_tiles_x, int tn_tiles,
-                                                         int nn_tiles_x) {
-    __shared__ __attribute__((aligned(16))) float As[kPanel * kLd];
-    __shared__ __attribute__((aligned(16))) float Bs[kPanel * kLd];
-    const int b = blockIdx.x, g = blockIdx.y;
-    if (b < tn_tiles) {
-        gemm16_tile<2, FAST>(tn, As, Bs, b % tn_tiles_x, b / tn_tiles_x, g);
-    } else {
-        const int c = b - tn_tiles;
-        gemm16_tile<1, FAST>(nn, As, Bs, c % nn_tiles_x, c / nn_tiles_x, g);
-    }
-}
-
-// Several independent stack backwards (e.g. the critic's backward for its own loss and its backward for the policy
-// loss, sac.py:233-239) share one launch: a flat grid over (problem, head, tile).  Problems with dW2 == null
-// contribute only their NN tiles (input gradient).
+// They share one launch, and so do several independent stack backwards (e.g. the critic's backward for its own loss and
+// its backward for the policy loss, sac.py:233-239): per member the tile counts of both products.  Members with
+// dW2 == null contribute only their NN tiles (input gradient).
 struct HiddenGroup {
     GemmArgs tn[kMaxGroup], nn[kMaxGroup];
     int tn_tiles_x[kMaxGroup], tn_tiles[kMaxGroup], nn_tiles_x[kMaxGroup], per_head[kMaxGroup], fast[kMaxGroup];
@@ -1528,11 +1513,6 @@ __device__ __forceinline__ void input_bwd_body(const InputBwdArgs& ib, int bx, i
     }
 }
 
-__global__ __launch_bounds__(256) void input_bwd_kernel(InputBwdArgs ib) {
-    __shared__ float red[kSlices][5][kCols];
-    input_bwd_body(ib, blockIdx.x, blockIdx.y, red);
-}
-
 struct InputBwdGroup {
     InputBwdArgs p[kMaxGroup];
     int G[kMaxGroup], blocks_x[kMaxGroup];
@@ -1579,35 +1559,23 @@ int rrl_gemm_f32(int mode, int G, int M, int N, int K, const float* A, int lda, 
     return check_launch();
 }
 
-// GemmArgs of one stack's hidden-layer backward (TN: dW2 + db2; NN: dh1)
-static bool hidden_args(int G, int B, int H, const float* dh2, const float* h1, const float* W2, float* dW2, float* db2,
-                        float* dh1, GemmArgs& tn, GemmArgs& nn, const rrl_first_layer_t* fl = nullptr) {
+// GemmArgs of one stack's hidden-layer backward (TN: dW2 + db2; NN: dh1); -> FAST geometry (full tiles, aligned operands)
+static bool hidden_args(const rrl_hidden_bwd_t& p, GemmArgs& tn, GemmArgs& nn) {
+    const int G = p.G, B = p.B, H = p.H;
     const long long sAct = (long long)B * H, sW = (long long)H * H;
     // TN: dW2 [H,H] = dh2^T [H,B] . h1 [B,H], column sums of dh2 -> db2        (A = dh2, K = B)
-    tn = GemmArgs{dh2, h1, dW2, nullptr, nullptr, db2, H, H, B, H, H, H, 0, sAct, sAct, sW, 0, 0, (long long)H, 0, 0};
+    tn = GemmArgs{p.dh2, p.h1, p.dW2, nullptr, nullptr, p.db2, H, H, B, H, H, H, 0, sAct, sAct, sW, 0, 0, (long long)H, 0, 0};
     // NN: dh1 [B,H] = dh2 [B,H] . W2 [H,H], masked by h1 > 0                     (K = H)
-    nn = GemmArgs{dh2, W2, dh1, nullptr, h1, nullptr, B, H, H, H, H, H, H, sAct, sW, sAct, 0, sAct, 0, 0, 0};
-    if (fl && fl->x) {
-        nn.x = fl->x; nn.W1 = fl->W1; nn.first_part = fl->first_part; nn.dx_part = fl->dx_part;
-        nn.first_stride = fl->first_stride; nn.ldx = fl->ldx; nn.din = fl->din; nn.G = G;
-        nn.skip_c = dh1 == nullptr;
-        nn.dx_fold = fl->dx_part ? fl->dx_fold : 0;
+    nn = GemmArgs{p.dh2, p.W2, p.dh1, nullptr, p.h1, nullptr, B, H, H, H, H, H, H, sAct, sW, sAct, 0, sAct, 0, 0, 0};
+    const rrl_first_layer_t& fl = p.first;
+    if (fl.x) {
+        nn.x = fl.x; nn.W1 = fl.W1; nn.first_part = fl.first_part; nn.dx_part = fl.dx_part;
+        nn.first_stride = fl.first_stride; nn.ldx = fl.ldx; nn.din = fl.din; nn.G = G;
+        nn.skip_c = p.dh1 == nullptr;
+        nn.dx_fold = fl.dx_part ? fl.dx_fold : 0;
     }
-    auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    return (H % kTile) == 0 && (B % kTile) == 0 && (H % kPanel) == 0 && (B % kPanel) == 0 && al(dh2) && al(h1) && al(W2);
-}
-
-int rrl_mlp_hidden_backward(int G, int B, int H, const float* dh2, const float* h1, const float* W2, float* dW2,
-                            float* db2, float* dh1, void* stream) {
-    if (!dh2 || !h1 || !W2 || !dW2 || !db2 || !dh1) return RRL_EINVAL;
-    if (G <= 0 || G > 65535 || B <= 0 || H <= 0) return RRL_ERANGE;
-    GemmArgs tn, nn;
-    const bool fast = hidden_args(G, B, H, dh2, h1, W2, dW2, db2, dh1, tn, nn);
-    const int tx = (H + kTile - 1) / kTile, ty = tx, nx = tx, ny = (B + kTile - 1) / kTile;
-    const dim3 grid(tx * ty + nx * ny, G), block(64);
-    if (fast) hipLaunchKernelGGL(gemm16_pair_kernel<true>, grid, block, 0, (hipStream_t)stream, tn, nn, tx, tx * ty, nx);
-    else hipLaunchKernelGGL(gemm16_pair_kernel<false>, grid, block, 0, (hipStream_t)stream, tn, nn, tx, tx * ty, nx);
-    return check_launch();
+    auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    return (H % kTile) == 0 && (B % kTile) == 0 && (H % kPanel) == 0 && (B % kPanel) == 0 && al(p.dh2) && al(p.h1) && al(p.W2);
 }
 
 static int build_hidden_group(int n, const rrl_hidden_bwd_t* ps, HiddenGroup& hg) {
@@ -1623,7 +1591,7 @@ static int build_hidden_group(int n, const rrl_hidden_bwd_t* ps, HiddenGroup& hg
         if (first && (!p.first.W1 || p.first.din <= 0 || p.first.din > 4 || (!p.first.first_part && !p.first.dx_part)))
             return RRL_EINVAL;
         if (!p.dh1 && !first) return RRL_EINVAL;
-        hg.fast[k] = hidden_args(p.G, p.B, p.H, p.dh2, p.h1, p.W2, p.dW2, p.db2, p.dh1, hg.tn[k], hg.nn[k], &p.first);
+        hg.fast[k] = hidden_args(p, hg.tn[k], hg.nn[k]);
         if (first && !hg.fast[k]) return RRL_ERANGE;          // the fused first layer needs full, aligned tiles
         const int tx = (p.H + kTile - 1) / kTile, ny = (p.B + kTile - 1) / kTile;
         hg.tn_tiles_x[k] = tx;
@@ -1773,67 +1741,26 @@ int rrl_mlp_hidden_backward_multi_packed(int S, const int* n, const rrl_hidden_b
     return check_launch();
 }
 
-int rrl_mlp_head_backward(int G, int B, int H, int dout, const float* dOut, const float* h2, const float* W3,
-                          float* dW3, float* db3, float* dh2, void* stream) {
-    if (!dOut || !h2 || !W3 || !dh2) return RRL_EINVAL;
+// HeadBwdArgs of one stack's last-layer backward, validated
+static int head_args(const rrl_head_bwd_t& p, HeadBwdArgs& hb) {
+    const rrl_loss_t& la = p.loss;
+    const int G = p.G, B = p.B, H = p.H, dout = p.dout;
+    if (!la.out || !p.h2 || !p.W3) return RRL_EINVAL;          // dh2 == NULL: weight gradients and loss scalars only
     if (G <= 0 || B <= 0 || B > 1024 || H <= 0 || dout <= 0 || dout > 4) return RRL_ERANGE;
-    HeadBwdArgs hb{};
-    hb.la.kind = kPlainDOut;
-    hb.la.out = dOut;
-    hb.B = B; hb.H = H; hb.dout = dout; hb.need_w = dW3 != nullptr && db3 != nullptr;
-    hb.h2 = h2; hb.W3 = W3; hb.dW3 = dW3; hb.db3 = db3; hb.dh2 = dh2;
-    hipLaunchKernelGGL((head_bwd_loss_kernel<kPlainDOut>), dim3((H + kCols - 1) / kCols, G), dim3(256), 0,
-                       (hipStream_t)stream, hb);
-    return check_launch();
-}
-
-static int head_loss_args(const rrl_loss_t* la, int G, int B, int H, int dout, const float* h2, const float* W3,
-                          float* dW3, float* db3, float* dh2, HeadBwdArgs& hb) {
-    if (!la || !la->out || !h2 || !W3) return RRL_EINVAL;          // dh2 == NULL: weight gradients and loss scalars only
-    if (G <= 0 || B <= 0 || B > 1024 || H <= 0 || dout <= 0 || dout > 4) return RRL_ERANGE;
-    if (la->kind != kPlainDOut) {
-        if (la->kind < 0 || la->kind > RRL_LOSS_DGD_QRISK || la->n_part <= 0 || la->n_part > 4) return RRL_ERANGE;
-        const bool critic = la->kind <= RRL_LOSS_QRISK_POLICY || la->kind == RRL_LOSS_DGD_QRISK;
+    if (la.kind != kPlainDOut) {
+        if (la.kind < 0 || la.kind > RRL_LOSS_DGD_QRISK || la.n_part <= 0 || la.n_part > 4) return RRL_ERANGE;
+        const bool critic = la.kind <= RRL_LOSS_QRISK_POLICY || la.kind == RRL_LOSS_DGD_QRISK;
         const int heads = critic ? 2 : 1;
-        const int width = critic ? 1 : (la->kind == RRL_LOSS_GAUSS_HEAD ? 4 : 2);
+        const int width = critic ? 1 : (la.kind == RRL_LOSS_GAUSS_HEAD ? 4 : 2);
         if (G != heads || dout != width) return RRL_EINVAL;
-        if (la->da_parts < 0 || la->da_parts > 16) return RRL_ERANGE;
-        if ((la->da_group != 0 && la->da_group != 1 && la->da_group != 4) || (la->da_group == 4 && (la->da_parts & 3)))
+        if (la.da_parts < 0 || la.da_parts > 16) return RRL_ERANGE;
+        if ((la.da_group != 0 && la.da_group != 1 && la.da_group != 4) || (la.da_group == 4 && (la.da_parts & 3)))
             return RRL_ERANGE;
     }
-    hb.la = *la;
-    hb.B = B; hb.H = H; hb.dout = dout; hb.need_w = dW3 != nullptr && db3 != nullptr;
-    hb.h2 = h2; hb.W3 = W3; hb.dW3 = dW3; hb.db3 = db3; hb.dh2 = dh2;
+    hb.la = la;
+    hb.B = B; hb.H = H; hb.dout = dout; hb.need_w = p.dW3 != nullptr && p.db3 != nullptr;
+    hb.h2 = p.h2; hb.W3 = p.W3; hb.dW3 = p.dW3; hb.db3 = p.db3; hb.dh2 = p.dh2;
     return RRL_OK;
-}
-
-int rrl_mlp_head_backward_loss(const rrl_loss_t* la, int G, int B, int H, int dout, const float* h2,
-                               const float* W3, float* dW3, float* db3, float* dh2, void* stream) {
-    HeadBwdArgs hb{};
-    if (la && la->kind == kPlainDOut) return RRL_EINVAL;
-    const int rc = head_loss_args(la, G, B, H, dout, h2, W3, dW3, db3, dh2, hb);
-    if (rc != RRL_OK) return rc;
-    const dim3 grid((H + kCols - 1) / kCols, G), block(256);
-    hipStream_t st = (hipStream_t)stream;
-#define RRL_LAUNCH_LOSS(K)                                                            \
-    case K:                                                                           \
-        hipLaunchKernelGGL((head_bwd_loss_kernel<K>), grid, block, 0, st, hb);        \
-        break;
-    switch (la->kind) {
-        RRL_LAUNCH_LOSS(RRL_LOSS_SAC_CRITIC)
-        RRL_LAUNCH_LOSS(RRL_LOSS_SAC_POLICY)
-        RRL_LAUNCH_LOSS(RRL_LOSS_QRISK_CRITIC)
-        RRL_LAUNCH_LOSS(RRL_LOSS_QRISK_POLICY)
-        RRL_LAUNCH_LOSS(RRL_LOSS_GAUSS_HEAD)
-        RRL_LAUNCH_LOSS(RRL_LOSS_STOCH_HEAD)
-        case RRL_LOSS_DGD_QRISK:
-            hipLaunchKernelGGL((head_bwd_loss_kernel<RRL_LOSS_QRISK_POLICY>), grid, block, 0, st, hb);
-            break;
-        default:
-            return RRL_EINVAL;
-    }
-#undef RRL_LAUNCH_LOSS
-    return check_launch();
 }
 
 static int build_head_group(int n, const rrl_head_bwd_t* ps, HeadBwdGroup& hg) {
@@ -1843,7 +1770,7 @@ static int build_head_group(int n, const rrl_head_bwd_t* ps, HeadBwdGroup& hg) {
     hg.first[0] = 0;
     for (int k = 0; k < n; ++k) {
         const rrl_head_bwd_t& p = ps[k];
-        const int rc = head_loss_args(&p.loss, p.G, p.B, p.H, p.dout, p.h2, p.W3, p.dW3, p.db3, p.dh2, hg.p[k]);
+        const int rc = head_args(p, hg.p[k]);
         if (rc != RRL_OK) return rc;
         hg.G[k] = p.G;
         hg.blocks_x[k] = (p.H + kCols - 1) / kCols;
@@ -2055,27 +1982,6 @@ int rrl_mlp_backward_pair_multi_packed(int S, const int* n, const rrl_head_bwd_t
     return check_launch();
 }
 
-static int input_args(int G, int B, int H, int din, const float* dh1, const float* x, int ldx, const float* W1,
-                      float* dW1, float* db1, float* dx, InputBwdArgs& ib, int& blocks) {
-    if (!dh1 || !x || !W1) return RRL_EINVAL;
-    if (G <= 0 || B <= 0 || H <= 0 || din <= 0 || din > 4) return RRL_ERANGE;
-    const int need_w = dW1 != nullptr && db1 != nullptr, need_x = dx != nullptr;
-    ib = InputBwdArgs{B, H, din, ldx, need_w, need_x, dh1, x, W1, dW1, db1, dx};
-    blocks = (need_w ? (H + kCols - 1) / kCols : 0) + (need_x ? (B + 3) / 4 : 0);
-    return RRL_OK;
-}
-
-int rrl_mlp_input_backward(int G, int B, int H, int din, const float* dh1, const float* x, int ldx,
-                           const float* W1, float* dW1, float* db1, float* dx, void* stream) {
-    InputBwdArgs ib;
-    int blocks;
-    const int rc = input_args(G, B, H, din, dh1, x, ldx, W1, dW1, db1, dx, ib, blocks);
-    if (rc != RRL_OK) return rc;
-    if (blocks == 0) return RRL_OK;
-    hipLaunchKernelGGL(input_bwd_kernel, dim3(blocks, G), dim3(256), 0, (hipStream_t)stream, ib);
-    return check_launch();
-}
-
 int rrl_mlp_input_backward_multi(int n, const rrl_input_bwd_t* ps, void* stream) {
     if (!ps || n <= 0 || n > kMaxGroup) return RRL_EINVAL;
     InputBwdGroup ig{};
@@ -2083,10 +1989,12 @@ int rrl_mlp_input_backward_multi(int n, const rrl_input_bwd_t* ps, void* stream)
     int m = 0;
     for (int k = 0; k < n; ++k) {
         const rrl_input_bwd_t& p = ps[k];
-        int blocks;
-        const int rc = input_args(p.G, p.B, p.H, p.din, p.dh1, p.x, p.ldx, p.W1, p.dW1, p.db1, p.dx, ig.p[m], blocks);
-        if (rc != RRL_OK) return rc;
+        if (!p.dh1 || !p.x || !p.W1) return RRL_EINVAL;
+        if (p.G <= 0 || p.B <= 0 || p.H <= 0 || p.din <= 0 || p.din > 4) return RRL_ERANGE;
+        const int need_w = p.dW1 != nullptr && p.db1 != nullptr, need_x = p.dx != nullptr;
+        const int blocks = (need_w ? (p.H + kCols - 1) / kCols : 0) + (need_x ? (p.B + 3) / 4 : 0);
         if (blocks == 0) continue;
+        ig.p[m] = InputBwdArgs{p.B, p.H, p.din, p.ldx, need_w, need_x, p.dh1, p.x, p.W1, p.dW1, p.db1, p.dx};
         ig.G[m] = p.G;
         ig.blocks_x[m] = blocks;
         ig.first[m + 1] = ig.first[m] + blocks * p.G;

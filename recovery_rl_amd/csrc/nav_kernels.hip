@@ -872,7 +872,7 @@ int rrl_pack_clear(void) { return rrl_pack::clear(); }
 
 // 2: pos_cnt carries a second count level (RRL_POS_CNT_LEN); 3: rrl_replay_t.pinned; 4: RRL_DRAW_DEMO_SHARE;
 // 5: the positional forms of the fused env step (plain and with the recovery gate) are gone: rrl_step_push_t is its one form
-int rrl_abi_version(void) { return 5; }
+int rrl_abi_version(void) { return 6; }
 
 int rrl_last_hip_error(void) { return rrl_host::last_hip_error; }
 

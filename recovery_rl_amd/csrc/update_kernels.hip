@@ -623,22 +623,6 @@ __global__ __launch_bounds__(kBlock) void normal_fill_kernel(long long n_pairs, 
     rrl::advance_counter(counter_dev, counter_inc);
 }
 
-__global__ __launch_bounds__(kBlock) void adam_kernel(long long n, float* p, const float* g, float* m,
-                                                      float* v, uint64_t* step_dev, float lr, float b1,
-                                                      float b2, float eps, float* target, float tau, int vec) {
-    __shared__ float sh[2];
-    if (threadIdx.x == 0) {   // bias corrections once per workgroup (double pow is ~100 instructions)
-        const double t = double(step_dev[0] + 1);
-        sh[0] = lr / float(1.0 - pow(double(b1), t));
-        sh[1] = float(sqrt(1.0 - pow(double(b2), t)));
-    }
-    __syncthreads();
-    AdamSlot none;
-    adam_range(n, p, g, m, v, sh[0], sh[1], b1, b2, eps, target, tau, 0.f, nullptr, blockIdx.x, gridDim.x, vec != 0, nullptr, 0, 0,
-               0, none, false);
-    rrl::advance_counter(step_dev, 1);
-}
-
 // ---- acting: recovery gate (experiment.py:546-577) ------------------------------------------------
 // z [2,N] pre-sigmoid Q_risk(s, a_task); recovery = max(sigmoid) > eps_safe; real = recovery ? rec : task
 __global__ void recovery_select_kernel(int N, const float* z, float eps_safe, const float* task_action,
@@ -770,17 +754,6 @@ int rrl_stoch_head_bwd(int B, const float* raw, int n_part, long long part_strid
     hipLaunchKernelGGL(stoch_head_bwd_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, B, raw, n_part,
                        part_stride, eps, log_std, min_log_std, scale, d_action, ld, n_heads, head_stride, draw,
                        dlog_std);
-    return check_launch();
-}
-
-int rrl_adam_step(long long n, float* p, const float* g, float* m, float* v, uint64_t* step_dev, float lr,
-                  float beta1, float beta2, float eps, float* target, float tau, void* stream) {
-    if (!p || !g || !m || !v || !step_dev || n <= 0) return RRL_EINVAL;
-    // <= 64 workgroups: the step ticket is one device-scope atomic per workgroup on a single word
-    const int grid = grid_for(n) < 64 ? grid_for(n) : 64;
-    const int vec = aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(target);
-    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, n, p, g, m, v,
-                       step_dev, lr, beta1, beta2, eps, target, tau, vec);
     return check_launch();
 }
 

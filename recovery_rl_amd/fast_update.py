@@ -111,23 +111,10 @@ class FlatNet:
                     prm.data = dst[i].view(prm.shape)
 
     def adam(self, lr, target=None, tau=0.0, betas=(0.9, 0.999), eps=1e-8, part=None):
-        """`part` = (first_part tensor [T, stride], n_first): the gradients of the leading n_first parameters
-        (W1, b1) arrive as T row-tile partials (Stack.backward with fuse_first)."""
-        packed_copy = self.w2p is not None or (target is not None and target.w2p is not None)
-        if part is not None or packed_copy:
-            # with a fragment-order W2 copy the step MUST be the launch that keeps the copy current (own parameters and
-            # Polyak target): a captured iteration re-makes nothing between its launches (w2_packed), so rrl_adam_step
-            # would leave every replayed forward on the W2 of capture time (batch sizes without fuse_first: part = None)
-            if part is None:
-                record("unsupported", "rrl_adam_step_multi without first-layer partials")
-            return adam_multi(lr, [(self, target, tau, part)], betas, eps)
-        record("unsupported", "rrl_adam_step")
-        lib = _lib.load()
-        rc = lib.rrl_adam_step(self.flat.numel(), self.flat.data_ptr(), self.grad.data_ptr(),
-                               self.m.data_ptr(), self.v.data_ptr(), self.step.data_ptr(), lr, betas[0],
-                               betas[1], eps, None if target is None else target.flat.data_ptr(), tau,
-                               _lib.current_stream())
-        _lib.check(rc, "rrl_adam_step")
+        """One optimiser step of this network alone (adam_multi with one member).  `part` = (first_part tensor
+        [T, stride], n_first): the gradients of the leading n_first parameters (W1, b1) arrive as T row-tile partials
+        (Stack.backward with fuse_first)."""
+        adam_multi(lr, [(self, target, tau, part)], betas, eps)
 
 
 def adam_multi(lr, nets, betas=(0.9, 0.999), eps=1e-8, duals=None):
@@ -231,7 +218,9 @@ class Stack:
         self.split = self.nsplit > 0
         self.scratch = z(max(self.nsplit, 1), G, B, net.dout)
         self.finalize = False                       # True: always hand back the summed output tensor
-        self.pair_hidden = True                     # dW2 and dh1 of the backward in one launch
+        # False is a TEST REFERENCE (tests/test_fast_update_gpu.py): the two hidden-layer products of backward() as
+        # rrl_gemm_f32 launches instead of the hidden-layer descriptor's tiles, for the bit-identity of the two
+        self.pair_hidden = True
         self._folded = False
         self._init_first(dev, G, B, H, net.din)
 
@@ -337,48 +326,32 @@ class Stack:
         return head, hidden, inp
 
     def backward(self, dout, weight_grads=True, input_grad=False, fuse_loss=True):
-        """dout: [G, B, dout] tensor, or an rrl_loss_t describing how the kernel computes it itself
-        (rrl_mlp_head_backward_loss; fuse_loss = False: how the stand-alone launch of its kind computes it first,
-        loss_dout).  Writes parameter gradients into net.g (weight_grads) and/or returns dL/dx per head [G, B, din]
-        (input_grad)."""
+        """dout: [G, B, dout] tensor, or an rrl_loss_t describing how the kernel computes it itself (fuse_loss = False:
+        how the stand-alone launch of its kind computes it first, loss_dout).  Writes parameter gradients into net.g --
+        (dW1, db1) as partials with fuse_first, grad_part -- (weight_grads) and/or returns dL/dx per head (input_grad):
+        [G, B, din], or with fuse_first its column-tile partials (dx_parts)."""
         if not fuse_loss and isinstance(dout, _lib.rrl_loss_t):
             dout = loss_dout(dout, self.B, self.dOut)
-        if self.fuse_first:             # head backward, then hidden + first layer in one launch (rrl_first_layer_t)
-            backward_multi([self.backward_descs(dout, weight_grads, input_grad)])
-            return self.dx_part if input_grad else None
-        P, Gr = self.net.p, self.net.g
-        net, lib, st = self.net, _lib.load(), _lib.current_stream()
-        G, B, H = net.G, self.B, net.H
-        assert self.x.stride(1) == 1
-        gw3 = Gr["W3"].data_ptr() if weight_grads else None
-        gb3 = Gr["b3"].data_ptr() if weight_grads else None
-        # last layer (1..4 outputs): dW3, db3 and the masked dh2 in one streaming kernel
-        if isinstance(dout, _lib.rrl_loss_t):
-            _lib.check(lib.rrl_mlp_head_backward_loss(C.byref(dout), G, B, H, net.dout, self.h2.data_ptr(),
-                                                      P["W3"].data_ptr(), gw3, gb3, self.dh2.data_ptr(), st),
-                       "rrl_mlp_head_backward_loss")
+        descs = self.backward_descs(dout, weight_grads, input_grad)
+        if self.pair_hidden:
+            backward_multi([descs])
         else:
-            assert dout.is_contiguous()
-            _lib.check(lib.rrl_mlp_head_backward(G, B, H, net.dout, dout.data_ptr(), self.h2.data_ptr(),
-                                                 P["W3"].data_ptr(), gw3, gb3, self.dh2.data_ptr(), st),
-                       "rrl_mlp_head_backward")
-        # hidden layer: the two H x H GEMMs on the MFMA kernel -- one launch when both are needed
-        if weight_grads and self.pair_hidden:
-            _lib.check(lib.rrl_mlp_hidden_backward(G, B, H, self.dh2.data_ptr(), self.h1.data_ptr(),
-                                                   P["W2"].data_ptr(), Gr["W2"].data_ptr(), Gr["b2"].data_ptr(),
-                                                   self.dh1.data_ptr(), st), "rrl_mlp_hidden_backward")
-        else:
-            if weight_grads:
-                gemm(TN, self.dh2, self.h1, out=Gr["W2"], colsum=Gr["b2"])
-            gemm(NN, self.dh2, P["W2"], out=self.dh1, mask=self.h1)
-        # first layer (2..4 inputs): dW1, db1 and/or dx in one streaming kernel
-        _lib.check(lib.rrl_mlp_input_backward(G, B, H, net.din, self.dh1.data_ptr(), self.x.data_ptr(),
-                                              self.x.stride(0), P["W1"].data_ptr(),
-                                              Gr["W1"].data_ptr() if weight_grads else None,
-                                              Gr["b1"].data_ptr() if weight_grads else None,
-                                              self.dx.data_ptr() if input_grad else None, st),
-                   "rrl_mlp_input_backward")
-        return self.dx if input_grad else None
+            self._backward_gemm_reference(descs, weight_grads)
+        if not input_grad:
+            return None
+        return self.dx_part if self.fuse_first else self.dx
+
+    def _backward_gemm_reference(self, descs, weight_grads):
+        """pair_hidden = False: head and input stages through their descriptors, dW2 (+ db2) and dh1 as two launches of
+        the general GEMM kernel."""
+        head, _, inp = descs
+        assert inp is not None, "the GEMM reference writes dh1: set_fuse_first(False)"
+        lib, st, P, Gr = _lib.load(), _lib.current_stream(), self.net.p, self.net.g
+        _lib.check(lib.rrl_mlp_head_backward_multi(1, C.byref(head), st), "rrl_mlp_head_backward_multi")
+        if weight_grads:
+            gemm(TN, self.dh2, self.h1, out=Gr["W2"], colsum=Gr["b2"])
+        gemm(NN, self.dh2, P["W2"], out=self.dh1, mask=self.h1)
+        _lib.check(lib.rrl_mlp_input_backward_multi(1, C.byref(inp), st), "rrl_mlp_input_backward_multi")
 
 
 def forward_multi(descs):
@@ -824,7 +797,8 @@ class FastUpdater:
         return self.losses
 
     # -- the sets of independent launches an update is made of: ONE rrl_*_multi launch each (grouped), or member by member
-    #    through the stand-alone entry points -- the same kernels on the same inputs, the same bits either way ------------
+    #    (forwards and policy heads through their stand-alone entry points, backwards as launches of one descriptor) -- the
+    #    same kernel bodies on the same inputs, the same bits either way ---------------------------------------------------
     def _forwards(self, members, grouped, riders=()):
         """Independent stack forwards: members = [(stack, x, options of Stack.forward_desc)]; `riders`: rrl_stack_t of
         another pass's forwards, in front of them in the same launch (FastActor.ride_*).  Grouped: one launch per four

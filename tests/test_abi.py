@@ -154,6 +154,181 @@ def test_step_push_struct_validation_without_gpu():
         assert lib.rrl_nav_step_push_packed(1, kind, ctypes.byref(S(n=0)), None) == EINVAL
 
 
+def _with(struct, **fields):
+    """`struct` with `fields` on top; a dotted name reaches into a nested struct (loss__kind -> .loss.kind)."""
+    for k, v in fields.items():
+        obj, names = struct, k.split("__")
+        for name in names[:-1]:
+            obj = getattr(obj, name)
+        setattr(obj, names[-1], v)
+    return struct
+
+
+def _head_bwd(**fields):
+    """A well-formed rrl_head_bwd_t on a plain dOut tensor (loss.kind = -1); device pointers are dummy non-null integers."""
+    d = 0x1000
+    loss = _lib.rrl_loss_t(kind=-1, n_part=1, out=d)
+    return _with(_lib.rrl_head_bwd_t(loss, 2, 64, 32, 1, d, d, d, d, d), **fields)
+
+
+def _gauss_head_bwd(**fields):
+    """The same with the loss description of a tanh-Gaussian policy head (one head, four outputs)."""
+    d = 0x1000
+    loss = _lib.rrl_loss_t(kind=_lib.LOSS_GAUSS_HEAD, n_part=1, out=d, v0=d, v1=d, d_action=d, ld=4, n_heads=2)
+    return _with(_lib.rrl_head_bwd_t(loss, 1, 64, 32, 4, d, d, d, d, d), **fields)
+
+
+def _hidden_bwd(**fields):
+    d = 0x1000
+    return _with(_lib.rrl_hidden_bwd_t(2, 64, 32, d, d, d, d, d, d, _lib.rrl_first_layer_t()), **fields)
+
+
+def _input_bwd(**fields):
+    d = 0x1000
+    return _with(_lib.rrl_input_bwd_t(2, 64, 32, 4, 4, d, d, d, d, d, d), **fields)
+
+
+def _adam_seg(**fields):
+    d = 0x1000
+    return _with(_lib.rrl_adam_seg_t(n=1 << 17, p=d, g=d, m=d, v=d, step_dev=d), **fields)
+
+
+def test_backward_and_adam_descriptor_validation_without_gpu():
+    """What the descriptor entry points of the stack backward and of the optimiser step (and the packed ones with one seed,
+    which forward to them) answer to a malformed descriptor: every call returns before any launch.  The codes are those
+    of ABI version 5, recorded from that library (where the positional forms still stood beside these).
+    Every case is rejected whatever else the descriptor holds, so nothing here can reach a launch on a machine with a GPU.
+    The partial-gradient count of an Adam segment is bounded by 64, not by the 4 of a stack output's partial sums: n_part
+    = 5 is rejected below for its companion fields (part_elems = 0) and is valid with them, 65 is never valid."""
+    lib = _lib.load()
+    EINVAL, ERANGE = -1, -3
+    d = 0x1000
+    first = lambda **f: _with(_lib.rrl_first_layer_t(x=d, W1=d, ldx=4, din=4, first_part=d, first_stride=512, dx_part=d), **f)
+    heads = [
+        ("h2 missing", _head_bwd(h2=None), EINVAL),
+        ("W3 missing", _head_bwd(W3=None), EINVAL),
+        ("loss.out (dOut) missing", _head_bwd(loss__out=None), EINVAL),
+        ("B 1025", _head_bwd(B=1025), ERANGE),
+        ("B 0", _head_bwd(B=0), ERANGE),
+        ("dout 5", _head_bwd(dout=5), ERANGE),
+        ("loss kind 7", _head_bwd(loss__kind=7), ERANGE),
+        ("loss kind -2", _head_bwd(loss__kind=-2), ERANGE),
+        ("loss n_part 5", _gauss_head_bwd(loss__n_part=5), ERANGE),
+        ("loss n_part 0", _gauss_head_bwd(loss__n_part=0), ERANGE),
+        ("G, dout not the loss kind's", _gauss_head_bwd(G=2), EINVAL),
+        ("da_group 2", _gauss_head_bwd(loss__da_group=2), ERANGE),
+        ("da_group 4 with da_parts 6", _gauss_head_bwd(loss__da_group=4, loss__da_parts=6), ERANGE),
+        ("da_parts 17", _gauss_head_bwd(loss__da_parts=17), ERANGE),
+        # several things wrong: pointers before sizes, sizes before the loss description
+        ("h2 missing and B 1025", _head_bwd(h2=None, B=1025), EINVAL),
+        ("B 1025 and loss kind 7", _head_bwd(B=1025, loss__kind=7), ERANGE),
+        ("loss kind 7 and the wrong G", _gauss_head_bwd(loss__kind=7, G=2), ERANGE),
+    ]
+    hidden = [
+        ("dh2 (the link to the head stage) missing", _hidden_bwd(dh2=None), EINVAL),
+        ("h1 missing", _hidden_bwd(h1=None), EINVAL),
+        ("W2 missing", _hidden_bwd(W2=None), EINVAL),
+        ("dW2 without db2", _hidden_bwd(db2=None), EINVAL),
+        ("db2 without dW2", _hidden_bwd(dW2=None), EINVAL),
+        ("G 65536", _hidden_bwd(G=65536), ERANGE),
+        ("B 0", _hidden_bwd(B=0), ERANGE),
+        ("dh1 missing without first", _hidden_bwd(dh1=None), EINVAL),
+        ("first.x with din 5", _hidden_bwd(B=128, H=128, first=first(din=5)), EINVAL),
+        ("first.x with din 0", _hidden_bwd(B=128, H=128, first=first(din=0)), EINVAL),
+        ("first.x without W1", _hidden_bwd(B=128, H=128, first=first(W1=None)), EINVAL),
+        ("first.x with neither first_part nor dx_part", _hidden_bwd(B=128, H=128, first=first(first_part=None, dx_part=None)),
+         EINVAL),
+        ("first.x on ragged tiles", _hidden_bwd(first=first()), ERANGE),
+        ("first.x on unaligned dh2", _hidden_bwd(B=128, H=128, dh2=d + 4, first=first()), ERANGE),
+        ("dh2 missing and G 65536", _hidden_bwd(dh2=None, G=65536), EINVAL),
+    ]
+    inputs = [
+        ("dh1 missing", _input_bwd(dh1=None), EINVAL),
+        ("x missing", _input_bwd(x=None), EINVAL),
+        ("W1 missing", _input_bwd(W1=None), EINVAL),
+        ("din 5", _input_bwd(din=5), ERANGE),
+        ("din 0", _input_bwd(din=0), ERANGE),
+        ("x missing and din 5", _input_bwd(x=None, din=5), EINVAL),
+    ]
+    one = ctypes.c_int * 1
+    ptrs = lambda T, arr: (ctypes.POINTER(T) * 1)(ctypes.cast(arr, ctypes.POINTER(T)))
+
+    def arr(T, x):
+        a = (T * 5)()                # five slots: a count of 5 is refused before any member is read, but stays in bounds
+        a[0] = x
+        return a
+
+    H, D, I, A = _lib.rrl_head_bwd_t, _lib.rrl_hidden_bwd_t, _lib.rrl_input_bwd_t, _lib.rrl_adam_seg_t
+    good_h, good_d = arr(H, _head_bwd()), arr(D, _hidden_bwd())
+    for what, x, want in heads:
+        a = arr(H, x)
+        assert lib.rrl_mlp_head_backward_multi(1, a, None) == want, ("head", what)
+        assert lib.rrl_mlp_backward_pair_multi(1, a, good_d, None) == want, ("pair", what)
+        assert lib.rrl_mlp_head_backward_multi_packed(1, one(1), ptrs(H, a), None) == want, ("head packed", what)
+        assert lib.rrl_mlp_backward_pair_multi_packed(1, one(1), ptrs(H, a), ptrs(D, good_d), None) == want, ("pair packed", what)
+    for what, x, want in hidden:
+        a = arr(D, x)
+        assert lib.rrl_mlp_hidden_backward_multi(1, a, None) == want, ("hidden", what)
+        assert lib.rrl_mlp_backward_pair_multi(1, good_h, a, None) == want, ("pair", what)
+        assert lib.rrl_mlp_hidden_backward_multi_packed(1, one(1), ptrs(D, a), None) == want, ("hidden packed", what)
+        assert lib.rrl_mlp_backward_pair_multi_packed(1, one(1), ptrs(H, good_h), ptrs(D, a), None) == want, ("pair packed", what)
+    for what, x, want in inputs:
+        assert lib.rrl_mlp_input_backward_multi(1, arr(I, x), None) == want, ("input", what)
+    # the head stage answers before the hidden stage
+    assert lib.rrl_mlp_backward_pair_multi(1, arr(H, _head_bwd(B=1025)), arr(D, _hidden_bwd(dh2=None)), None) == ERANGE
+    # the member count is looked at before any member: 1 .. 4
+    good_i = arr(I, _input_bwd())
+    for n in (0, 5, -1):
+        assert lib.rrl_mlp_head_backward_multi(n, good_h, None) == EINVAL
+        assert lib.rrl_mlp_hidden_backward_multi(n, good_d, None) == EINVAL
+        assert lib.rrl_mlp_input_backward_multi(n, good_i, None) == EINVAL
+        assert lib.rrl_mlp_backward_pair_multi(n, good_h, good_d, None) == EINVAL
+        assert lib.rrl_mlp_head_backward_multi_packed(1, one(n), ptrs(H, good_h), None) == EINVAL
+        assert lib.rrl_mlp_hidden_backward_multi_packed(1, one(n), ptrs(D, good_d), None) == EINVAL
+        assert lib.rrl_mlp_backward_pair_multi_packed(1, one(n), ptrs(H, good_h), ptrs(D, good_d), None) == EINVAL
+    for fn in (lib.rrl_mlp_head_backward_multi, lib.rrl_mlp_hidden_backward_multi, lib.rrl_mlp_input_backward_multi):
+        assert fn(1, None, None) == EINVAL
+    assert lib.rrl_mlp_backward_pair_multi(1, None, good_d, None) == EINVAL
+    assert lib.rrl_mlp_backward_pair_multi(1, good_h, None, None) == EINVAL
+
+    part = dict(g_part=d, n_part=4, part_stride=512, part_elems=256)
+    w2 = dict(w2p=d, target=d, target_w2p=d, w2_off=0, w2_heads=2)
+    segs = [
+        ("p missing", _adam_seg(p=None)),
+        ("g missing", _adam_seg(g=None)),
+        ("m missing", _adam_seg(m=None)),
+        ("v missing", _adam_seg(v=None)),
+        ("step_dev missing", _adam_seg(step_dev=None)),
+        ("n 0", _adam_seg(n=0)),
+        ("g_part with n_part 5 and no part_elems", _adam_seg(g_part=d, n_part=5)),
+        ("g_part with n_part 0", _adam_seg(**dict(part, n_part=0))),
+        ("g_part with n_part 65", _adam_seg(**dict(part, n_part=65))),
+        ("g_part with part_elems 0", _adam_seg(**dict(part, part_elems=0))),
+        ("g_part with part_elems > n", _adam_seg(**dict(part, part_elems=1 << 18))),
+        ("g_part with part_elems 6", _adam_seg(**dict(part, part_elems=6))),
+        ("g_part with part_stride 510", _adam_seg(**dict(part, part_stride=510))),
+        ("g_part unaligned", _adam_seg(**dict(part, g_part=d + 4))),
+        ("w2p unaligned", _adam_seg(**dict(w2, w2p=d + 4))),
+        ("target_w2p unaligned", _adam_seg(**dict(w2, target_w2p=d + 8))),
+        ("w2p with unaligned parameters", _adam_seg(**dict(w2, p=d + 4))),
+        ("w2p with w2_off 2", _adam_seg(**dict(w2, w2_off=2))),
+        ("w2p with w2_heads 0", _adam_seg(**dict(w2, w2_heads=0))),
+        ("w2p past the end of the segment", _adam_seg(**dict(w2, w2_heads=3))),
+    ]
+    lr = (ctypes.c_float * 1)(3e-4)
+    dual = (_lib.rrl_dual_t * 1)(_lib.rrl_dual_t(stat=d, loss_in=d, loss_out=d))
+    for what, x in segs:
+        a = (A * 1)(x)
+        assert lib.rrl_adam_step_multi(1, a, 3e-4, 0.9, 0.999, 1e-8, None) == EINVAL, ("adam", what)
+        assert lib.rrl_adam_step_multi_duals(1, a, 1, dual, 3e-4, 0.9, 0.999, 1e-8, None) == EINVAL, ("adam duals", what)
+        assert lib.rrl_adam_step_multi_packed(1, one(1), ptrs(A, a), lr, 0.9, 0.999, 1e-8, None) == EINVAL, ("adam packed", what)
+    good = (A * 1)(_adam_seg())
+    for n in (0, 13, -1):                       # 1 .. RRL_ADAM_MAX_SEGS
+        assert lib.rrl_adam_step_multi(n, good, 3e-4, 0.9, 0.999, 1e-8, None) == EINVAL
+        assert lib.rrl_adam_step_multi_packed(1, one(n), ptrs(A, good), lr, 0.9, 0.999, 1e-8, None) == EINVAL
+    assert lib.rrl_adam_step_multi(1, None, 3e-4, 0.9, 0.999, 1e-8, None) == EINVAL
+
+
 def test_product_has_no_cpu_fallback():
     import pytest
     import torch

@@ -239,9 +239,10 @@ def test_adam_multi_equals_separate_adam_steps():
 
 @pytest.mark.parametrize("hidden,B", ((32, 64), (256, 256)))
 def test_loss_fused_head_backward_is_bit_identical_to_the_separate_grad_kernels(hidden, B):
-    """rrl_mlp_head_backward_loss evaluates the formulas of the stand-alone *_grad / *_head_bwd kernels inside the
-    head-backward kernel, and rrl_mlp_hidden_backward runs the dW2 / dh1 tiles of rrl_gemm_f32 in one launch: every
-    parameter after 3 updates must be bit-identical to the unfused launches, the logged losses close."""
+    """A head backward with a loss description (rrl_head_bwd_t.loss.kind >= 0) evaluates the formulas of the stand-alone
+    *_grad / *_head_bwd kernels inside the head-backward kernel, and the hidden-layer descriptor (rrl_hidden_bwd_t) runs the
+    dW2 / dh1 tiles of rrl_gemm_f32 in one launch: every parameter after 3 updates must be bit-identical to the unfused
+    launches, the logged losses close."""
     _, a, _ = make_pair(hidden)
     _, b, _ = make_pair(hidden)
     for dst, src in ((b.critic, a.critic), (b.critic_target, a.critic_target), (b.policy, a.policy),
@@ -362,7 +363,7 @@ def test_grouped_entry_points_match_their_members():
 @pytest.mark.parametrize("B", (256,))
 def test_first_layer_backward_inside_the_hidden_launch(B):
     """rrl_first_layer_t: (dW1, db1) as row-tile partials summed by Adam and dx as column-tile partials summed by the
-    policy-head backward, against the stand-alone rrl_mlp_input_backward launch: the partial sums add up to its outputs
+    policy-head backward, against the first layer as a launch of its own (rrl_input_bwd_t): the partial sums add up to its outputs
     (summation order differs: float tolerance), and three updates give the same parameters within Adam's noise floor."""
     _, a, _ = make_pair(256)
     _, b, _ = make_pair(256)
