@@ -173,7 +173,7 @@ typedef struct {
                           * reference never wraps within a run (4e4 env-steps), i.e. never loses them. */
 } rrl_replay_t;
 
-/* Stratified draws (rrl_creplay_sample_gather) that ask for more positives (or negatives) than the ring holds: the
+/* Stratified draws (RRL_DRAW_STRATIFIED) that ask for more positives (or negatives) than the ring holds: the
  * reference aborts (random.sample raises ValueError, replay_memory.py:61-66) and so does the default here (error flag
  * state[3] = 1, outputs untouched).  With this bit the draw takes every row of the short class and fills the batch
  * from the other one: n_pos' = min(n_pos, positives), n_neg' = B - n_pos' (and the other way round).  The lock-step
@@ -188,45 +188,32 @@ int rrl_replay_push(const rrl_replay_t* rb, int64_t n, const float* s, const flo
                     const float* r, const float* s2, const float* m, const uint8_t* valid,
                     int32_t* scratch, void* stream);
 
-/* sample (replay_memory.py:27-30): B distinct uniform rows gathered into 5 batch tensors.
- * idx_out (nullable, int64[B]) receives the chosen slots.  xu / x2u / xpu (nullable, f32 [B,4]) receive the
- * rows pre-assembled for the networks: xu = (s, a), x2u = (s', -, -), xpu = (s, -, -) (columns 2..3 of
- * the latter two are written later by the policy-head kernels).  B <= 1024, cap < 2^31.  If B > size the error
- * flag state[3] is set to 1 and the outputs are left untouched (the reference raises
- * ValueError; callers guard, experiment.py:397,403). */
-int rrl_replay_sample_gather(const rrl_replay_t* rb, int32_t B, uint64_t seed, uint64_t counter,
-                             uint64_t* counter_dev, uint64_t counter_inc, float* s, float* a, float* r, float* s2,
-                             float* m, int64_t* idx_out, float* xu, float* x2u, float* xpu, void* stream);
-
-/* stratified sample (replay_memory.py:54-72): first n_pos rows uniform among slots with r != 0,
- * then n_neg rows uniform among filled slots with r == 0.  Needs rb->pos_cnt. cap <= 2^21.
- * Too few rows of a class: see RRL_REPLAY_CLAMP_STRATIFIED. */
-int rrl_creplay_sample_gather(const rrl_replay_t* rb, int32_t n_pos, int32_t n_neg, uint64_t seed,
-                              uint64_t counter, uint64_t* counter_dev, uint64_t counter_inc, float* s, float* a,
-                              float* r, float* s2, float* m, int64_t* idx_out, float* xu, float* x2u, float* xpu,
-                              void* stream);
-
-/* Demonstration-share sample -- a vectorisation rule, not a reference function: first n_demo distinct uniform rows of the
- * pinned range [0, rb->pinned) (the offline constraint demonstrations, experiment.py:278-286), then n_online distinct
- * uniform rows of the online range [rb->pinned, size).  In a one-env reference run the 20 000 demonstrations stay about
- * half of recovery_memory from the first to the last episode (uniform draw, replay_memory.py:54-72, qrisk.py:100-105);
- * N lock-step envs push N rows per iteration, so a uniform draw over the ring would show the safety critic the
- * demonstrations -- the only violations a safe policy ever produces -- in 2 % of its batch rows.  This draw keeps their
- * share fixed.  A range with fewer rows than asked gives every row it has and the other range fills the batch
- * (n_online' = min(n_online, size - pinned), n_demo' = B - n_online', and the other way round); B > size sets the
- * error flag state[3] = 1.  Same outputs and the same Philox streams as rrl_creplay_sample_gather (demo group = its
- * positive group, online group = its negative group).  B <= 1024, cap < 2^31, 0 <= pinned < cap. */
-int rrl_replay_sample_gather_split(const rrl_replay_t* rb, int32_t n_demo, int32_t n_online, uint64_t seed,
-                                   uint64_t counter, uint64_t* counter_dev, uint64_t counter_inc, float* s, float* a,
-                                   float* r, float* s2, float* m, int64_t* idx_out, float* xu, float* x2u, float* xpu,
-                                   void* stream);
-
-/* Description of one policy-head evaluation (used by rrl_policy_heads_fwd_multi, by the input head of rrl_stack_t and
- * by the recovery action of the fused env step, rrl_step_push_t.sel_rec_head). */
-/* rrl_gauss_head_fwd / rrl_stoch_head_fwd calls that do not depend on each other in ONE launch (n <= 4): a' = pi(s')
- * and pi(s) of one SAC step (sac.py:192-218), the task action and the recovery action of the acting pass
- * (experiment.py:546-577).  kind RRL_HEAD_GAUSS: fields of rrl_gauss_head_fwd (mean_out = mean_action);
- * RRL_HEAD_STOCH: fields of rrl_stoch_head_fwd (head = raw).  Results equal the stand-alone launches'. */
+/* One policy-head evaluation: the sampling step behind a policy stack's last linear layer.  Used by
+ * rrl_policy_heads_fwd_multi (a launch of up to four), by the input head of rrl_stack_t (in_head) and by the recovery
+ * action of the fused env step (rrl_step_push_t.sel_rec_head); the same formulas and the same bits in all three.
+ *   kind         RRL_HEAD_GAUSS: GaussianPolicy.sample (recovery_rl/model.py:324-340).  head[b] = (mean0, mean1, log_std0,
+ *                  log_std1); log_std is clamped to [-20, 2] (model.py:14-16); y = tanh(mean + exp(log_std) eps),
+ *                  action = y scale + bias, mean_out = tanh(mean) scale + bias,
+ *                  logp = sum_j -eps_j^2 / 2 - log_std_j - log(2 pi) / 2 - log(scale_j (1 - y_j^2) + 1e-6).
+ *                RRL_HEAD_STOCH: StochasticPolicy.sample (model.py:511-525).  head[b] = the two raw outputs;
+ *                  mean = tanh(raw) scale + bias, action = mean + exp(max(log_std, min_log_std)) eps, mean_out = mean.
+ *                Anything else: RRL_EINVAL.
+ *   B            rows, >= 1 (RRL_EINVAL); any size: one thread per row, 256 rows per workgroup
+ *   head         [B,4] (Gaussian) / [B,2] (stochastic) f32, required: the stack's output, as n_part partial sums
+ *   n_part,      part_stride floats apart (element i = p[i] + p[part_stride + i] + ..., fixed order: the partial last-layer
+ *   part_stride  sums of rrl_mlp3_forward(scratch, finalize = 0)); n_part = 1: a plain tensor.  1 <= n_part <= 4 (RRL_EINVAL)
+ *   eps          [B,2] N(0,1) draws.  Gaussian: required.  Stochastic: nullable, NULL = no noise (action = mean)
+ *   scale, bias  [2] action_scale / action_bias of the policy, required
+ *   action       out, required: row b at action + b * ld_action (2 floats); ld_action = 2 for a plain [B,2] tensor, 4 to
+ *   ld_action    write columns 2..3 of a [B,4] critic input in place
+ *   logp         [B] out, nullable.  Gaussian only (the stochastic head has no log-probability and ignores the field)
+ *   mean_out     [B,2] out, nullable: the deterministic action (the reference's third return value), both kinds
+ *   obs_in,      Gaussian only, nullable: obs_in [B,2] is copied to obs_out + b * ld_action (2 floats), which assembles the
+ *   obs_out      [s | a] critic input in place when obs_out is the [B,4] buffer and action its column 2.  obs_in without
+ *                obs_out: RRL_EINVAL.  The stochastic head ignores both
+ *   log_std,     stochastic only: the policy's log_std parameter [2] (required) and its lower clamp
+ *   min_log_std
+ * A lone head is rrl_policy_heads_fwd_multi(1, ...). */
 enum { RRL_HEAD_GAUSS = 0, RRL_HEAD_STOCH = 1 };
 typedef struct {
     int kind, B;
@@ -243,12 +230,40 @@ typedef struct {
     float min_log_std;
 } rrl_policy_head_t;
 
-/* The two draws of one lock-step iteration (task buffer -> SAC update, safety buffer -> Q_risk update,
- * experiment.py:397-416) and the iteration's policy noise (rrl_normal_fill) in ONE launch: they do not depend on
- * each other.  A member is a rrl_replay_sample_gather call (stratified = RRL_DRAW_UNIFORM, B = n_pos + n_neg), a
- * rrl_creplay_sample_gather call (RRL_DRAW_STRATIFIED) or a rrl_replay_sample_gather_split call (RRL_DRAW_DEMO_SHARE:
- * n_pos = n_demo, n_neg = n_online); `second` and the noise part (noise_pairs = 0) are optional.
- * Rows, indices and normals equal the stand-alone launches'. */
+/* One replay draw: B = n_pos + n_neg distinct rows of a ring, gathered into five batch tensors (row i of the batch is
+ * drawn by lane i of ONE workgroup).  Replaces ReplayMemory.sample / ConstraintReplayMemory.sample
+ * (replay_memory.py:27-30,54-72).  Three modes (`stratified`); 1 <= B <= 1024 and n_pos, n_neg >= 0 in all of them:
+ *   RRL_DRAW_UNIFORM     sample (replay_memory.py:27-30): B distinct uniform rows among the `size` filled ones; only the
+ *                        sum n_pos + n_neg is used.  cap < 2^31.  B > size: error flag 1 (the reference raises ValueError;
+ *                        callers guard, experiment.py:397,403).
+ *   RRL_DRAW_STRATIFIED  stratified sample (replay_memory.py:54-72): first n_pos rows uniform among the slots with r != 0,
+ *                        then n_neg rows uniform among the filled slots with r == 0.  Needs rb->pos_cnt (RRL_EINVAL
+ *                        without) and cap <= 2^21.  A class with fewer rows than asked: error flag 1, or the clamped draw
+ *                        with RRL_REPLAY_CLAMP_STRATIFIED in rb->flags (then only B > size is an error).
+ *   RRL_DRAW_DEMO_SHARE  a vectorisation rule, not a reference function: first n_pos (= n_demo) distinct uniform rows of the
+ *                        pinned range [0, rb->pinned) (the offline constraint demonstrations, experiment.py:278-286), then
+ *                        n_neg (= n_online) distinct uniform rows of the online range [rb->pinned, size).  In a one-env
+ *                        reference run the 20 000 demonstrations stay about half of recovery_memory from the first to the
+ *                        last episode (uniform draw, replay_memory.py:54-72, qrisk.py:100-105); N lock-step envs push N
+ *                        rows per iteration, so a uniform draw over the ring would show the safety critic the
+ *                        demonstrations -- the only violations a safe policy ever produces -- in 2 % of its batch rows.
+ *                        This draw keeps their share fixed.  A range with fewer rows than asked gives every row it has and
+ *                        the other range fills the batch (n_online' = min(n_online, size - pinned), n_demo' = B - n_online',
+ *                        and the other way round); B > size: error flag 1.  cap < 2^31, 0 <= pinned < cap.
+ * Checked before anything is launched, in this order: the ring (rb, its five arrays and state non-NULL, cap > 0) and the
+ * five outputs, else RRL_EINVAL; n_pos, n_neg and B, else RRL_ERANGE; then the mode's own bounds (capacity, pinned:
+ * RRL_ERANGE; an unknown mode or a stratified draw without pos_cnt: RRL_EINVAL).
+ *   seed, counter      lane i of the first group (uniform: every lane; the positives; the demonstrations) draws from Philox
+ *   counter_dev        stream RRL_STREAM_SAMPLE at row i, lane j of the second group (negatives; online rows) from
+ *   counter_inc        RRL_STREAM_SAMPLE_NEG at row j, at counter + tick (see the conventions above).  A draw that passes
+ *                      its population check does tick += counter_inc; one that raises error flag 1 leaves the tick alone.
+ *   s, a, r, s2, m     out, required: [B,2] [B,2] [B] [B,2] [B] f32
+ *   idx_out            out, nullable: int64[B], the chosen slots
+ *   xu, x2u, xpu       out, nullable: f32 [B,4] rows pre-assembled for the networks, xu = (s, a), x2u = (s', -, -),
+ *                      xpu = (s, -, -) (columns 2..3 of the latter two are written later by the policy heads)
+ * Error flags (rb->state[3], outputs untouched; ReplayMemory.check_error): 1 population too small (above); 2 the
+ * rejection rounds did not end (after the tick advanced); 3 pos_cnt disagrees with the rows (stratified); 4 see
+ * rrl_draw_ahead_t. */
 enum { RRL_DRAW_UNIFORM = 0, RRL_DRAW_STRATIFIED = 1, RRL_DRAW_DEMO_SHARE = 2 };
 typedef struct {
     const rrl_replay_t* rb;
@@ -261,6 +276,12 @@ typedef struct {
     int64_t* idx_out;
     float *xu, *x2u, *xpu;
 } rrl_draw_t;
+/* The two draws of one lock-step iteration (task buffer -> SAC update, safety buffer -> Q_risk update,
+ * experiment.py:397-416) and the iteration's policy noise (rrl_normal_fill: noise_pairs pairs into noise_out, its own
+ * seed and tick) in ONE launch: they do not depend on each other.  `second` and the noise part (noise_pairs = 0) are
+ * optional; a lone draw is rrl_sample_multi(first, NULL, 0, ...).  first == NULL, noise_pairs < 0 or >= 2^32, or
+ * noise_pairs > 0 without noise_out: RRL_EINVAL, before the draws are looked at.  Every member runs on its own
+ * workgroups, so rows, indices and normals do not depend on what else is in the launch. */
 int rrl_sample_multi(const rrl_draw_t* first, const rrl_draw_t* second, long long noise_pairs, uint64_t noise_seed,
                      uint64_t noise_counter, uint64_t* noise_counter_dev, uint64_t noise_counter_inc, float* noise_out,
                      void* stream);
@@ -271,7 +292,7 @@ int rrl_sample_multi(const rrl_draw_t* first, const rrl_draw_t* second, long lon
  * tick is not advanced and no flag raised.  GATHER (a rider of rrl_mlp3_forward_riders) does, after those rows were pushed,
  * what the draw does around its selection: flags rb.state[3] = 1 (B > size') before, = 2 (round cap) after advancing the
  * tick, gathers the rows of the keys into the draw's outputs.  Select + pushes + gather leave exactly what the pushes + the
- * stand-alone draw leave; keys drawn for another tick or size are refused (rb.state[3] = 4). */
+ * whole draw leave; keys drawn for another tick or size are refused (rb.state[3] = 4).  Another mode: RRL_EINVAL. */
 #define RRL_AHEAD_META 8
 typedef struct {
     const rrl_draw_t* draw;      /* RRL_DRAW_UNIFORM */
@@ -308,8 +329,8 @@ typedef struct {
     long long sel_part_stride;
     float sel_eps_safe;
     const float* sel_rec_action;            /* [n,2] the recovery action, or NULL: it is evaluated in the kernel from */
-    const rrl_policy_head_t* sel_rec_head;  /* this RRL_HEAD_STOCH description (rrl_stoch_head_fwd's formula on the
-                                             * recovery policy's stack output) */
+    const rrl_policy_head_t* sel_rec_head;  /* this RRL_HEAD_STOCH description (its formula on the recovery policy's
+                                             * stack output) */
     float* real_action_out;  /* [n,2] out     with the gate: the executed action and the flag, */
     uint8_t* recovery_out;   /* [n]   out     what rrl_recovery_select would have written */
     uint64_t seed, counter;  /* Philox stream position, as rrl_nav_step */
@@ -490,7 +511,7 @@ typedef struct {
  * -- the action in_head yields for the same row (in_head.B is ignored: the stack's M rows) -- so the policy head needs no
  * launch of its own between the policy stack and the critic stack that consumes its action.  Columns 0..1 come from
  * in_head.obs_in (rows 2 floats apart) when given, else from x.  in_head.action / logp / obs_out, when non-null,
- * receive what the stand-alone head kernel would have written (same formulas, same bits). */
+ * receive what the head as a launch of its own would have written (same formulas, same bits). */
 typedef struct {
     int G, M, H, din, dout, ldx;
     const float *x, *W1, *b1, *W2, *b2, *W3, *b3;
@@ -582,9 +603,13 @@ int rrl_mlp_backward_pair_multi(int n, const rrl_head_bwd_t* heads, const rrl_hi
 
 /* --------------------------------------------------------------------------------------------
  * Fused element-wise pieces of the updates (one launch each instead of a chain of PyTorch ops).
- *   rrl_gauss_head_fwd/bwd   GaussianPolicy.sample and its backward (recovery_rl/model.py:324-340);
- *                            head[b] = (mean0, mean1, log_std0, log_std1) raw linear outputs; the backward
- *                            sums d_action over n_heads critic heads (pointer + head_stride, row stride ld)
+ *   rrl_policy_heads_fwd_multi  1 <= n <= 4 policy heads (rrl_policy_head_t, either kind) that do not depend on each
+ *                            other in ONE launch: a' = pi(s') and pi(s) of one SAC step (sac.py:192-218), the task action
+ *                            and the recovery action of the acting pass (experiment.py:546-577).  Every member is validated
+ *                            before anything is launched and runs on its own workgroups
+ *   rrl_gauss_head_bwd       the backward of GaussianPolicy.sample (recovery_rl/model.py:324-340); head as in the
+ *                            RRL_HEAD_GAUSS head; sums d_action over n_heads critic heads (pointer + head_stride, row
+ *                            stride ld)
  *   rrl_sac_critic_grad      target r + m gamma (min Q' - alpha log pi') and d(mse1+mse2)/dq
  *                            (recovery_rl/sac.py:192-214); q, qt are [2,B]; loss[2] = the two MSEs
  *   rrl_sac_policy_grad      d mean(alpha log pi - min Q)/dq (sac.py:216-231); loss[1]
@@ -595,17 +620,13 @@ int rrl_mlp_backward_pair_multi(int n, const rrl_head_bwd_t* heads, const rrl_hi
  *   rrl_rcpo_penalty         penalty[b] = lambda[0] max sigmoid(z[.][b]) for rrl_sac_critic_grad's `penalty` (--RCPO,
  *                            sac.py:202-205; lambda read from device memory) and mean[0] = the batch mean of max sigmoid(z)
  *                            (penalty = NULL: the mean only -- the nu step of --update_nu at (s, pi))
- *   rrl_stoch_head_fwd/bwd   StochasticPolicy.sample and its backward (model.py:511-525)
+ *   rrl_stoch_head_bwd       the backward of StochasticPolicy.sample (model.py:511-525); raw = `head` of RRL_HEAD_STOCH
  *   rrl_recovery_select      recovery gate max sigmoid(z) > eps_safe and action select
  *                            (recovery_rl/experiment.py:546-577)
  * Operands that are stack outputs (head, q, qt, qp, z, zt, zp, raw) take (n_part, part_stride): the value of
  * element i is p[i] + p[part_stride + i] + ... (n_part terms, fixed order) -- the partial last-layer sums of
  * rrl_mlp3_forward(scratch, finalize = 0); n_part = 1 for a plain tensor.
  * ------------------------------------------------------------------------------------------ */
-/* obs_in (nullable, [B,2]) is copied to obs_out (row stride ld_action): builds the [s | a] critic input in place */
-int rrl_gauss_head_fwd(int B, const float* head, int n_part, long long part_stride, const float* eps,
-                       const float* scale, const float* bias, float* action, int ld_action, float* logp,
-                       float* mean_action, const float* obs_in, float* obs_out, void* stream);
 int rrl_gauss_head_bwd(int B, const float* head, int n_part, long long part_stride, const float* eps,
                        const float* scale, const float* d_action, int ld, int n_heads, long long head_stride,
                        float dlogp, float* dhead, void* stream);
@@ -622,9 +643,6 @@ int rrl_dgd_qrisk_grad(int B, const float* zp, int n_part, long long part_stride
                        void* stream);
 int rrl_rcpo_penalty(int B, const float* z, int n_part, long long part_stride, const float* lambda, float* penalty,
                      float* mean, void* stream);
-int rrl_stoch_head_fwd(int B, const float* raw, int n_part, long long part_stride, const float* eps,
-                       const float* log_std, float min_log_std, const float* scale, const float* bias,
-                       float* action, int ld_action, float* mean_out, void* stream);
 int rrl_stoch_head_bwd(int B, const float* raw, int n_part, long long part_stride, const float* eps,
                        const float* log_std, float min_log_std, const float* scale, const float* d_action, int ld,
                        int n_heads, long long head_stride, float* draw, float* dlog_std, void* stream);

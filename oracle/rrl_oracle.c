@@ -747,7 +747,7 @@ int rrl_oracle_sample_stratified_clamped(const rrl_oracle_replay* rb, int32_t n_
 }
 
 /* Demonstration-share draw (the build's vectorisation rule for the safety critic's batch; include/rrl_hip.h
- * rrl_replay_sample_gather_split): n_demo distinct rows of the pinned range [0, pinned), then n_online distinct rows of
+ * rrl_draw_t, mode RRL_DRAW_DEMO_SHARE): n_demo distinct rows of the pinned range [0, pinned), then n_online distinct rows of
  * [pinned, size).  What it restores: in a one-env run of the reference the demonstrations pushed at
  * experiment.py:278-286 stay about half of recovery_memory (uniform draw, replay_memory.py:54-72; batch clamp
  * qrisk.py:100-105).  A range with too few rows gives all of them, the other fills the batch. */

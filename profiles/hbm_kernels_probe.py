@@ -54,9 +54,9 @@ crow = (r(n2, 2), r(n2, 2), (torch.rand(n2, device=dev) < 0.1).float(), r(n2, 2)
 out.append(entry("push_kernel with positive counts (constraint buffer), 2^20 rows", timed(lambda: cmem.push(*crow)), n2, 64, "row"))
 # sampling: latency-bound single workgroup
 t = timed(lambda: mem.sample(256), 100)
-out.append(entry("sample_gather_kernel B=256 (latency-bound, one workgroup)", t, 256, 64, "row"))
+out.append(entry("sample_group_kernel, one uniform draw B=256 (latency-bound, one workgroup)", t, 256, 64, "row"))
 t = timed(lambda: cmem.sample(256, pos_fraction=0.3), 100)
-out.append(entry("creplay_sample_gather_kernel B=256, capacity 2^21 (latency-bound)", t, 256, 64, "row"))
+out.append(entry("sample_group_kernel, one stratified draw B=256, capacity 2^21 (latency-bound)", t, 256, 64, "row"))
 # env reset and maze step
 for name, envname, nenv in (("nav_reset_kernel", "navigation1", 1 << 22), ("maze_reset_kernel", "maze", 1 << 22)):
     env = make_vec_env(envname, nenv, device=dev, seed=1)

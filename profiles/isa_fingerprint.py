@@ -35,6 +35,8 @@ def fingerprint(path):
                 name, h, hm, hv, n = m.group(1), hashlib.sha1(), hashlib.sha1(), hashlib.sha1(), 0
             elif name and line.startswith("\t"):
                 ins = line.split("//")[0].strip()
+                if ins == "...":                                   # objdump's mark for elided zero padding, not an instruction
+                    continue
                 h.update(ins.encode() + b"\n")
                 hm.update(ins.split()[0].encode() + b"\n")      # mnemonics only: blind to kernarg / struct offsets
                 if not ins.startswith("s_"):                      # vector / LDS / memory / MFMA stream, operands included

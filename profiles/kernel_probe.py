@@ -81,4 +81,4 @@ for cap, fill in ((1000000, 300000), (4096, 4096)):
     rows = (r(fill, 2), r(fill, 2), r(fill), r(fill, 2), r(fill))
     mem.push(*rows)
     for B in (64, 256, 1024):
-        print("sample_gather cap=%d size=%d B=%d: %.2f us" % (cap, fill, B, bench(lambda: mem.sample(B))))
+        print("sample_multi, one uniform draw, cap=%d size=%d B=%d: %.2f us" % (cap, fill, B, bench(lambda: mem.sample(B))))

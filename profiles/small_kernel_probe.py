@@ -43,9 +43,14 @@ print("normal_fill 9216 pairs (no ticket): %.2f us" % bench(lambda: lib.rrl_norm
 print("normal_fill 64 pairs (no ticket): %.2f us" % bench(lambda: lib.rrl_normal_fill(64, 1, 0, None, 0, p(out), st())))
 for n in (256, 4096):
     head, eps, scale, bias, act, logp = r(n, 4), r(n, 2), torch.ones(2, device=dev), torch.zeros(2, device=dev), r(n, 4), r(n)
-    print("gauss_head_fwd n=%d: %.2f us" % (n, bench(lambda: lib.rrl_gauss_head_fwd(n, p(head), 1, 0, p(eps), p(scale), p(bias), p(act), 4, p(logp), None, None, None, st()))))
     parts = r(4, n, 4)
-    print("gauss_head_fwd n=%d 4 partials: %.2f us" % (n, bench(lambda: lib.rrl_gauss_head_fwd(n, p(parts), 4, n * 4, p(eps), p(scale), p(bias), p(act), 4, p(logp), None, None, None, st()))))
+    log_std = torch.zeros(2, device=dev)
+    H = lambda kind, t, n_part: (_lib.rrl_policy_head_t * 1)(_lib.rrl_policy_head_t(
+        kind=kind, B=n, head=p(t), n_part=n_part, part_stride=n * 4, eps=p(eps), scale=p(scale), bias=p(bias), action=p(act),
+        ld_action=4, logp=p(logp), log_std=p(log_std), min_log_std=-13.8))
+    for what, hd in (("Gaussian head", H(_lib.HEAD_GAUSS, head, 1)), ("Gaussian head, 4 partials", H(_lib.HEAD_GAUSS, parts, 4)),
+                     ("stochastic head", H(_lib.HEAD_STOCH, head, 1))):
+        print("policy_heads_fwd_multi, one %s, n=%d: %.2f us" % (what, n, bench(lambda: lib.rrl_policy_heads_fwd_multi(1, hd, st()))))
 ctr = torch.zeros(2, dtype=torch.int64, device=dev)
 print("counter_add: %.2f us" % bench(lambda: lib.rrl_counter_add(p(ctr), 1, st())))
 a, b = r(N, 2), r(N, 2)

@@ -1,6 +1,7 @@
 // Torch-free check of the side libraries (librrl_hip_w2perm*.so) against the default library THROUGH THE C ABI:
 // both are dlopen'ed in one process, fed the same device buffers, and every output is compared byte for byte; then the
-// launches are timed with HIP events.  Starts in milliseconds (no Python, no torch import): written for the last GPU minutes
+// launches are timed with HIP events.  Also run with the parent commit's library as the side library when a clean-up moved a
+// surviving kernel's code (the replay draws were added for that, profiles/draw_heads_one_entry_fingerprint.txt).  Starts in milliseconds (no Python, no torch import): written for the last GPU minutes
 // of round 3.      hipcc -O2 -o profiles/_ab_w2perm_check profiles/w2perm_check.cpp -ldl
 //                  profiles/_ab_w2perm_check recovery_rl_amd/csrc [side library file names ...]
 #include <dlfcn.h>
@@ -19,12 +20,19 @@ typedef int (*fwd_t)(int, int, int, int, int, const float*, int, const float*, c
 typedef int (*hid_t)(int, const rrl_hidden_bwd_t*, void*);
 typedef int (*gemm_t)(int, int, int, int, int, const float*, int, long long, const float*, int, long long, float*, int,
                       long long, const float*, long long, int, const float*, int, long long, float*, long long, int, void*);
+typedef int (*push_t)(const rrl_replay_t*, int64_t, const float*, const float*, const float*, const float*, const float*,
+                      const uint8_t*, int32_t*, void*);
+typedef int (*sample_t)(const rrl_draw_t*, const rrl_draw_t*, long long, uint64_t, uint64_t, uint64_t*, uint64_t, float*, void*);
+typedef int (*sample_packed_t)(int, const rrl_sample_args_t*, void*);
 
 struct Lib {
     std::string name;
     fwd_t fwd;
     hid_t hid_multi;
     gemm_t gemm;
+    push_t push;                    // the replay draws (sample_group_kernel / sample_pack_kernel): optional, null in older libraries
+    sample_t sample;
+    sample_packed_t sample_packed;
     // one stack's hidden-layer backward (dW2 + db2 and dh1) as a launch of its own
     int hid(int G, int B, int H, const float* dh2, const float* h1, const float* W2, float* dW2, float* db2, float* dh1,
             void* stream) const {
@@ -82,6 +90,9 @@ static bool load(const std::string& dir, const std::string& file, Lib& lib) {
     lib.fwd = (fwd_t)dlsym(h, "rrl_mlp3_forward");
     lib.hid_multi = (hid_t)dlsym(h, "rrl_mlp_hidden_backward_multi");
     lib.gemm = (gemm_t)dlsym(h, "rrl_gemm_f32");
+    lib.push = (push_t)dlsym(h, "rrl_replay_push");
+    lib.sample = (sample_t)dlsym(h, "rrl_sample_multi");
+    lib.sample_packed = (sample_packed_t)dlsym(h, "rrl_sample_multi_packed");
     return lib.fwd && lib.hid_multi && lib.gemm;
 }
 
@@ -187,6 +198,83 @@ int main(int argc, char** argv) {
                 bad += compare("gemm NT bias relu 256^3 G=2", libs[k], want_g, got_g);
             }
         }
+    }
+    // ---- replay draws: every mode of rrl_draw_t with the noise fill, solo (sample_group_kernel) and two seeds packed
+    //      (sample_pack_kernel); rings of 32 and of 5 super-chunks (the stratified count scan ends on / inside a lane's run) ----
+    for (const int64_t cap : {int64_t(32768), int64_t(5000)}) {
+        bool all = true;
+        for (const auto& l : libs) all = all && l.push && l.sample && l.sample_packed;
+        if (!all) break;
+        const int64_t pinned = 1000, rows = cap - pinned - 300;
+        const int B = 256, pairs = 3000, n_cnt = int(RRL_POS_CNT_LEN(cap));
+        Buf s(2 * rows, 5.f), a(2 * rows, 1.f), r(rows, 1.f), s2(2 * rows, 5.f), m(rows, 1.f);
+        {       // r != 0 for every seventh row or so: the stratified classes
+            std::vector<float> h = r.host();
+            for (auto& v : h) v = v > 0.7f ? 1.f : 0.f;
+            HIP(hipMemcpy(r.d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
+        Buf ring[5] = {Buf(2 * cap), Buf(2 * cap), Buf(cap), Buf(2 * cap), Buf(cap)};
+        Buf words(2 * (4 + 6 * 2) + n_cnt);       // state int64[4], six ticks uint64[2] (four draws, two noise fills), pos_cnt
+        int64_t* state = (int64_t*)words.d;
+        uint64_t *tick = (uint64_t*)(state + 4), *ntick = tick + 8;
+        rrl_replay_t rb{ring[0].d, ring[1].d, ring[2].d, ring[3].d, ring[4].d, cap, state, (int32_t*)(ntick + 4),
+                        RRL_REPLAY_CLAMP_STRATIFIED, pinned};
+        // outputs of two draws (5 tensors, idx int64[B], xu / x2u / xpu) and the normals, for two seeds
+        auto outs = [&](std::vector<Buf*>& o) {
+            for (int k = 0; k < 2 * 2; ++k)
+                for (size_t n : {2 * B, 2 * B, B, 2 * B, B, 2 * B, 4 * B, 4 * B, 4 * B}) o.push_back(new Buf(n));
+            o.push_back(new Buf(2 * pairs)), o.push_back(new Buf(2 * pairs));
+        };
+        std::vector<Buf*> o;
+        outs(o);
+        auto draw = [&](int k, int mode, int n_pos) {
+            Buf** b = &o[9 * k];
+            return rrl_draw_t{&rb, mode, n_pos, B - n_pos, 1234 + uint64_t(k), 0, tick + 2 * k, 1, b[0]->d, b[1]->d, b[2]->d, b[3]->d,
+                              b[4]->d, (int64_t*)b[5]->d, b[6]->d, b[7]->d, b[8]->d};
+        };
+        Result want;
+        char what[96];
+        snprintf(what, sizeof what, "draws cap=%lld solo + 2 seeds packed", (long long)cap);
+        for (size_t k = 0; k < libs.size(); ++k) {
+            for (auto* b : o) b->clear();
+            for (auto& b : ring) HIP(hipMemset(b.d, 0, b.n * sizeof(float)));
+            HIP(hipMemset(words.d, 0, words.n * sizeof(float)));
+            int rc = libs[k].push(&rb, rows, s.d, a.d, r.d, s2.d, m.d, nullptr, nullptr, st);
+            Result got;
+            for (int round = 0; round < 2; ++round) {
+                // uniform + stratified, demo share + uniform, then both pairs as two seeds of one packed launch
+                const rrl_draw_t d[4] = {draw(0, RRL_DRAW_UNIFORM, 0), draw(1, RRL_DRAW_STRATIFIED, 77),
+                                         draw(2, RRL_DRAW_DEMO_SHARE, 128), draw(3, RRL_DRAW_UNIFORM, 0)};
+                const rrl_sample_args_t args[2] = {{&d[0], &d[1], pairs, 99, 0, ntick, 1, o[36]->d},
+                                                   {&d[2], &d[3], pairs, 98, 0, ntick + 2, 1, o[37]->d}};
+                for (int pass = 0; pass < 2; ++pass) {
+                    if (pass == 0) {
+                        rc |= libs[k].sample(&d[0], &d[1], pairs, 99, 0, ntick, 1, o[36]->d, st);
+                        rc |= libs[k].sample(&d[2], &d[3], pairs, 98, 0, ntick + 2, 1, o[37]->d, st);
+                    } else {
+                        rc |= libs[k].sample_packed(2, args, st);
+                    }
+                    HIP(hipStreamSynchronize(st));
+                    for (auto* b : o) got.push_back(b->host());
+                    got.push_back(words.host());
+                }
+            }
+            if (rc) printf("  %s: rc %d\n", libs[k].name.c_str(), rc), ++bad;
+            if (k == 0) {
+                want = got;
+                const std::vector<float> w = words.host();
+                int64_t st4[4];
+                memcpy(st4, w.data(), sizeof st4);
+                size_t nan = 0;
+                for (float e : got[0]) nan += e != e;
+                printf("%s: default library left size %lld, error flag %lld, %zu unwritten floats in the first batch (expected %lld, 0, 0)\n",
+                       what, (long long)st4[1], (long long)st4[3], nan, (long long)rows);
+                bad += st4[1] != rows || st4[3] != 0 || nan != 0;
+            } else {
+                bad += compare(what, libs[k], want, got);
+            }
+        }
+        for (auto* b : o) delete b;
     }
     // ---- timing: back-to-back launches on one stream, HIP events; libraries interleaved, three rounds, best of ----------
     {

@@ -36,8 +36,7 @@ EXPORTS = [
     "rrl_nav_step", "rrl_nav_step_compact", "rrl_nav_reset", "rrl_nav_rollout", "rrl_nav_offline_rollouts",
     "rrl_nav_offline",
     "rrl_maze_step", "rrl_maze_reset", "rrl_maze_offline",
-    "rrl_replay_push", "rrl_replay_sample_gather", "rrl_creplay_sample_gather", "rrl_replay_sample_gather_split",
-    "rrl_sample_multi", "rrl_draw_select", "rrl_mlp3_forward_riders",
+    "rrl_replay_push", "rrl_sample_multi", "rrl_draw_select", "rrl_mlp3_forward_riders",
     "rrl_nav_step_push_x", "rrl_maze_step_push_x",
     "rrl_sample_multi_packed", "rrl_pack_clear", "rrl_mlp3_forward_multi_packed", "rrl_mlp_head_backward_multi_packed",
     "rrl_mlp_hidden_backward_multi_packed", "rrl_mlp_backward_pair_multi_packed", "rrl_adam_step_multi_packed", "rrl_nav_step_push_packed",
@@ -46,8 +45,8 @@ EXPORTS = [
     "rrl_gemm_f32", "rrl_mlp3_forward", "rrl_mlp3_is_split",
     "rrl_mlp3_forward_multi", "rrl_mlp_head_backward_multi", "rrl_mlp_hidden_backward_multi",
     "rrl_mlp_input_backward_multi", "rrl_mlp_backward_pair_multi", "rrl_policy_heads_fwd_multi",
-    "rrl_gauss_head_fwd", "rrl_gauss_head_bwd", "rrl_sac_critic_grad", "rrl_sac_policy_grad",
-    "rrl_qrisk_critic_grad", "rrl_qrisk_policy_grad", "rrl_stoch_head_fwd", "rrl_stoch_head_bwd",
+    "rrl_gauss_head_bwd", "rrl_sac_critic_grad", "rrl_sac_policy_grad",
+    "rrl_qrisk_critic_grad", "rrl_qrisk_policy_grad", "rrl_stoch_head_bwd",
     "rrl_dgd_qrisk_grad", "rrl_rcpo_penalty", "rrl_adam_step_multi_duals",
     "rrl_adam_step_multi", "rrl_w2_pack", "rrl_normal_fill", "rrl_recovery_select", "rrl_episode_log_append",
     "rrl_plan_supported", "rrl_plan_pack_floats", "rrl_plan_scratch_floats", "rrl_plan_pack", "rrl_plan_cost", "rrl_plan_pack_f16x3",
@@ -283,11 +282,6 @@ def _declare(lib):
         "rrl_maze_reset": (ci, [i64, vp, vp, vp, vp, ci, ci, u64, u64, vp, vp]),
         "rrl_maze_offline": (ci, [i64, u64, vp, vp, vp, vp, vp, i64, vp]),
         "rrl_replay_push": (ci, [rp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "rrl_replay_sample_gather": (ci, [rp, i32, u64, u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "rrl_creplay_sample_gather": (ci, [rp, i32, i32, u64, u64, vp, u64, vp, vp, vp, vp, vp,
-                                           vp, vp, vp, vp, vp]),
-        "rrl_replay_sample_gather_split": (ci, [rp, i32, i32, u64, u64, vp, u64, vp, vp, vp, vp, vp,
-                                                vp, vp, vp, vp, vp]),
         "rrl_sample_multi": (ci, [C.POINTER(rrl_draw_t), C.POINTER(rrl_draw_t), ll, u64, u64, vp, u64, vp, vp]),
         "rrl_mlp3_forward_multi": (ci, [ci, C.POINTER(rrl_stack_t), vp]),
         "rrl_draw_select": (ci, [C.POINTER(rrl_draw_ahead_t), vp]),
@@ -321,7 +315,6 @@ def _declare(lib):
                               ci, vp]),
         "rrl_mlp3_forward": (ci, [ci, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]),
         "rrl_mlp3_is_split": (ci, [ci, ci]),
-        "rrl_gauss_head_fwd": (ci, [ci, vp, ci, ll, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp]),
         "rrl_gauss_head_bwd": (ci, [ci, vp, ci, ll, vp, vp, vp, ci, ci, ll, f32, vp, vp]),
         "rrl_sac_critic_grad": (ci, [ci, vp, vp, ci, ll, vp, vp, vp, f32, vp, vp, vp, vp, vp]),
         "rrl_sac_policy_grad": (ci, [ci, vp, ci, ll, vp, vp, vp, vp, vp]),
@@ -330,7 +323,6 @@ def _declare(lib):
         "rrl_dgd_qrisk_grad": (ci, [ci, vp, ci, ll, f32, vp, vp, vp]),
         "rrl_rcpo_penalty": (ci, [ci, vp, ci, ll, vp, vp, vp, vp]),
         "rrl_adam_step_multi_duals": (ci, [ci, C.POINTER(rrl_adam_seg_t), ci, C.POINTER(rrl_dual_t), f32, f32, f32, f32, vp]),
-        "rrl_stoch_head_fwd": (ci, [ci, vp, ci, ll, vp, vp, f32, vp, vp, vp, ci, vp, vp]),
         "rrl_stoch_head_bwd": (ci, [ci, vp, ci, ll, vp, vp, f32, vp, vp, ci, ci, ll, vp, vp, vp]),
         "rrl_adam_step_multi": (ci, [ci, C.POINTER(rrl_adam_seg_t), f32, f32, f32, f32, vp]),
         "rrl_w2_pack": (ci, [ci, ci, vp, vp, vp]),

@@ -22,8 +22,8 @@ struct StackArgs {
     float* h1; float* h2;               // [G,M,H] or null
     float* out;                          // [G,M,dout]
     int M, H, din, dout, ldx;
-    // optional: columns 2..3 of x are not read but computed -- the action a policy head (rrl_gauss_head_fwd /
-    // rrl_stoch_head_fwd) yields for the same row -- so the head needs no launch of its own between the policy stack and
+    // optional: columns 2..3 of x are not read but computed -- the action a policy head (rrl_policy_head_t, either
+    // kind) yields for the same row -- so the head needs no launch of its own between the policy stack and
     // the critic stack that consumes its action (sac.py:192-218, qrisk.py:119-152, experiment.py:546-577)
     rrl_policy_head_t in_head;
     int use_in_head;

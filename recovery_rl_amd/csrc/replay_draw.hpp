@@ -1,5 +1,5 @@
 // replay_draw.hpp -- the replay draws' device code (index selection, gather, the per-mode bodies and the noise fill) and
-// their launch parameters, shared by the stand-alone / grouped draw launches (replay_kernels.hip) and by the forward
+// their launch parameters, shared by the draw launches (replay_kernels.hip) and by the forward
 // launch that takes the draws along as rider workgroups (mlp_fwd_kernels.hip).
 #pragma once
 
@@ -109,8 +109,8 @@ __device__ __forceinline__ void gather_row(const rrl_replay_t& rb, int64_t slot,
 }
 
 // The uniform draw in two halves.  SELECT: B distinct keys for a ring of `size` rows at tick `ctr`, left in LDS (`key`);
-// 0, or the error code the stand-alone draw flags in rb.state[3] (1: B > size, 2: round cap).  GATHER: the rows of the keys.
-// The stand-alone draw runs both in one workgroup; the draw-ahead form (rrl_draw_ahead_t) runs the select half one env step
+// 0, or the error code the whole draw flags in rb.state[3] (1: B > size, 2: round cap).  GATHER: the rows of the keys.
+// The whole draw (mode 1) runs both in one workgroup; the draw-ahead form (rrl_draw_ahead_t) runs the select half one env step
 // early -- `size` is then the size AFTER that step's rows, min(cap, size now + rows_ahead) -- and the gather half after it.
 __device__ __forceinline__ int select_keys(int B, int64_t size, uint64_t seed, uint64_t ctr, uint32_t* key,
                                            unsigned long long* table, int table_mask) {
@@ -140,7 +140,7 @@ __device__ __forceinline__ void sample_gather_body(const rrl_replay_t& rb, int B
 
 // Keys selected ahead live in a device buffer of B + RRL_AHEAD_META words: the keys, then the tick and the ring size they were
 // drawn for (two words each) and the select half's error code.  The select half changes nothing else: the tick advances and
-// the error flag is raised where the stand-alone draw would do it, by the gather half one step later -- between the two
+// the error flag is raised where the whole draw would do it, by the gather half one step later -- between the two
 // every observable word (tick, rb.state) reads as in a run without draw-ahead.
 constexpr int kAheadMeta = RRL_AHEAD_META;
 
@@ -385,10 +385,10 @@ __device__ __forceinline__ void split_sample_gather_body(const rrl_replay_t& rb,
 
 // The two draws of one lock-step iteration (task buffer for the SAC update, safety buffer for the Q_risk update:
 // experiment.py:397-416) and the iteration's policy noise do not depend on each other: one launch, workgroup 0 and 1
-// are the samplers (exactly the stand-alone kernels' code), the remaining workgroups fill the noise buffer.
+// are the samplers (one draw_body each; an absent member has mode 0), the remaining workgroups fill the noise buffer.
 struct DrawArgs {
     rrl_replay_t rb;
-    int mode;            // 0: none, 1: uniform (sample_gather), 2: stratified (creplay_sample_gather), 3: demo share (split_sample_gather)
+    int mode;            // 0: none, 1: RRL_DRAW_UNIFORM, 2: RRL_DRAW_STRATIFIED, 3: RRL_DRAW_DEMO_SHARE (n_pos demo, n_neg online rows)
     int B, n_pos, n_neg, n_chunks, table_mask;
     uint64_t seed, counter;
     uint64_t* counter_dev;
@@ -439,7 +439,7 @@ inline bool valid_rb(const rrl_replay_t* rb) {
     return rb && rb->s && rb->a && rb->r && rb->s2 && rb->m && rb->state && rb->cap > 0;
 }
 
-// launch parameters of one draw (threads, dynamic LDS) shared by the stand-alone and the grouped entry points
+// one draw's checks and launch parameters (threads, dynamic LDS): rrl_draw_t's contract (include/rrl_hip.h) in code
 inline int draw_setup(const rrl_draw_t& d, DrawArgs& a, int& threads, size_t& lds) {
     const rrl_replay_t* rb = d.rb;
     if (!valid_rb(rb) || !d.s || !d.a || !d.r || !d.s2 || !d.m) return RRL_EINVAL;

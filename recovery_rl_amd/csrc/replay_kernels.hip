@@ -118,34 +118,6 @@ __global__ __launch_bounds__(kBlock) void push_masked_kernel(rrl_replay_t rb, in
     advance_ring(rb, pos, size, total);
 }
 
-__global__ __launch_bounds__(1024) void sample_gather_kernel(rrl_replay_t rb, int B, uint64_t seed,
-                                                             uint64_t counter,
-                                                             uint64_t* counter_dev,
-                                                             uint64_t counter_inc, int table_mask,
-                                                             BatchOut out) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    sample_gather_body(rb, B, seed, counter, counter_dev, counter_inc, table_mask, out, smem);
-}
-
-__global__ __launch_bounds__(1024) void creplay_sample_gather_kernel(rrl_replay_t rb, int n_pos,
-                                                                     int n_neg, int n_chunks,
-                                                                     uint64_t seed, uint64_t counter,
-                                                                     uint64_t* counter_dev,
-                                                                     uint64_t counter_inc, int table_mask,
-                                                                     BatchOut out) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    creplay_sample_gather_body(rb, n_pos, n_neg, n_chunks, seed, counter, counter_dev, counter_inc, table_mask, out,
-                               smem);
-}
-
-__global__ __launch_bounds__(1024) void split_sample_gather_kernel(rrl_replay_t rb, int n_demo, int n_online,
-                                                                   uint64_t seed, uint64_t counter,
-                                                                   uint64_t* counter_dev, uint64_t counter_inc,
-                                                                   int table_mask, BatchOut out) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    split_sample_gather_body(rb, n_demo, n_online, seed, counter, counter_dev, counter_inc, table_mask, out, smem);
-}
-
 // the select half on its own (rrl_draw_select): the keys a draw would use `rows_ahead` pushed rows from now
 __global__ __launch_bounds__(1024) void select_ahead_kernel(rrl_replay_t rb, int B, uint64_t seed, uint64_t counter,
                                                             const uint64_t* counter_dev, int table_mask, int64_t rows_ahead,
@@ -183,6 +155,7 @@ __global__ __launch_bounds__(1024) void sample_pack_kernel(const SamplePack* __r
 
 }  // namespace
 
+// gfx950 has 160 KiB of LDS per CU; opt in (once per size) above the 64 KiB default
 template <class K>
 static bool grant_sample_lds(K kernel, size_t lds, size_t& granted) {
     if (lds > granted) {
@@ -329,68 +302,6 @@ int rrl_sample_multi_packed(int S, const rrl_sample_args_t* args, void* stream) 
     }
     hipLaunchKernelGGL(sample_pack_kernel, dim3(plan->grid), dim3(plan->i0), plan->z0, st,
                        (const SamplePack*)plan->dev, plan->ix);
-    return check_launch();
-}
-
-int rrl_replay_sample_gather(const rrl_replay_t* rb, int32_t B, uint64_t seed, uint64_t counter,
-                             uint64_t* counter_dev, uint64_t counter_inc, float* s, float* a, float* r, float* s2,
-                             float* m, int64_t* idx_out, float* xu, float* x2u, float* xpu, void* stream) {
-    if (!valid_rb(rb) || !s || !a || !r || !s2 || !m) return RRL_EINVAL;
-    if (B <= 0 || B > 1024 || rb->cap >= (int64_t(1) << 31)) return RRL_ERANGE;
-    const BatchOut out{(float2*)s, (float2*)a, r, (float2*)s2, m, idx_out, (float4*)xu, (float4*)x2u, (float4*)xpu};
-    const int threads = ((B + 63) / 64) * 64;
-    int table_size = 64;
-    while (table_size < 4 * B) table_size <<= 1;
-    const size_t lds = size_t(table_size) * 8 + size_t(B) * 4 + 16;
-    hipLaunchKernelGGL(sample_gather_kernel, dim3(1), dim3(threads), lds, (hipStream_t)stream, *rb,
-                       B, seed, counter, counter_dev, counter_inc, table_size - 1, out);
-    return check_launch();
-}
-
-int rrl_replay_sample_gather_split(const rrl_replay_t* rb, int32_t n_demo, int32_t n_online, uint64_t seed,
-                                   uint64_t counter, uint64_t* counter_dev, uint64_t counter_inc, float* s, float* a,
-                                   float* r, float* s2, float* m, int64_t* idx_out, float* xu, float* x2u, float* xpu,
-                                   void* stream) {
-    if (!valid_rb(rb) || !s || !a || !r || !s2 || !m) return RRL_EINVAL;
-    const int B = n_demo + n_online;
-    if (n_demo < 0 || n_online < 0 || B <= 0 || B > 1024 || rb->cap >= (int64_t(1) << 31)) return RRL_ERANGE;
-    if (rb->pinned < 0 || rb->pinned >= rb->cap) return RRL_ERANGE;
-    const BatchOut out{(float2*)s, (float2*)a, r, (float2*)s2, m, idx_out, (float4*)xu, (float4*)x2u, (float4*)xpu};
-    const int threads = ((B + 63) / 64) * 64;
-    int table_size = 64;
-    while (table_size < 4 * B) table_size <<= 1;
-    const size_t lds = size_t(table_size) * 8 + size_t(B) * 4 + 16;
-    hipLaunchKernelGGL(split_sample_gather_kernel, dim3(1), dim3(threads), lds, (hipStream_t)stream, *rb, n_demo,
-                       n_online, seed, counter, counter_dev, counter_inc, table_size - 1, out);
-    return check_launch();
-}
-
-int rrl_creplay_sample_gather(const rrl_replay_t* rb, int32_t n_pos, int32_t n_neg, uint64_t seed,
-                              uint64_t counter, uint64_t* counter_dev, uint64_t counter_inc, float* s, float* a,
-                              float* r, float* s2, float* m, int64_t* idx_out, float* xu, float* x2u, float* xpu,
-                              void* stream) {
-    if (!valid_rb(rb) || !rb->pos_cnt || !s || !a || !r || !s2 || !m) return RRL_EINVAL;
-    const int B = n_pos + n_neg;
-    if (n_pos < 0 || n_neg < 0 || B <= 0 || B > 1024) return RRL_ERANGE;
-    if (rb->cap > (int64_t(1) << 21)) return RRL_ERANGE;
-    const int n_chunks = int((rb->cap + kChunk - 1) / kChunk);
-    const int threads = ((B + 63) / 64) * 64;
-    int table_size = 64;
-    while (table_size < 4 * B) table_size <<= 1;
-    const size_t lds = size_t(table_size) * 8 + size_t((B + 3) & ~3) * 4 + size_t(rrl_replay::count_supers(rb->cap) + 2) * 4 + 16;
-    static size_t granted = 64 * 1024;   // gfx950 has 160 KiB of LDS per CU; opt in (once per size) above the default
-    if (lds > granted) {
-        if (hipFuncSetAttribute((const void*)creplay_sample_gather_kernel,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)) != hipSuccess) {
-            (void)hipGetLastError();
-            return RRL_ERANGE;
-        }
-        granted = lds;
-    }
-    const BatchOut out{(float2*)s, (float2*)a, r, (float2*)s2, m, idx_out, (float4*)xu, (float4*)x2u, (float4*)xpu};
-    hipLaunchKernelGGL(creplay_sample_gather_kernel, dim3(1), dim3(threads), lds,
-                       (hipStream_t)stream, *rb, n_pos, n_neg, n_chunks, seed, counter, counter_dev,
-                       counter_inc, table_size - 1, out);
     return check_launch();
 }
 

@@ -63,7 +63,7 @@ struct StepPushArgs {
     long long sel_ps;
     float sel_eps;
     const float2* sel_rec_action;   // the recovery action, or (null) computed here from the recovery policy's head:
-    rrl_policy_head_t sel_rec_head; // rrl_stoch_head_fwd evaluated per env (same formulas, same bits)
+    rrl_policy_head_t sel_rec_head; // the RRL_HEAD_STOCH head evaluated per env (same formulas, same bits)
     float2* sel_real_out;     // the executed action and the flag are written for the consumers downstream
     uint8_t* sel_recovery_out;
     float reward_penalty;

@@ -63,14 +63,6 @@ __device__ __forceinline__ void gauss_head_fwd_row(int b, const float* head, int
     if (logp) logp[b] = lp;
 }
 
-__global__ void gauss_head_fwd_kernel(int B, const float* head, int np, long long ps, const float* eps,
-                                      const float* scale, const float* bias, float* action, int ld_action,
-                                      float* logp, float* mean_action, const float* obs_in, float* obs_out) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    gauss_head_fwd_row(b, head, np, ps, eps, scale, bias, action, ld_action, logp, mean_action, obs_in, obs_out);
-}
-
 // backward of the head: given dL/d action[b,j] (d_action, leading dim ld) and dL/d logp[b] = dlogp
 // (a constant, alpha / B) produce dL/d head[b, 0..3]
 __global__ void gauss_head_bwd_kernel(int B, const float* head, int np, long long ps, const float* eps,
@@ -235,15 +227,6 @@ __device__ __forceinline__ void stoch_head_fwd_row(int b, const float* raw, int 
         action[(long long)b * ld_action + j] = mean + std * e;
         if (mean_out) mean_out[2 * b + j] = mean;
     }
-}
-
-__global__ void stoch_head_fwd_kernel(int B, const float* raw, int np, long long ps, const float* eps,
-                                      const float* log_std,
-                                      float min_log_std, const float* scale, const float* bias,
-                                      float* action, int ld_action, float* mean_out) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    stoch_head_fwd_row(b, raw, np, ps, eps, log_std, min_log_std, scale, bias, action, ld_action, mean_out);
 }
 
 // independent policy heads in one launch (e.g. a' = pi(s') and pi(s) of one SAC step; the task action and the
@@ -645,16 +628,6 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 extern "C" {
 
-int rrl_gauss_head_fwd(int B, const float* head, int n_part, long long part_stride, const float* eps,
-                       const float* scale, const float* bias, float* action, int ld_action, float* logp,
-                       float* mean_action, const float* obs_in, float* obs_out, void* stream) {
-    if (!head || !eps || !scale || !bias || !action || B <= 0 || n_part <= 0 || (obs_in && !obs_out))
-        return RRL_EINVAL;
-    hipLaunchKernelGGL(gauss_head_fwd_kernel, rows_grid(B), dim3(kBlock), 0, (hipStream_t)stream, B, head, n_part,
-                       part_stride, eps, scale, bias, action, ld_action, logp, mean_action, obs_in, obs_out);
-    return check_launch();
-}
-
 int rrl_policy_heads_fwd_multi(int n, const rrl_policy_head_t* heads, void* stream) {
     if (!heads || n <= 0 || n > kMaxHeads) return RRL_EINVAL;
     HeadGroup hg{};
@@ -733,15 +706,6 @@ int rrl_rcpo_penalty(int B, const float* z, int n_part, long long part_stride, c
     if (!z || (penalty && !lambda) || (!penalty && !mean) || B <= 0 || n_part <= 0 || n_part > 4) return RRL_EINVAL;
     hipLaunchKernelGGL(rcpo_penalty_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, B, z, n_part, part_stride,
                        lambda, penalty, mean);
-    return check_launch();
-}
-
-int rrl_stoch_head_fwd(int B, const float* raw, int n_part, long long part_stride, const float* eps,
-                       const float* log_std, float min_log_std, const float* scale, const float* bias,
-                       float* action, int ld_action, float* mean_out, void* stream) {
-    if (!raw || !log_std || !scale || !bias || !action || B <= 0 || n_part <= 0 || n_part > 4) return RRL_EINVAL;
-    hipLaunchKernelGGL(stoch_head_fwd_kernel, rows_grid(B), dim3(kBlock), 0, (hipStream_t)stream, B, raw, n_part,
-                       part_stride, eps, log_std, min_log_std, scale, bias, action, ld_action, mean_out);
     return check_launch();
 }
 

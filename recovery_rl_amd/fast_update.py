@@ -379,24 +379,11 @@ def backward_multi(triples):
 
 
 def heads_multi(heads):
+    """Independent policy heads (rrl_policy_head_t) in one launch; a lone head is a list of one."""
     arr = (_lib.rrl_policy_head_t * len(heads))(*heads)
     record("unsupported", "rrl_policy_heads_fwd_multi")
     _lib.check(_lib.load().rrl_policy_heads_fwd_multi(len(heads), arr, _lib.current_stream()),
                "rrl_policy_heads_fwd_multi")
-
-
-# -- the stand-alone launch of a descriptor: the same operands field for field, the same bits (include/rrl_hip.h) -----
-def head_forward(hd):
-    """One rrl_policy_head_t as a launch of its own (rrl_gauss_head_fwd / rrl_stoch_head_fwd)."""
-    lib, st = _lib.load(), _lib.current_stream()
-    if hd.kind == _lib.HEAD_GAUSS:
-        _lib.check(lib.rrl_gauss_head_fwd(hd.B, hd.head, hd.n_part, hd.part_stride, hd.eps, hd.scale, hd.bias, hd.action,
-                                          hd.ld_action, hd.logp, hd.mean_out, hd.obs_in, hd.obs_out, st),
-                   "rrl_gauss_head_fwd")
-    else:
-        _lib.check(lib.rrl_stoch_head_fwd(hd.B, hd.head, hd.n_part, hd.part_stride, hd.eps, hd.log_std, hd.min_log_std,
-                                          hd.scale, hd.bias, hd.action, hd.ld_action, hd.mean_out, st),
-                   "rrl_stoch_head_fwd")
 
 
 def loss_dout(loss, B, dout):
@@ -797,7 +784,7 @@ class FastUpdater:
         return self.losses
 
     # -- the sets of independent launches an update is made of: ONE rrl_*_multi launch each (grouped), or member by member
-    #    (forwards and policy heads through their stand-alone entry points, backwards as launches of one descriptor) -- the
+    #    (forwards through their stand-alone entry point, policy heads and backwards as launches of one descriptor) -- the
     #    same kernel bodies on the same inputs, the same bits either way ---------------------------------------------------
     def _forwards(self, members, grouped, riders=()):
         """Independent stack forwards: members = [(stack, x, options of Stack.forward_desc)]; `riders`: rrl_stack_t of
@@ -826,7 +813,7 @@ class FastUpdater:
             heads_multi(live)
         else:
             for hd in live:
-                head_forward(hd)
+                heads_multi([hd])
         return [None] * len(heads)
 
     def _backwards(self, members, grouped):
@@ -1043,7 +1030,7 @@ class FastActor:
             noise = f.actor_noise(n)
         if not use_recovery:
             self.pol.forward(obs, save=False)
-            head_forward(f._gauss_desc(self.pol.parts, noise[0], self.task_action, None, n=n))
+            heads_multi([f._gauss_desc(self.pol.parts, noise[0], self.task_action, None, n=n)])
             return self.task_action, self.task_action, None
         assert mf_recovery, "FastActor covers the model-free recovery policy"
         grouped = f.grouped
@@ -1061,7 +1048,7 @@ class FastActor:
         if grouped:
             heads_multi([task_head, rec_head])
         else:
-            head_forward(task_head), head_forward(rec_head)
+            heads_multi([task_head]), heads_multi([rec_head])
         if defer_select:
             self.qr.finalize = False            # the step kernel adds the partial last-layer sums itself
             self.qr.forward(self.xa, save=False)
@@ -1075,7 +1062,7 @@ class FastActor:
             noise = self.f.actor_noise(self.n)
         self.pending_select = None
         self.pol.forward(obs, save=False)
-        head_forward(self._task_head(noise[0], obs))
+        heads_multi([self._task_head(noise[0], obs)])
         # the kernel's action selection runs on a dummy recovery action: the planner's action is merged in by the caller
         task, _, recovery = self._gate(eps_safe)
         return task, recovery

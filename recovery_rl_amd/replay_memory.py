@@ -1,5 +1,5 @@
 """Device-resident replay buffers: host-side mirror of recovery_rl/replay_memory.py over
-rrl_replay_push / rrl_replay_sample_gather / rrl_creplay_sample_gather.
+rrl_replay_push / rrl_sample_multi (rrl_draw_t: uniform, stratified and demonstration-share draws).
 
 Same names and call shapes as the reference (`push`, `sample`, `__len__`), batched:
 `push` takes N rows per call (one row per env) and `sample` returns five CUDA tensors
@@ -19,7 +19,7 @@ class DrawAhead:
     situation -- the tick they were drawn at, the ring after exactly that step -- so they are usable only when that one step
     (`stepped`) and nothing else happened to the ring since `selected`; everything else that touches the ring or its tick
     (push, sample, a draw, a checkpoint load: `drop`) discards them, which costs nothing: selecting advances no tick and
-    raises no flag, the next draw is simply the stand-alone launch.  No device state: exercised on the CPU."""
+    raises no flag, the next draw is simply a whole draw.  No device state: exercised on the CPU."""
 
     def __init__(self):
         self.pending = None               # [B, rows, stepped]
@@ -174,32 +174,26 @@ class ReplayMemory:
         """B distinct uniform rows (random.sample semantics, replay_memory.py:27-30).
         Returns persistent batch tensors (overwritten by the next sample of the same size).
         `rows` = (xu, x2u, xpu) [B,4] buffers that additionally receive (s,a), (s',-,-), (s,-,-)."""
+        return self._draw(*self.draw_desc(batch_size, out=out, rows=rows))
+
+    def _draw(self, d, batch):
+        """One rrl_draw_t as a launch of its own: rrl_sample_multi with no second draw and no noise."""
+        _lib.check(self.lib.rrl_sample_multi(C.byref(d), None, 0, 0, 0, None, 0, None, _lib.current_stream()),
+                   "rrl_sample_multi")
+        return batch
+
+    def draw_desc(self, batch_size, pos_fraction=None, out=None, rows=None, demo_share=None, ahead=0):
+        """The arguments of sample() as an rrl_draw_t for rrl_sample_multi and the batch tensors it fills, after the
+        host-side checks: sample() launches it alone, update_pair two of them with the policy noise.  `ahead`: the draw's
+        select half runs now, for the ring as it will be `ahead` pushed rows from now (select_ahead); its population check
+        is the gather half's."""
         B = int(batch_size)
         self.ahead.drop()
-        if self._len_exact and B > self._len:
+        if pos_fraction is None and self._len_exact and B > min(self._len + ahead, self.capacity):
             raise ValueError("Sample larger than population or is negative")
         s, a, r, s2, m, idx = out if out is not None else self._batch(B)
         xu, x2u, xpu = rows if rows is not None else (None, None, None)
-        rc = self.lib.rrl_replay_sample_gather(C.byref(self._desc), B, self.seed, 0,
-                                               _lib.ptr(self.tick), 1, _lib.ptr(s), _lib.ptr(a),
-                                               _lib.ptr(r), _lib.ptr(s2), _lib.ptr(m), _lib.ptr(idx),
-                                               _lib.ptr(xu), _lib.ptr(x2u), _lib.ptr(xpu),
-                                               _lib.current_stream())
-        _lib.check(rc, "rrl_replay_sample_gather")
-        return s, a, r, s2, m
-
-
-    def draw_desc(self, batch_size, pos_fraction=None, out=None, rows=None, demo_share=None, ahead=0):
-        """The arguments of sample() as an rrl_draw_t for rrl_sample_multi (several draws in one launch) and the batch
-        tensors it fills.  Same checks, same tick, same rows as sample().  `ahead`: the draw's select half runs now, for
-        the ring as it will be `ahead` pushed rows from now (select_ahead); its population check is the gather half's."""
-        B = int(batch_size)
-        self.ahead.drop()
-        s, a, r, s2, m, idx = out if out is not None else self._batch(B)
-        xu, x2u, xpu = rows if rows is not None else (None, None, None)
         if pos_fraction is None:
-            if self._len_exact and B > min(self._len + ahead, self.capacity):
-                raise ValueError("Sample larger than population or is negative")
             if demo_share:
                 stratified, n_pos = _lib.DRAW_DEMO_SHARE, int(B * demo_share)
                 n_neg = B - n_pos
@@ -242,36 +236,6 @@ class ConstraintReplayMemory(ReplayMemory):
 
     def sample(self, batch_size, pos_fraction=None, out=None, rows=None, demo_share=None):
         """`demo_share` (lock-step loop only, ignored with pos_fraction): int(B * demo_share) rows from the pinned
-        demonstrations, the rest from the online rows (rrl_replay_sample_gather_split)."""
-        if pos_fraction is None and demo_share:
-            return self._sample_split(batch_size, demo_share, out, rows)
-        if pos_fraction is None:
-            return super().sample(batch_size, out=out, rows=rows)
-        B = int(batch_size)
-        self.ahead.drop()
-        n_pos = int(B * pos_fraction)          # replay_memory.py:56-57
-        n_neg = B - n_pos
-        s, a, r, s2, m, idx = out if out is not None else self._batch(B)
-        xu, x2u, xpu = rows if rows is not None else (None, None, None)
-        rc = self.lib.rrl_creplay_sample_gather(C.byref(self._desc), n_pos, n_neg, self.seed, 0,
-                                                _lib.ptr(self.tick), 1, _lib.ptr(s), _lib.ptr(a),
-                                                _lib.ptr(r), _lib.ptr(s2), _lib.ptr(m),
-                                                _lib.ptr(idx), _lib.ptr(xu), _lib.ptr(x2u), _lib.ptr(xpu),
-                                                _lib.current_stream())
-        _lib.check(rc, "rrl_creplay_sample_gather")
-        return s, a, r, s2, m
-
-    def _sample_split(self, batch_size, demo_share, out, rows):
-        B = int(batch_size)
-        self.ahead.drop()
-        if self._len_exact and B > self._len:
-            raise ValueError("Sample larger than population or is negative")
-        n_demo = int(B * demo_share)
-        s, a, r, s2, m, idx = out if out is not None else self._batch(B)
-        xu, x2u, xpu = rows if rows is not None else (None, None, None)
-        rc = self.lib.rrl_replay_sample_gather_split(C.byref(self._desc), n_demo, B - n_demo, self.seed, 0,
-                                                     _lib.ptr(self.tick), 1, _lib.ptr(s), _lib.ptr(a), _lib.ptr(r),
-                                                     _lib.ptr(s2), _lib.ptr(m), _lib.ptr(idx), _lib.ptr(xu),
-                                                     _lib.ptr(x2u), _lib.ptr(xpu), _lib.current_stream())
-        _lib.check(rc, "rrl_replay_sample_gather_split")
-        return s, a, r, s2, m
+        demonstrations, the rest from the online rows (RRL_DRAW_DEMO_SHARE).  With pos_fraction: int(B * pos_fraction)
+        rows with r != 0, the rest with r == 0 (replay_memory.py:56-57), no host-side population check."""
+        return self._draw(*self.draw_desc(batch_size, pos_fraction=pos_fraction, out=out, rows=rows, demo_share=demo_share))

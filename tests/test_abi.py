@@ -329,6 +329,134 @@ def test_backward_and_adam_descriptor_validation_without_gpu():
     assert lib.rrl_adam_step_multi(1, None, 3e-4, 0.9, 0.999, 1e-8, None) == EINVAL
 
 
+def _draw(ring=None, **fields):
+    """A well-formed uniform rrl_draw_t of 64 rows on a 4096-row ring; device pointers are dummy non-null integers.  `ring`:
+    fields of the rrl_replay_t on top (the ring is a host struct and real)."""
+    d = 0x1000
+    rb = _with(_lib.rrl_replay_t(s=d, a=d, r=d, s2=d, m=d, cap=4096, state=d, pos_cnt=d), **(ring or {}))
+    draw = _lib.rrl_draw_t(ctypes.pointer(rb), _lib.DRAW_UNIFORM, 0, 64, 1, 0, d, 1, d, d, d, d, d, d, None, None, None)
+    return _with(draw, **fields)
+
+
+def _head(kind=_lib.HEAD_GAUSS, **fields):
+    d = 0x1000
+    h = _lib.rrl_policy_head_t(kind=kind, B=8, head=d, n_part=1, eps=d, scale=d, bias=d, action=d, ld_action=2, log_std=d)
+    return _with(h, **fields)
+
+
+def test_draw_and_policy_head_descriptor_validation_without_gpu():
+    """What rrl_sample_multi, rrl_draw_select and rrl_policy_heads_fwd_multi (and rrl_sample_multi_packed with one seed,
+    which forwards) answer to a malformed rrl_draw_t / rrl_policy_head_t: every call returns before any launch.  The codes
+    are those of ABI version 6, recorded from that library (where the positional forms still stood beside these).  Order
+    for a draw: the noise arguments of the launch, then per draw the ring and the outputs, the batch size, the mode's own
+    bounds.  No case is well formed, so nothing here can reach a launch on a machine with a GPU: the valid capacity bound
+    of the stratified mode is shown by a second draw that is refused for another reason with another code."""
+    lib = _lib.load()
+    EINVAL, ERANGE = -1, -3
+    U, ST, DEMO = _lib.DRAW_UNIFORM, _lib.DRAW_STRATIFIED, _lib.DRAW_DEMO_SHARE
+    d = 0x1000
+    draws = [
+        ("ring missing", _draw(rb=None), EINVAL),
+        ("ring without state", _draw(ring=dict(state=None)), EINVAL),
+        ("ring without rewards", _draw(ring=dict(r=None)), EINVAL),
+        ("ring with cap 0", _draw(ring=dict(cap=0)), EINVAL),
+        ("output s2 missing", _draw(s2=None), EINVAL),
+        ("output m missing", _draw(m=None), EINVAL),
+        ("n_pos < 0", _draw(n_pos=-1, n_neg=65), ERANGE),
+        ("n_neg < 0", _draw(n_pos=65, n_neg=-1), ERANGE),
+        ("B == 0", _draw(n_neg=0), ERANGE),
+        ("B == 1025", _draw(n_pos=1, n_neg=1024), ERANGE),
+        ("uniform, cap 2^31", _draw(ring=dict(cap=1 << 31)), ERANGE),
+        ("demo share, cap 2^31", _draw(stratified=DEMO, ring=dict(cap=1 << 31)), ERANGE),
+        ("demo share, pinned == cap", _draw(stratified=DEMO, ring=dict(pinned=4096)), ERANGE),
+        ("demo share, pinned < 0", _draw(stratified=DEMO, ring=dict(pinned=-1)), ERANGE),
+        ("stratified == 3", _draw(stratified=3), EINVAL),
+        ("stratified == -1", _draw(stratified=-1), EINVAL),
+        ("stratified without pos_cnt", _draw(stratified=ST, ring=dict(pos_cnt=None)), EINVAL),
+        ("stratified, cap 2^21 + 1", _draw(stratified=ST, ring=dict(cap=(1 << 21) + 1)), ERANGE),
+        # several things wrong: pointers before the batch size, the batch size before the mode
+        ("output missing and B == 0", _draw(s=None, n_neg=0), EINVAL),
+        ("stratified without pos_cnt and B == 1025", _draw(stratified=ST, ring=dict(pos_cnt=None), n_neg=1025), ERANGE),
+        ("stratified == 3 and B == 0", _draw(stratified=3, n_neg=0), ERANGE),
+        ("stratified without pos_cnt and cap 2^21 + 1", _draw(stratified=ST, ring=dict(pos_cnt=None, cap=(1 << 21) + 1)), EINVAL),
+    ]
+    noise = (0, 0, 0, None, 0, None)                 # noise_pairs, seed, counter, counter_dev, counter_inc, out
+    keys = ctypes.c_void_p(d)
+
+    def sample(first, second, nz=noise):
+        a, b = (None if x is None else ctypes.byref(x) for x in (first, second))
+        args = _lib.rrl_sample_args_t(None if first is None else ctypes.pointer(first),
+                                      None if second is None else ctypes.pointer(second), *nz)
+        rc = lib.rrl_sample_multi(a, b, *nz, None)
+        assert lib.rrl_sample_multi_packed(1, ctypes.byref(args), None) == rc
+        return rc
+
+    refused = _draw(stratified=3)                   # RRL_EINVAL: behind a first draw that passes, the launch answers this
+    for what, x, want in draws:
+        assert sample(x, None) == want, ("first", what)
+        assert sample(x, refused) == want, ("first before a refused second", what)
+        if want != EINVAL:
+            assert sample(_draw(stratified=ST, ring=dict(cap=1 << 21)), x) == want, ("second", what)
+        sel = _lib.rrl_draw_ahead_t(ctypes.pointer(x), 64, keys)
+        assert lib.rrl_draw_select(ctypes.byref(sel), None) == (want if x.stratified == U else EINVAL), ("select", what)
+    # the valid bounds pass: the second draw's code comes back, not RRL_ERANGE
+    for what, x in [("stratified, cap 2^21", _draw(stratified=ST, ring=dict(cap=1 << 21))),
+                    ("stratified, B == 1024", _draw(stratified=ST, n_pos=512, n_neg=512)),
+                    ("uniform, cap 2^31 - 1", _draw(ring=dict(cap=(1 << 31) - 1))),
+                    ("demo share, pinned == cap - 1", _draw(stratified=DEMO, ring=dict(pinned=4095)))]:
+        assert sample(x, refused) == EINVAL, what
+    # the launch's own arguments are looked at before any draw
+    assert sample(None, None) == EINVAL
+    assert sample(None, _draw()) == EINVAL
+    for first in (_draw(), _draw(n_neg=0)):
+        assert sample(first, None, (-1, 0, 0, None, 0, ctypes.c_void_p(d))) == EINVAL, "noise_pairs < 0"
+        assert sample(first, None, (1 << 32, 0, 0, None, 0, ctypes.c_void_p(d))) == EINVAL, "noise_pairs 2^32"
+        assert sample(first, None, (8, 0, 0, None, 0, None)) == EINVAL, "noise_pairs > 0 without noise_out"
+    # rrl_draw_select: its own fields, then the mode, then the draw
+    good = ctypes.pointer(_draw())
+    assert lib.rrl_draw_select(None, None) == EINVAL
+    assert lib.rrl_draw_select(ctypes.byref(_lib.rrl_draw_ahead_t(None, 64, keys)), None) == EINVAL
+    assert lib.rrl_draw_select(ctypes.byref(_lib.rrl_draw_ahead_t(good, 64, None)), None) == EINVAL
+    assert lib.rrl_draw_select(ctypes.byref(_lib.rrl_draw_ahead_t(good, -1, keys)), None) == EINVAL
+    for mode in (ST, DEMO):
+        sel = _lib.rrl_draw_ahead_t(ctypes.pointer(_draw(stratified=mode)), 64, keys)
+        assert lib.rrl_draw_select(ctypes.byref(sel), None) == EINVAL, "select of a non-uniform draw"
+
+    G, SH = _lib.HEAD_GAUSS, _lib.HEAD_STOCH
+    heads = [
+        ("head missing", _head(head=None)),
+        ("scale missing", _head(scale=None)),
+        ("bias missing", _head(bias=None)),
+        ("action missing", _head(action=None)),
+        ("B == 0", _head(B=0)),
+        ("B < 0", _head(B=-8)),
+        ("n_part 0", _head(n_part=0)),
+        ("n_part 5", _head(n_part=5)),
+        ("Gaussian without eps", _head(eps=None)),
+        ("Gaussian with obs_in but no obs_out", _head(obs_in=d)),
+        ("stochastic: head missing", _head(SH, head=None)),
+        ("stochastic: n_part 5", _head(SH, n_part=5)),
+        ("stochastic without log_std", _head(SH, log_std=None)),
+        ("kind == 2", _head(kind=2)),
+        ("kind == -1", _head(kind=-1)),
+    ]
+    P = _lib.rrl_policy_head_t
+
+    def arr(*members):
+        a = (P * 5)()                # five slots: a count of 5 is refused before any member is read, but stays in bounds
+        for k, x in enumerate(members):
+            a[k] = x
+        return a
+
+    for what, x in heads:
+        assert lib.rrl_policy_heads_fwd_multi(1, arr(x), None) == EINVAL, what
+        assert lib.rrl_policy_heads_fwd_multi(2, arr(_head(), x), None) == EINVAL, ("behind a good member", what)
+        assert lib.rrl_policy_heads_fwd_multi(2, arr(x, _head(SH, eps=None)), None) == EINVAL, ("before a good member", what)
+    for n in (0, 5, -1):             # 1 .. 4 members
+        assert lib.rrl_policy_heads_fwd_multi(n, arr(_head()), None) == EINVAL
+    assert lib.rrl_policy_heads_fwd_multi(1, None, None) == EINVAL
+
+
 def test_product_has_no_cpu_fallback():
     import pytest
     import torch

@@ -360,6 +360,107 @@ def test_grouped_entry_points_match_their_members():
     m1.check_error(), c1.check_error()
 
 
+def test_four_mixed_policy_heads_in_one_launch_equal_four_lone_launches():
+    """rrl_policy_heads_fwd_multi: one launch of four mixed members (both kinds, 1 and 4 partial sums, 1 .. 300 rows: one
+    and two workgroups per member, a last workgroup with one live row) against four launches of one member each, bit for
+    bit, sentinel-filled outputs included (ld_action = 4 leaves columns 0..1 alone without obs_in; optional outputs that
+    are not asked for are not written).  Actions, logp and means also against GaussianPolicy.sample / StochasticPolicy.sample
+    of model.py fed with the summed head outputs (their last linear layers set to the identity), at the tolerance of
+    test_fast_actor_matches_module_path, rtol 1e-4 / atol 1e-5; logp at atol 1e-4: log(scale (1 - y^2) + 1e-6) moves by 1.2e-5
+    per ulp of y at |x| = 3, the largest pre-tanh value drawn here (1 - y^2 = 1e-2), per action dimension, and the two tanh
+    implementations may differ by a few ulp.  Rows with log_std outside [-20, 2] exercise both clamps."""
+    from recovery_rl_amd.fast_update import heads_multi
+    from recovery_rl_amd.model import GaussianPolicy, StochasticPolicy
+    g = torch.Generator(device=DEV).manual_seed(11)
+    u = lambda *s: torch.rand(*s, device=DEV, generator=g) * 2 - 1
+    box = Box(np.array([-2.0, -1.0]), np.array([1.0, 3.0]))          # scale (1.5, 2), bias (-0.5, 1)
+    gauss = GaussianPolicy(4, 2, 4, box).to(DEV)
+    stoch = StochasticPolicy(2, 2, 2, box).to(DEV)
+    eye = torch.eye(4, device=DEV)
+    with torch.no_grad():
+        gauss.trunk = stoch.trunk = lambda x: x
+        gauss.mean_linear.weight.copy_(eye[:2]), gauss.log_std_linear.weight.copy_(eye[2:])
+        stoch.mean.weight.copy_(eye[:2, :2])
+        stoch.log_std.copy_(torch.tensor([-0.7, -16.0]))           # the second one under the floor log 1e-6 = -13.8
+    scale, bias = gauss.action_scale.contiguous(), gauss.action_bias.contiguous()
+    FILL = 12345.0
+
+    def parts(B, width, n_part):
+        """n_part partial sums whose fixed-order sum has |mean| <= 1 and, for the Gaussian head, log_std in [-3, 0] -- so
+        that |mean + std eps| <= 3 with |eps| <= 2 -- but for rows 0..9 (log_std -25) and 10..19 (log_std 5, eps / 10)."""
+        t = u(n_part, B, width) / n_part
+        if width == 4:
+            t[:, :, 2:] = t[:, :, 2:] * 1.5 - 1.5 / n_part
+            t[0, 0:10, 2:] -= 23.5
+            t[0, 10:20, 2:] += 6.5
+        total = t[0].clone()
+        for k in range(1, n_part):
+            total = total + t[k]
+        return t.contiguous(), total
+
+    def eps_for(B):
+        e = (u(B, 2) * 2).contiguous()
+        e[10:20] *= 0.1
+        return e
+
+    p = _lib.ptr
+    cases = []          # (descriptor fields, outputs by name, summed head, eps)
+    for kind, B, n_part, ld, opts in ((_lib.HEAD_GAUSS, 300, 4, 4, ("obs", "logp", "mean_out")), (_lib.HEAD_GAUSS, 1, 1, 2, ()),
+                                      (_lib.HEAD_STOCH, 70, 4, 2, ("eps",)), (_lib.HEAD_STOCH, 257, 1, 2, ("mean_out",))):
+        head, total = parts(B, 4 if kind == _lib.HEAD_GAUSS else 2, n_part)
+        eps = eps_for(B) if kind == _lib.HEAD_GAUSS or "eps" in opts else None
+        obs = u(B, 2).contiguous() if "obs" in opts else None
+        cases.append((kind, B, n_part, ld, opts, head, total, eps, obs))
+
+    def launch(together):
+        outs, descs = [], []
+        for kind, B, n_part, ld, opts, head, total, eps, obs in cases:
+            o = dict(act=torch.full((B, ld), FILL, device=DEV), logp=torch.full((B,), FILL, device=DEV),
+                     mean_out=torch.full((B, 2), FILL, device=DEV))
+            descs.append(_lib.rrl_policy_head_t(
+                kind=kind, B=B, head=p(head), n_part=n_part, part_stride=head[0].numel(), eps=p(eps), scale=p(scale),
+                bias=p(bias), action=p(o["act"][:, ld - 2:]), ld_action=ld, logp=p(o["logp"]) if "logp" in opts else None,
+                mean_out=p(o["mean_out"]) if "mean_out" in opts else None, obs_in=p(obs),
+                obs_out=p(o["act"]) if obs is not None else None, log_std=p(stoch.log_std) if kind == _lib.HEAD_STOCH else None,
+                min_log_std=stoch.min_log_std))
+            outs.append(o)
+        if together:
+            heads_multi(descs)
+        else:
+            for d in descs:
+                heads_multi([d])
+        torch.cuda.synchronize()
+        return outs
+
+    one, four = launch(True), launch(False)
+    for k, (a, b) in enumerate(zip(one, four)):
+        for name in a:
+            assert torch.equal(a[name], b[name]), (k, name)
+    close = lambda x, y, atol=1e-5: torch.allclose(x, y, rtol=1e-4, atol=atol)
+    with torch.no_grad():
+        for o, (kind, B, n_part, ld, opts, head, total, eps, obs) in zip(one, cases):
+            if kind == _lib.HEAD_GAUSS:
+                act, logp, mean = gauss.sample(total, eps)
+            else:
+                act, _, mean = stoch.sample(total, eps if eps is not None else torch.zeros(B, 2, device=DEV))
+            assert close(o["act"][:, ld - 2:], act), (kind, B)
+            if obs is not None:
+                assert torch.equal(o["act"][:, :2], obs)
+            elif ld == 4:
+                assert bool((o["act"][:, :2] == FILL).all())
+            if "logp" in opts:
+                assert close(o["logp"], logp.squeeze(1), atol=1e-4), (kind, B)
+                assert float(o["logp"][:10].min()) > 30 and float(logp.abs().max()) < 60        # the low clamp: 2 x 20
+            else:
+                assert bool((o["logp"] == FILL).all())
+            if "mean_out" in opts:
+                assert close(o["mean_out"], mean), (kind, B)
+            else:
+                assert bool((o["mean_out"] == FILL).all())
+            if kind == _lib.HEAD_STOCH and eps is None:
+                assert torch.equal(o["act"], o["mean_out"])          # no noise: the action is the mean
+
+
 @pytest.mark.parametrize("B", (256,))
 def test_first_layer_backward_inside_the_hidden_launch(B):
     """rrl_first_layer_t: (dW1, db1) as row-tile partials summed by Adam and dx as column-tile partials summed by the

@@ -5,7 +5,9 @@ qrisk_update) and issued either member by member through the stand-alone entry p
 QRiskWrapper.update_parameters run, and the reference of the GPU tests -- or with independent kernels sharing launches
 (grouped = True: update_pair, the captured iteration, the bench).  The expected values were recorded the same way before
 the two statements of each update were merged into one, and the stack backward and the optimiser step then moved from
-their positional entry points to the descriptor ones (ABI 6): the entry-point names below changed, no count did."""
+their positional entry points to the descriptor ones (ABI 6): the entry-point names below changed, no count did.  The same
+holds for the policy heads (ABI 7): a lone head is rrl_policy_heads_fwd_multi with one member, where the positional Gaussian
+and stochastic head entry points stood (2 and 1 + 1 launches became 2 and 2)."""
 from collections import Counter
 
 import numpy as np
@@ -65,9 +67,9 @@ def test_launches_of_the_two_updates_at_hidden_256_batch_256(calls):
         [FWD, FWD, PAIR, ADAM, FWD, PAIR, PAIR, ADAM]
     # member by member: the same work through the stand-alone entry points
     assert Counter(launches(calls, fast.sac_update, batch, e1, e2)) == \
-        {"mlp3_forward": 4, "gauss_head_fwd": 2, PAIR: 3, ADAM: 1}
+        {"mlp3_forward": 4, "policy_heads_fwd_multi": 2, PAIR: 3, ADAM: 1}
     assert Counter(launches(calls, fast.qrisk_update, batch, e1, e2)) == \
-        {"mlp3_forward": 5, "gauss_head_fwd": 1, "stoch_head_fwd": 1, PAIR: 3, ADAM: 2}
+        {"mlp3_forward": 5, "policy_heads_fwd_multi": 2, PAIR: 3, ADAM: 2}
 
 
 # a lone stack backward, first layer as its own launch: with weight gradients / for the input gradient only (the same
@@ -90,9 +92,9 @@ def test_launches_of_the_two_updates_at_hidden_32_batch_64(calls):
     assert Counter(launches(calls, fast.qrisk_update, batch, e1, e2, rows=fast.rows_q, grouped=True)) == total(
         {FWD: 2, "policy_heads_fwd_multi": 1, "mlp3_forward": 1, ADAM: 2}, BWD_W, BWD_X, BWD_W)
     assert Counter(launches(calls, fast.sac_update, batch, e1, e2)) == total(
-        {"mlp3_forward": 4, "gauss_head_fwd": 2, ADAM: 1}, BWD_W, BWD_X, BWD_W)
+        {"mlp3_forward": 4, "policy_heads_fwd_multi": 2, ADAM: 1}, BWD_W, BWD_X, BWD_W)
     assert Counter(launches(calls, fast.qrisk_update, batch, e1, e2)) == total(
-        {"mlp3_forward": 5, "gauss_head_fwd": 1, "stoch_head_fwd": 1, ADAM: 2}, BWD_W, BWD_X, BWD_W)
+        {"mlp3_forward": 5, "policy_heads_fwd_multi": 2, ADAM: 2}, BWD_W, BWD_X, BWD_W)
 
 
 def test_launches_of_the_two_updates_at_hidden_512_batch_256(calls):
@@ -100,6 +102,6 @@ def test_launches_of_the_two_updates_at_hidden_512_batch_256(calls):
     fast, batch, e1, e2 = updater(512, 256)
     assert not fast.grouped and not fast.cri_a.fuse_first
     assert Counter(launches(calls, fast.sac_update, batch, e1, e2)) == total(
-        {"gemm_f32": 3 * 4, "gauss_head_fwd": 2, ADAM: 1}, BWD_W, BWD_X, BWD_W)
+        {"gemm_f32": 3 * 4, "policy_heads_fwd_multi": 2, ADAM: 1}, BWD_W, BWD_X, BWD_W)
     assert Counter(launches(calls, fast.qrisk_update, batch, e1, e2)) == total(
-        {"gemm_f32": 3 * 5, "gauss_head_fwd": 1, "stoch_head_fwd": 1, ADAM: 2}, BWD_W, BWD_X, BWD_W)
+        {"gemm_f32": 3 * 5, "policy_heads_fwd_multi": 2, ADAM: 2}, BWD_W, BWD_X, BWD_W)

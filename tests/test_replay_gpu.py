@@ -288,9 +288,9 @@ def test_pinned_rows_are_never_overwritten(cap, pinned, n):
     (5000, 1200, 2000, 7, 0.3),
 ])
 def test_demo_share_draw_matches_oracle(cap, pinned, online, B, share):
-    """rrl_replay_sample_gather_split (vectorisation rule for the safety critic's batch): indices bit-equal to the C
-    checker's, first n_demo rows from [0, pinned), the rest from [pinned, size); stand-alone entry and as a member of
-    rrl_sample_multi; three consecutive calls (the tick advances)."""
+    """RRL_DRAW_DEMO_SHARE (vectorisation rule for the safety critic's batch): indices bit-equal to the C
+    checker's, first n_demo rows from [0, pinned), the rest from [pinned, size); through sample() and as a descriptor
+    handed to rrl_sample_multi here; three consecutive calls (the tick advances)."""
     import ctypes as C
     from recovery_rl_amd import _lib
     rng = np.random.RandomState(cap + online)
