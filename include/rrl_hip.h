@@ -863,6 +863,16 @@ int rrl_ens_train_epoch_big(const rrl_ens_t* m, int n_seg, const rrl_adam_seg_t*
  *                                          every seed qualifies for the paired form, the two packed launches otherwise)
  *   rrl_adam_step_multi_packed             rrl_adam_step_multi         (lr[s])
  *   rrl_nav_step_push_packed / rrl_maze_step_push_packed    rrl_*_step_push_x (a[s]; one env kind, sizes on one side of 16384)
+ * The launches of the comparison algorithms' iterations (LR, RSPO, RCPO, SAC without a recovery policy) that the list above
+ * does not cover:
+ *   rrl_adam_step_multi_duals_packed       rrl_adam_step_multi_duals   (n_seg[s] may be 0, 1 <= n_dual[s] <= RRL_ADAM_MAX_DUALS;
+ *                                          a kernel of its own: seed s's dual row is its row n_seg[s], as in the solo launch)
+ *   rrl_rcpo_penalty_packed                rrl_rcpo_penalty            (args[s]; one workgroup per seed; seeds may differ in
+ *                                          penalty == NULL, i.e. the mean-only form)
+ *   rrl_policy_heads_fwd_multi_packed      rrl_policy_heads_fwd_multi  (n[s] heads heads[s][0..n[s]), either kind; flat grid
+ *                                          over (seed, member, row block))
+ * Every seed's arguments are checked before anything is stored or launched (the stand-alone entry's codes); S outside
+ * 1 .. 16 or a NULL array: RRL_EINVAL.  S == 1 is the stand-alone launch.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
     const rrl_draw_t *first, *second;
@@ -885,6 +895,21 @@ int rrl_adam_step_multi_packed(int S, const int* n_seg, const rrl_adam_seg_t* co
                                float beta2, float eps, void* stream);
 int rrl_nav_step_push_packed(int S, int env_kind, const rrl_step_push_t* a, void* stream);
 int rrl_maze_step_push_packed(int S, const rrl_step_push_t* a, void* stream);
+int rrl_adam_step_multi_duals_packed(int S, const int* n_seg, const rrl_adam_seg_t* const* segs, const int* n_dual,
+                                     const rrl_dual_t* const* duals, const float* lr, float beta1, float beta2, float eps,
+                                     void* stream);
+/* One seed's arguments of rrl_rcpo_penalty (same meaning, same checks). */
+typedef struct {
+    int B;
+    const float* z;
+    int n_part;
+    long long part_stride;
+    const float* lambda;  /* read from device memory by the kernel: the dual step of the same iteration writes it */
+    float* penalty;       /* nullable: the mean only */
+    float* mean;
+} rrl_penalty_args_t;
+int rrl_rcpo_penalty_packed(int S, const rrl_penalty_args_t* args, void* stream);
+int rrl_policy_heads_fwd_multi_packed(int S, const int* n, const rrl_policy_head_t* const* heads, void* stream);
 
 #ifdef __cplusplus
 }

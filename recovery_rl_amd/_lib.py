@@ -41,6 +41,7 @@ EXPORTS = [
     "rrl_sample_multi_packed", "rrl_pack_clear", "rrl_mlp3_forward_multi_packed", "rrl_mlp_head_backward_multi_packed",
     "rrl_mlp_hidden_backward_multi_packed", "rrl_mlp_backward_pair_multi_packed", "rrl_adam_step_multi_packed", "rrl_nav_step_push_packed",
     "rrl_maze_step_push_packed",
+    "rrl_adam_step_multi_duals_packed", "rrl_rcpo_penalty_packed", "rrl_policy_heads_fwd_multi_packed",
     "rrl_cem_sample", "rrl_cem_update", "rrl_cem_begin", "rrl_cem_sample_n", "rrl_cem_update_n", "rrl_cem_finish",
     "rrl_gemm_f32", "rrl_mlp3_forward", "rrl_mlp3_is_split",
     "rrl_mlp3_forward_multi", "rrl_mlp_head_backward_multi", "rrl_mlp_hidden_backward_multi",
@@ -254,6 +255,11 @@ class rrl_dual_t(C.Structure):
                 ("loss_in", C.c_void_p), ("loss_out", C.c_void_p), ("f_loss", C.c_float)]
 
 
+class rrl_penalty_args_t(C.Structure):
+    _fields_ = [("B", C.c_int), ("z", C.c_void_p), ("n_part", C.c_int), ("part_stride", C.c_longlong),
+                ("lambda_", C.c_void_p), ("penalty", C.c_void_p), ("mean", C.c_void_p)]
+
+
 class rrl_plan_weights_t(C.Structure):
     _fields_ = [("hq", C.c_int), ("he", C.c_int), ("n_nets", C.c_int)] + [
         (name, C.c_void_p) for name in ("q_w1", "q_b1", "q_w2", "q_b2", "q_w3", "q_b3", "e_w0", "e_b0", "e_w1",
@@ -300,6 +306,10 @@ def _declare(lib):
                                                     C.POINTER(C.POINTER(rrl_hidden_bwd_t)), vp]),
         "rrl_adam_step_multi_packed": (ci, [ci, C.POINTER(ci), C.POINTER(C.POINTER(rrl_adam_seg_t)), C.POINTER(f32), f32,
                                             f32, f32, vp]),
+        "rrl_adam_step_multi_duals_packed": (ci, [ci, C.POINTER(ci), C.POINTER(C.POINTER(rrl_adam_seg_t)), C.POINTER(ci),
+                                                  C.POINTER(C.POINTER(rrl_dual_t)), C.POINTER(f32), f32, f32, f32, vp]),
+        "rrl_rcpo_penalty_packed": (ci, [ci, C.POINTER(rrl_penalty_args_t), vp]),
+        "rrl_policy_heads_fwd_multi_packed": (ci, [ci, C.POINTER(ci), C.POINTER(C.POINTER(rrl_policy_head_t)), vp]),
         "rrl_nav_step_push_packed": (ci, [ci, ci, C.POINTER(rrl_step_push_t), vp]),
         "rrl_maze_step_push_packed": (ci, [ci, C.POINTER(rrl_step_push_t), vp]),
         "rrl_nav_step_push_x": (ci, [ci, C.POINTER(rrl_step_push_t), vp]),

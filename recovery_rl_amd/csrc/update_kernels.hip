@@ -213,6 +213,30 @@ __global__ void rcpo_penalty_kernel(int B, const float* z, int np, long long ps,
     }
     if (threadIdx.x == 0 && mean) mean[0] = red[0] / B;
 }
+// the same for S seeds (pack.hpp): workgroup s is seed s's stand-alone launch on its own argument block -- the statement above
+// once more, reduction tree included (the solo kernel keeps its code as compiled: the body is not shared).  The dispatcher hands
+// workgroup s to XCD s % 8: the XCD the pinned placements of the other packed launches keep seed s's rows on
+__global__ __launch_bounds__(kBlock) void rcpo_penalty_pack_kernel(const rrl_penalty_args_t* __restrict__ args) {
+    __shared__ float red[kBlock];
+    rrl_penalty_args_t a = args[blockIdx.x];
+    rrl_pack::to_global_all(a.z, a.lambda, a.penalty, a.mean);
+    const int B = a.B, np = a.n_part;
+    const long long ps = a.part_stride;
+    const float lam = a.penalty ? a.lambda[0] : 0.f;
+    float l = 0.f;
+    for (int b = threadIdx.x; b < B; b += kBlock) {
+        const float q = fmaxf(sigmoidf(psum(a.z, b, np, ps)), sigmoidf(psum(a.z, B + b, np, ps)));
+        if (a.penalty) a.penalty[b] = lam * q;
+        l += q;
+    }
+    red[threadIdx.x] = l;
+    __syncthreads();
+    for (int off = kBlock / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && a.mean) a.mean[0] = red[0] / B;
+}
 
 // ---- model-free recovery policy head (StochasticPolicy, model.py:511-525) ------------------------
 // raw[b] = last linear output (2); mean = tanh(raw) scale + bias; action = mean + exp(max(log_std, min)) eps
@@ -243,6 +267,27 @@ __global__ __launch_bounds__(kBlock) void policy_heads_group_kernel(HeadGroup hg
     while (k + 1 < hg.n && (int)blockIdx.x >= hg.first[k + 1]) ++k;
     const rrl_policy_head_t& h = hg.h[k];
     const int b = (blockIdx.x - hg.first[k]) * kBlock + threadIdx.x;
+    if (b >= h.B) return;
+    if (h.kind == RRL_HEAD_GAUSS)
+        gauss_head_fwd_row(b, h.head, h.n_part, h.part_stride, h.eps, h.scale, h.bias, h.action, h.ld_action, h.logp,
+                           h.mean_out, h.obs_in, h.obs_out);
+    else
+        stoch_head_fwd_row(b, h.head, h.n_part, h.part_stride, h.eps, h.log_std, h.min_log_std, h.scale, h.bias,
+                           h.action, h.ld_action, h.mean_out);
+}
+
+// the same launch for S seeds (pack.hpp): flat grid over (seed, member, row block) -- the seed's HeadGroup comes out of the
+// plan's device copy, the member out of its first[] as in the solo kernel
+__global__ __launch_bounds__(kBlock) void policy_heads_pack_kernel(const HeadGroup* __restrict__ groups, rrl_pack::Idx ix) {
+    int s, local;
+    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
+    const HeadGroup& hg = groups[s];
+    const int n = hg.n;
+    int k = 0;
+    while (k + 1 < n && local >= hg.first[k + 1]) ++k;
+    rrl_policy_head_t h = hg.h[k];
+    rrl_pack::globalize(h);
+    const int b = (local - hg.first[k]) * kBlock + threadIdx.x;
     if (b >= h.B) return;
     if (h.kind == RRL_HEAD_GAUSS)
         gauss_head_fwd_row(b, h.head, h.n_part, h.part_stride, h.eps, h.scale, h.bias, h.action, h.ld_action, h.logp,
@@ -592,6 +637,40 @@ __global__ __launch_bounds__(kBlock) void adam_pack_kernel(const AdamPack* __res
     if (k >= n_seg || local >= blocks) return;
     adam_seg_body(sg, vec != 0, lr, b1, b2, eps, local, blocks, sh);
 }
+// ... with the duals (rrl_adam_step_multi_duals for S seeds): a kernel of its own, adam_pack_kernel stays as it is.  The grid has
+// one row more than the seeds' largest segment count; seed s's dual row is ITS row n_seg (as in adam_multi_dual_kernel), thread 0
+// of the seed's first workgroup there
+struct AdamDualPack {
+    AdamPack pk;
+    DualSet ds;
+};
+__global__ __launch_bounds__(kBlock) void adam_pack_dual_kernel(const AdamDualPack* __restrict__ packs, rrl_pack::Idx ix) {
+    __shared__ float sh[4];
+    int s, local;
+    asm volatile("" ::"s"(ix.sp), "s"(ix.p), "s"(ix.r), "s"(ix.S));
+    if (!rrl_pack::locate_grid(ix, blockIdx.x, s, local)) return;
+    const AdamPack& pk = packs[s].pk;
+    const int k = blockIdx.y;
+    const int kk = k < RRL_ADAM_MAX_SEGS ? k : RRL_ADAM_MAX_SEGS - 1;     // (the dual row of a seed with every segment in use)
+    rrl_adam_seg_t sg = pk.a.seg[kk];
+    const int vec = pk.a.vec[kk], blocks = pk.a.first_block[kk + 1] - pk.a.first_block[kk];
+    const float lr = pk.lr, b1 = pk.b1, b2 = pk.b2, eps = pk.eps;
+    const int n_seg = pk.n_seg;
+    rrl_pack::to_global_all(sg.p, sg.g, sg.m, sg.v, sg.step_dev, sg.target, sg.g2, sg.g_part, sg.w2p, sg.target_w2p);
+    asm volatile("" ::"s"(sg.n), "s"(sg.tau), "s"(sg.weight_decay), "s"(sg.n_part), "s"(sg.part_stride), "s"(sg.part_elems),
+                 "s"(sg.w2_off), "s"(sg.w2_heads), "s"(vec), "s"(blocks), "s"(lr), "s"(b1), "s"(b2), "s"(eps), "s"(n_seg));
+    if (k == n_seg) {
+        if (local != 0 || threadIdx.x != 0) return;
+        const DualSet& ds = packs[s].ds;
+        const int n_dual = ds.n;
+#pragma unroll
+        for (int j = 0; j < RRL_ADAM_MAX_DUALS; ++j)
+            if (j < n_dual) dual_body(ds.d[j], b1, b2, eps);
+        return;
+    }
+    if (k > n_seg || local >= blocks) return;
+    adam_seg_body(sg, vec != 0, lr, b1, b2, eps, local, blocks, sh);
+}
 
 // ---- N(0,1) fill: out[2i], out[2i+1] = the Philox normal pair of index i (stream RRL_STREAM_NOISE) ----
 __global__ __launch_bounds__(kBlock) void normal_fill_kernel(long long n_pairs, uint64_t seed, uint64_t counter,
@@ -628,9 +707,9 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 extern "C" {
 
-int rrl_policy_heads_fwd_multi(int n, const rrl_policy_head_t* heads, void* stream) {
+static int build_head_group(int n, const rrl_policy_head_t* heads, HeadGroup& hg) {
     if (!heads || n <= 0 || n > kMaxHeads) return RRL_EINVAL;
-    HeadGroup hg{};
+    hg = HeadGroup{};
     hg.n = n;
     hg.first[0] = 0;
     for (int k = 0; k < n; ++k) {
@@ -647,7 +726,48 @@ int rrl_policy_heads_fwd_multi(int n, const rrl_policy_head_t* heads, void* stre
         hg.first[k + 1] = hg.first[k] + (h.B + kBlock - 1) / kBlock;
     }
     for (int k = n; k < kMaxHeads; ++k) hg.first[k + 1] = hg.first[n];
+    return RRL_OK;
+}
+
+int rrl_policy_heads_fwd_multi(int n, const rrl_policy_head_t* heads, void* stream) {
+    HeadGroup hg;
+    const int rc = build_head_group(n, heads, hg);
+    if (rc != RRL_OK) return rc;
     hipLaunchKernelGGL(policy_heads_group_kernel, dim3(hg.first[n]), dim3(kBlock), 0, (hipStream_t)stream, hg);
+    return check_launch();
+}
+
+int rrl_policy_heads_fwd_multi_packed(int S, const int* n, const rrl_policy_head_t* const* heads, void* stream) {
+    if (S <= 0 || S > rrl_pack::kMaxSeeds || !n || !heads) return RRL_EINVAL;
+    rrl_pack::Key key;
+    key.pod(8);
+    key.pod(S);
+    for (int s = 0; s < S; ++s) {
+        if (n[s] <= 0 || n[s] > kMaxHeads || !heads[s]) return RRL_EINVAL;
+        key.pod(n[s]);
+        key.add(heads[s], sizeof(rrl_policy_head_t) * n[s]);
+    }
+    // one seed: the packed launch IS the solo launch (argument block in the kernel arguments, no plan)
+    if (S == 1) return rrl_policy_heads_fwd_multi(n[0], heads[0], stream);
+    hipStream_t st = (hipStream_t)stream;
+    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    if (!plan) {
+        std::vector<HeadGroup> groups(S);
+        rrl_pack::Idx ix;
+        ix.S = S;
+        ix.first[0] = 0;
+        for (int s = 0; s < S; ++s) {               // every seed's heads are validated before anything is stored or launched
+            const int rc = build_head_group(n[s], heads[s], groups[s]);
+            if (rc != RRL_OK) return rc;
+            ix.first[s + 1] = ix.first[s] + groups[s].first[n[s]];
+        }
+        for (int s = S; s < rrl_pack::kMaxSeeds; ++s) ix.first[s + 1] = ix.first[S];
+        plan = rrl_pack::store(key, groups.data(), sizeof(HeadGroup) * S, st);
+        if (!plan) return rrl_pack::store_error();
+        plan->grid = rrl_pack::finish(ix);
+        plan->ix = ix;
+    }
+    hipLaunchKernelGGL(policy_heads_pack_kernel, dim3(plan->grid), dim3(kBlock), 0, st, (const HeadGroup*)plan->dev, plan->ix);
     return check_launch();
 }
 
@@ -706,6 +826,32 @@ int rrl_rcpo_penalty(int B, const float* z, int n_part, long long part_stride, c
     if (!z || (penalty && !lambda) || (!penalty && !mean) || B <= 0 || n_part <= 0 || n_part > 4) return RRL_EINVAL;
     hipLaunchKernelGGL(rcpo_penalty_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, B, z, n_part, part_stride,
                        lambda, penalty, mean);
+    return check_launch();
+}
+
+int rrl_rcpo_penalty_packed(int S, const rrl_penalty_args_t* args, void* stream) {
+    if (S <= 0 || S > rrl_pack::kMaxSeeds || !args) return RRL_EINVAL;
+    for (int s = 0; s < S; ++s) {
+        const rrl_penalty_args_t& a = args[s];
+        if (!a.z || (a.penalty && !a.lambda) || (!a.penalty && !a.mean) || a.B <= 0 || a.n_part <= 0 || a.n_part > 4)
+            return RRL_EINVAL;
+    }
+    // one seed: the packed launch IS the solo launch
+    if (S == 1)
+        return rrl_rcpo_penalty(args[0].B, args[0].z, args[0].n_part, args[0].part_stride, args[0].lambda, args[0].penalty,
+                                args[0].mean, stream);
+    rrl_pack::Key key;
+    key.pod(9);
+    key.pod(S);
+    key.add(args, sizeof(rrl_penalty_args_t) * S);
+    hipStream_t st = (hipStream_t)stream;
+    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    if (!plan) {
+        plan = rrl_pack::store(key, args, sizeof(rrl_penalty_args_t) * S, st);
+        if (!plan) return rrl_pack::store_error();
+        plan->grid = S;
+    }
+    hipLaunchKernelGGL(rcpo_penalty_pack_kernel, dim3(plan->grid), dim3(kBlock), 0, st, (const rrl_penalty_args_t*)plan->dev);
     return check_launch();
 }
 
@@ -781,10 +927,9 @@ int rrl_adam_step_multi(int n_seg, const rrl_adam_seg_t* segs, float lr, float b
     return check_launch();
 }
 
-int rrl_adam_step_multi_duals(int n_seg, const rrl_adam_seg_t* segs, int n_dual, const rrl_dual_t* duals, float lr,
-                              float beta1, float beta2, float eps, void* stream) {
-    if (n_dual <= 0 || n_dual > RRL_ADAM_MAX_DUALS || !duals || n_seg < 0) return RRL_EINVAL;
-    DualSet ds{};
+static int build_dual_set(int n_dual, const rrl_dual_t* duals, DualSet& ds) {
+    if (n_dual <= 0 || n_dual > RRL_ADAM_MAX_DUALS || !duals) return RRL_EINVAL;
+    ds = DualSet{};
     ds.n = n_dual;
     for (int k = 0; k < n_dual; ++k) {
         const rrl_dual_t& d = duals[k];
@@ -793,6 +938,15 @@ int rrl_adam_step_multi_duals(int n_seg, const rrl_adam_seg_t* segs, int n_dual,
             return RRL_EINVAL;
         ds.d[k] = d;
     }
+    return RRL_OK;
+}
+
+int rrl_adam_step_multi_duals(int n_seg, const rrl_adam_seg_t* segs, int n_dual, const rrl_dual_t* duals, float lr,
+                              float beta1, float beta2, float eps, void* stream) {
+    if (n_seg < 0) return RRL_EINVAL;
+    DualSet ds;
+    const int rcd = build_dual_set(n_dual, duals, ds);
+    if (rcd != RRL_OK) return rcd;
     AdamSegs a{};
     int most = 1;
     if (n_seg > 0) {
@@ -847,6 +1001,58 @@ int rrl_adam_step_multi_packed(int S, const int* n_seg, const rrl_adam_seg_t* co
         plan->i0 = segs_most;
     }
     hipLaunchKernelGGL(adam_pack_kernel, dim3(plan->grid, plan->i0), dim3(kBlock), 0, st, (const AdamPack*)plan->dev, plan->ix);
+    return check_launch();
+}
+
+int rrl_adam_step_multi_duals_packed(int S, const int* n_seg, const rrl_adam_seg_t* const* segs, const int* n_dual,
+                                     const rrl_dual_t* const* duals, const float* lr, float beta1, float beta2, float eps,
+                                     void* stream) {
+    if (S <= 0 || S > rrl_pack::kMaxSeeds || !n_seg || !segs || !n_dual || !duals || !lr) return RRL_EINVAL;
+    rrl_pack::Key key;
+    key.pod(10);
+    key.pod(S);
+    key.pod(beta1); key.pod(beta2); key.pod(eps);
+    for (int s = 0; s < S; ++s) {
+        if (n_seg[s] < 0 || n_seg[s] > RRL_ADAM_MAX_SEGS || (n_seg[s] > 0 && !segs[s]) || n_dual[s] <= 0 ||
+            n_dual[s] > RRL_ADAM_MAX_DUALS || !duals[s])
+            return RRL_EINVAL;
+        key.pod(n_seg[s]);
+        key.pod(n_dual[s]);
+        key.pod(lr[s]);
+        if (n_seg[s] > 0) key.add(segs[s], sizeof(rrl_adam_seg_t) * n_seg[s]);
+        key.add(duals[s], sizeof(rrl_dual_t) * n_dual[s]);
+    }
+    // one seed: the packed launch IS the solo launch (argument block in the kernel arguments, no plan)
+    if (S == 1) return rrl_adam_step_multi_duals(n_seg[0], segs[0], n_dual[0], duals[0], lr[0], beta1, beta2, eps, stream);
+    hipStream_t st = (hipStream_t)stream;
+    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    if (!plan) {
+        std::vector<AdamDualPack> packs(S);
+        rrl_pack::Idx ix;
+        ix.S = S;
+        ix.first[0] = 0;
+        int segs_most = 0;
+        for (int s = 0; s < S; ++s) {               // every seed's segments and duals are validated before anything is launched
+            packs[s] = AdamDualPack{};
+            int rc = build_dual_set(n_dual[s], duals[s], packs[s].ds);
+            if (rc == RRL_OK && n_seg[s] > 0) rc = build_adam_segs(n_seg[s], segs[s], packs[s].pk.a);
+            if (rc != RRL_OK) return rc;
+            packs[s].pk.n_seg = n_seg[s];
+            packs[s].pk.lr = lr[s]; packs[s].pk.b1 = beta1; packs[s].pk.b2 = beta2; packs[s].pk.eps = eps;
+            int most = 1;                 // the dual row needs one workgroup of the seed, a segment row as many as its largest segment
+            for (int k = 0; k < n_seg[s]; ++k) most = std::max(most, packs[s].pk.a.first_block[k + 1] - packs[s].pk.a.first_block[k]);
+            ix.first[s + 1] = ix.first[s] + most;
+            segs_most = std::max(segs_most, n_seg[s]);
+        }
+        for (int s = S; s < rrl_pack::kMaxSeeds; ++s) ix.first[s + 1] = ix.first[S];
+        plan = rrl_pack::store(key, packs.data(), sizeof(AdamDualPack) * S, st);
+        if (!plan) return rrl_pack::store_error();
+        plan->grid = rrl_pack::finish(ix);
+        plan->ix = ix;
+        plan->i0 = segs_most + 1;         // one row more: row n_seg of a seed is its dual row
+    }
+    hipLaunchKernelGGL(adam_pack_dual_kernel, dim3(plan->grid, plan->i0), dim3(kBlock), 0, st, (const AdamDualPack*)plan->dev,
+                       plan->ix);
     return check_launch();
 }
 

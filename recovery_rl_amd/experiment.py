@@ -1099,17 +1099,40 @@ def run_packed(exp_cfg, rank=0, world_size=1):
     iteration of all of them is ONE hipGraph whose launches are shared (packed.PackedLoop); every seed's trajectory is the one
     its solo run produces.  Logging per seed at the `--log_every` cadence: counters, the per-episode table (`episode_stats`,
     `episode_stats.bin`) and, with `--info_envs K`, the per-step `train_stats` of the first K envs -- the files the solo
-    lock-step run of that seed writes.  Returns the list of per-seed histories."""
+    lock-step run of that seed writes.  Returns the list of per-seed histories.
+
+    Packed lines of the comparison (scripts/navigation1.sh): Recovery RL with the model-free recovery policy, unconstrained
+    SAC and the reward penalty (no recovery, no baseline flags), LR (--DGD_constraints --update_nu), RSPO (--DGD_constraints
+    --nu_schedule) and RCPO (--RCPO), each of the last three with or without --use_recovery --MF_recovery and on the fused
+    update path (RRL_FAST_BASELINES=1).  RSPO packs with the multiplier the solo lock-step loop uses throughout,
+    nu_schedule(1) (the lock-step loop has no episode index; the recorded launches carry that value).  Not packed: SQRL's
+    --use_constraint_sampling (its acting pass draws the candidates through module code), model-based recovery,
+    --dp_mode env_shard, --resume / --checkpoint_every."""
     import copy
-    from .fast_update import fast_path_supported, uses_baseline_terms
+    from .fast_update import fast_baselines_enabled, fast_path_supported, uses_baseline_terms
     from .packed import PackedLoop
     S = int(exp_cfg.seeds_per_gpu)
-    if exp_cfg.num_envs < 2 or not fast_path_supported(exp_cfg) or uses_baseline_terms(exp_cfg) or uses_mb_recovery(exp_cfg) or \
-            not (exp_cfg.use_recovery and exp_cfg.MF_recovery) or getattr(exp_cfg, "dp_mode", "replicas") != "replicas":
-        raise ValueError("--seeds_per_gpu needs the lock-step loop (--num_envs > 1) on the fused update path with model-free "
-                         "recovery (every rank of a multi-GPU launch packs its own seeds: replicas, no exchange)")
+    if exp_cfg.num_envs < 2:
+        raise ValueError("--seeds_per_gpu needs the lock-step loop (--num_envs > 1)")
+    if exp_cfg.use_constraint_sampling:
+        raise ValueError("--seeds_per_gpu does not pack --use_constraint_sampling (SQRL's acting pass draws its candidates "
+                         "through module code): run the seeds one at a time")
+    if exp_cfg.use_recovery and not exp_cfg.MF_recovery:
+        raise ValueError("--seeds_per_gpu packs the model-free recovery policy only (--use_recovery needs --MF_recovery; "
+                         "model-based recovery and --Q_sampling_recovery run one seed at a time)")
+    if getattr(exp_cfg, "dp_mode", "replicas") != "replicas":
+        raise ValueError("--seeds_per_gpu does not combine with --dp_mode env_shard (every rank of a multi-GPU launch packs "
+                         "its own seeds: replicas, no exchange)")
+    if uses_baseline_terms(exp_cfg) and not fast_baselines_enabled():
+        raise ValueError("--seeds_per_gpu packs the comparison algorithms (--DGD_constraints, --update_nu, --nu_schedule, "
+                         "--RCPO) on the fused update path only: set RRL_FAST_BASELINES=1")
+    if not fast_path_supported(exp_cfg) or getattr(exp_cfg, "no_fast_path", False):
+        raise ValueError("--seeds_per_gpu needs the fused update path (Gaussian policy, fixed alpha, "
+                         "--target_update_interval 1, no --no_fast_path)")
     if getattr(exp_cfg, "resume", "") or getattr(exp_cfg, "checkpoint_every", 0):
-        raise ValueError("--seeds_per_gpu: checkpoints are written and resumed by the solo lock-step run (--seeds_per_gpu 1)")
+        raise ValueError("--seeds_per_gpu: checkpoints (--resume, --checkpoint_every) are written and resumed by the solo "
+                         "lock-step run (--seeds_per_gpu 1)")
+    constrained = bool(uses_constraint_buffer(exp_cfg))
     from .episode_log import EPISODE_DTYPE, EpisodeLog, InfoRing
     n = exp_cfg.num_envs
     log_every = exp_cfg.log_every if getattr(exp_cfg, "log_every", 0) else 100
@@ -1120,7 +1143,7 @@ def run_packed(exp_cfg, rank=0, world_size=1):
         cfg.seed = exp_cfg.seed + k
         cfg.logdir_suffix = "%s_seed%d" % (exp_cfg.logdir_suffix, cfg.seed)
         exp = Experiment(cfg)
-        if not cfg.disable_offline_updates:
+        if not cfg.disable_offline_updates and constrained:         # as Experiment.run
             exp.pretrain_critic_recovery()
         exp.loop.start()
         # per-episode table and per-step info stream from the first iteration on, as in the solo lock-step run
@@ -1171,10 +1194,14 @@ def run_packed(exp_cfg, rank=0, world_size=1):
                                 if infos[k] is not None else {})}, f)
         return done
 
-    # eager until every seed has a batch, has left the random-action phase and trains Q_risk online
+    def gate(e):
+        """Q_risk trained online?  The gate of run_vectorized: never without a constraint buffer (unconstrained SAC, RP)."""
+        return e.online_qrisk_enabled() if constrained else False
+
+    # eager until every seed has a batch, has left the random-action phase and (with a constraint buffer) trains Q_risk online
     it, logged, finished = 0, 0, False
     while True:
-        ready = [len(e.memory) > cfg.batch_size and e.loop.total_numsteps >= cfg.start_steps and e.online_qrisk_enabled()
+        ready = [len(e.memory) > cfg.batch_size and e.loop.total_numsteps >= cfg.start_steps and gate(e) == constrained
                  for e in exps]
         if all(ready) or finished:
             break
@@ -1184,14 +1211,14 @@ def run_packed(exp_cfg, rank=0, world_size=1):
         for e in exps:
             e.loop.vector_step(do_update=len(e.memory) > cfg.batch_size,
                                random_actions=cfg.start_steps > e.loop.total_numsteps,
-                               online_qrisk=e.online_qrisk_enabled())
+                               online_qrisk=gate(e))
         after()
         it += 1
         if it // log_every > logged:
             logged = it // log_every
             finished = log_point(it)
     if not finished:
-        packed = PackedLoop([e.loop for e in exps], online_qrisk=True)
+        packed = PackedLoop([e.loop for e in exps], online_qrisk=constrained)
         # (a capture advances every seed by <= 5 real iterations: the tables and rings have 8 iterations of head-room)
         many = 1 if info_k else max(1, int(getattr(exp_cfg, "graph_iterations", 4)))
         it += packed.capture(around=(before, after) if info_k else None, iters=many)

@@ -140,7 +140,7 @@ def adam_multi(lr, nets, betas=(0.9, 0.999), eps=1e-8, duals=None):
                                       net.offset["W2"] if pack else 0, net.p["W2"].shape[0] if pack else 0)
     if duals:
         arr = (_lib.rrl_dual_t * len(duals))(*duals)
-        record("unsupported", "rrl_adam_step_multi_duals")
+        record("adam_duals", segs, len(nets), arr, len(duals), float(lr), float(betas[0]), float(betas[1]), float(eps))
         _lib.check(lib.rrl_adam_step_multi_duals(len(nets), segs, len(duals), arr, lr, betas[0], betas[1], eps,
                                                  _lib.current_stream()), "rrl_adam_step_multi_duals")
         return
@@ -381,7 +381,7 @@ def backward_multi(triples):
 def heads_multi(heads):
     """Independent policy heads (rrl_policy_head_t) in one launch; a lone head is a list of one."""
     arr = (_lib.rrl_policy_head_t * len(heads))(*heads)
-    record("unsupported", "rrl_policy_heads_fwd_multi")
+    record("heads", arr, len(heads))
     _lib.check(_lib.load().rrl_policy_heads_fwd_multi(len(heads), arr, _lib.current_stream()),
                "rrl_policy_heads_fwd_multi")
 
@@ -574,11 +574,12 @@ class FastUpdater:
     def _penalty(self, z, want_penalty=True, mean=None):
         """rrl_rcpo_penalty: penalty = lambda max sigmoid(z) (want_penalty) and the batch mean of max sigmoid(z)."""
         t, n_part, ps = z
-        record("unsupported", "rrl_rcpo_penalty")
         p = _lib.ptr
-        _lib.check(self.lib.rrl_rcpo_penalty(self.B, p(t), n_part, ps, p(self.agent.lambda_RCPO) if want_penalty else None,
-                                             p(self.penalty) if want_penalty else None, p(mean), _lib.current_stream()),
-                   "rrl_rcpo_penalty")
+        a = _lib.rrl_penalty_args_t(self.B, p(t), n_part, ps, p(self.agent.lambda_RCPO) if want_penalty else None,
+                                    p(self.penalty) if want_penalty else None, p(mean))
+        record("penalty", a)
+        _lib.check(self.lib.rrl_rcpo_penalty(a.B, a.z, a.n_part, a.part_stride, a.lambda_, a.penalty, a.mean,
+                                             _lib.current_stream()), "rrl_rcpo_penalty")
 
     def policy_loss(self):
         """The SAC policy loss statistic of the last update (with the Lagrangian term under --DGD_constraints, put together
@@ -1029,7 +1030,9 @@ class FastActor:
         if noise is None:
             noise = f.actor_noise(n)
         if not use_recovery:
-            self.pol.forward(obs, save=False)
+            # (grouped, on the column-split kernels: the stand-alone launch's kernel body through the group entry point, a launch
+            # the tape can pack)
+            f._forwards([(self.pol, obs, dict(save=False))], f.grouped)
             heads_multi([f._gauss_desc(self.pol.parts, noise[0], self.task_action, None, n=n)])
             return self.task_action, self.task_action, None
         assert mf_recovery, "FastActor covers the model-free recovery policy"

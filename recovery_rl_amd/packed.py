@@ -67,7 +67,8 @@ class PackedLoop:
             bad = [op for op in tape if op[0] == "unsupported"]
             if bad:
                 raise _lib.RRLError("seed packing needs the grouped fused path (hidden_size 256-style stacks, first layer "
-                                    "fused into the hidden-layer backward): %s was launched" % bad[0][1])
+                                    "fused into the hidden-layer backward, acting on the fused kernels): %s was launched"
+                                    % bad[0][1])
             tapes.append(tape)
         kinds = [tuple(op[0] for op in t) for t in tapes]
         if any(k != kinds[0] for k in kinds):
@@ -106,6 +107,23 @@ class PackedLoop:
                 segs = (p(_lib.rrl_adam_seg_t) * S)(*[C.cast(op[1], p(_lib.rrl_adam_seg_t)) for op in ops])
                 lr = (C.c_float * S)(*[op[3] for op in ops])
                 stages.append((self.lib.rrl_adam_step_multi_packed, (S, n, segs, lr, b1, b2, eps), ops))
+            elif kind == "adam_duals":
+                # the optimiser launch of a comparison algorithm's SAC update: the segments plus the seed's dual variables
+                b1, b2, eps = ops[0][6], ops[0][7], ops[0][8]
+                assert all(op[6:9] == (b1, b2, eps) for op in ops)
+                n = (C.c_int * S)(*[op[2] for op in ops])
+                segs = (p(_lib.rrl_adam_seg_t) * S)(*[C.cast(op[1], p(_lib.rrl_adam_seg_t)) for op in ops])
+                n_dual = (C.c_int * S)(*[op[4] for op in ops])
+                duals = (p(_lib.rrl_dual_t) * S)(*[C.cast(op[3], p(_lib.rrl_dual_t)) for op in ops])
+                lr = (C.c_float * S)(*[op[5] for op in ops])
+                stages.append((self.lib.rrl_adam_step_multi_duals_packed, (S, n, segs, n_dual, duals, lr, b1, b2, eps), ops))
+            elif kind == "penalty":
+                args = (_lib.rrl_penalty_args_t * S)(*[op[1] for op in ops])
+                stages.append((self.lib.rrl_rcpo_penalty_packed, (S, args), ops))
+            elif kind == "heads":
+                n = (C.c_int * S)(*[op[2] for op in ops])
+                heads = (p(_lib.rrl_policy_head_t) * S)(*[C.cast(op[1], p(_lib.rrl_policy_head_t)) for op in ops])
+                stages.append((self.lib.rrl_policy_heads_fwd_multi_packed, (S, n, heads), ops))
             elif kind == "step":
                 env_name, env_kind = ops[0][1], ops[0][2]
                 assert all(op[1] == env_name and op[2] == env_kind for op in ops), "one env per packed run"
@@ -126,12 +144,14 @@ class PackedLoop:
     def launches(self):
         """Kernel launches of one packed iteration: a head + hidden backward stage is ONE launch when its stacks share a loss
         class and there are at most PAIR_MAX_SEEDS seeds (rrl_mlp_backward_pair_multi_packed: tile form up to two seeds,
-        block form beyond), two otherwise; per-seed calls count once per seed."""
+        block form beyond), two otherwise; per-seed calls count once per seed; every other kind (the comparison algorithms'
+        "adam_duals", "penalty" and "heads" included) is one launch."""
         total = 0
         for fn, args, ops in self.stages:
             if ops[0][0] == "pair_bwd":
                 kinds = {op[1][k].loss.kind for op in ops for k in range(op[3])}
-                outputs = {1 if kind <= _lib.LOSS_QRISK_POLICY else kind for kind in kinds}     # one kernel per output count
+                one = (_lib.LOSS_SAC_CRITIC, _lib.LOSS_SAC_POLICY, _lib.LOSS_QRISK_CRITIC, _lib.LOSS_QRISK_POLICY, _lib.LOSS_DGD_QRISK)
+                outputs = {1 if kind in one else kind for kind in kinds}     # one kernel per output count
                 total += 1 if min(kinds) >= 0 and len(outputs) == 1 and self.S <= self.PAIR_MAX_SEEDS else 2
             elif ops[0][0] == "call":
                 total += len(ops)
