@@ -911,6 +911,53 @@ typedef struct {
 int rrl_rcpo_penalty_packed(int S, const rrl_penalty_args_t* args, void* stream);
 int rrl_policy_heads_fwd_multi_packed(int S, const int* n, const rrl_policy_head_t* const* heads, void* stream);
 
+/* --------------------------------------------------------------------------------------------
+ * SQRL constraint-sampling acting.  Replaces SAC.select_action with --use_constraint_sampling (recovery_rl/sac.py:139-161)
+ * for n envs at once: per env e, k candidate actions of the task policy, the twin Q_risk on each, one pick.  One MFMA
+ * kernel, one workgroup per env; nothing but action[n, 2] (and the diagnostics that are asked for) leaves the chip.
+ *   candidate  eps[e, c] = the normal pair of Philox (seed, row e k + c, RRL_STREAM_SQRL, counter + tick) rounded to f32
+ *              (as rrl_normal_fill rounds), or eps_in[e, c];  a[e, c], logp[e, c] = the tanh-Gaussian head on
+ *              head[e] = (mean0, mean1, log_std0, log_std1) -- RRL_HEAD_GAUSS of rrl_policy_head_t, same arithmetic
+ *   score      z_h = head h of Q_risk (4 -> 256 relu -> 256 relu -> 1) on [obs_e | a_ec], exact-f32 MFMA;
+ *              q = max(sigmoid z_0, sigmoid z_1) (NaN propagates); safe = q <= eps_safe
+ *   pick       no safe candidate: argmin q (lowest index on ties).  Otherwise u = the open-unit double of the low 64 bits
+ *              of Philox (seed, row e, RRL_STREAM_SQRL_PICK, counter + tick), or u_in[e]; weights in double
+ *              w_c = safe ? exp(logp_c - max safe logp) : 0, T = their sum in ascending c, c* = the first safe c whose
+ *              running sum exceeds u T (none: the last safe c); pick = (safe candidates with index <= c*) - 1 -- the
+ *              position in the SAFE list applied to the FULL list, as the reference does (sac.py:157-158).
+ *   action[e] = a[e, pick]
+ * Weights: the stacked twin heads W1 [2,256,4], b1 [2,256], b2 [2,256], W3 [2,1,256], b3 [2,1] (nn.Linear layout) and W2 as
+ * its fragment-order copy W2p (rrl_w2_pack, 16-byte aligned).
+ * Checks before any launch: a required pointer NULL, n <= 0, H != 256, d_obs or d_act != 2, n_part outside 1..4,
+ * misaligned W2p: RRL_EINVAL; k outside 1..128 or n k >= 2^32: RRL_ERANGE.
+ * rrl_sqrl_scratch_floats(n, k): floats of `scratch` this form of the kernel needs (0: the candidates' q, logp and actions stay
+ * in LDS; `scratch` may be NULL); the same range checks.
+ * ------------------------------------------------------------------------------------------ */
+enum { RRL_STREAM_SQRL = 9,       /* SQRL candidate noise           */
+       RRL_STREAM_SQRL_PICK = 10  /* SQRL categorical draw          */ };
+typedef struct {
+    int n, k;                     /* envs, candidates per env */
+    int H, d_obs, d_act;          /* 256, 2, 2 */
+    const float* obs;             /* [n, 2] */
+    const float* head;            /* [n, 4] last-layer output of the task policy, as n_part partial sums part_stride floats */
+    int n_part;                   /* apart (added in the fixed order ((p0 + p1) + p2) + p3) */
+    long long part_stride;
+    const float *scale, *bias;    /* [2] action scale / bias */
+    const float *W1, *b1, *W2p, *b2, *W3, *b3;
+    float eps_safe;
+    uint64_t seed, counter;
+    uint64_t* counter_dev;        /* nullable {tick, ticket}: tick read by every workgroup, += counter_inc by the last one */
+    uint64_t counter_inc;
+    const float* eps_in;          /* nullable [n, k, 2]: replaces the candidate noise */
+    const double* u_in;           /* nullable [n]: replaces the pick's uniform */
+    float* scratch;               /* [rrl_sqrl_scratch_floats(n, k)]; nullable when that is 0 */
+    float* action;                /* [n, 2] */
+    float *q, *logp, *cand, *z;   /* nullable diagnostics: [n, k], [n, k], [n, k, 2], [2, n, k] (pre-activations) */
+    int32_t *pick, *cstar, *n_safe;   /* nullable diagnostics [n]; cstar = -1 on the argmin branch */
+} rrl_sqrl_act_t;
+long long rrl_sqrl_scratch_floats(long long n, int k);
+int rrl_sqrl_act(const rrl_sqrl_act_t* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

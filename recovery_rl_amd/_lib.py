@@ -15,7 +15,7 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
 HIP_SOURCES = ["nav_kernels.hip", "replay_kernels.hip", "maze_kernels.hip", "cem_kernels.hip",
                "mlp_kernels.hip", "mlp_fwd_kernels.hip", "update_kernels.hip", "log_kernels.hip", "plan_kernels.hip", "ens_train_kernels.hip",
-               "ens_train_big_kernels.hip"]
+               "ens_train_big_kernels.hip", "sqrl_kernels.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-ffp-contract=off", "-Wall", "-Wno-unused-function",
                "-Wno-bitwise-instead-of-logical"]
@@ -54,6 +54,7 @@ EXPORTS = [
     "rrl_plan_cost_f16x3", "rrl_plan_cost_n",
     "rrl_ens_train_supported", "rrl_ens_scratch_floats", "rrl_ens_train_grad", "rrl_ens_train_epoch",
     "rrl_ens_train_big_supported", "rrl_ens_big_scratch_floats", "rrl_ens_train_grad_big", "rrl_ens_train_epoch_big",
+    "rrl_sqrl_scratch_floats", "rrl_sqrl_act",
 ]
 
 class RRLError(RuntimeError):
@@ -266,6 +267,19 @@ class rrl_plan_weights_t(C.Structure):
                                         "e_b1", "e_w2", "e_b2", "e_w3", "e_b3", "inputs_mu", "inputs_sigma",
                                         "max_logvar", "min_logvar")]
 
+
+STREAM_SQRL, STREAM_SQRL_PICK = 9, 10
+
+
+class rrl_sqrl_act_t(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n", "k", "H", "d_obs", "d_act")] + [
+        ("obs", C.c_void_p), ("head", C.c_void_p), ("n_part", C.c_int), ("part_stride", C.c_longlong)] + [
+        (n, C.c_void_p) for n in ("scale", "bias", "W1", "b1", "W2p", "b2", "W3", "b3")] + [
+        ("eps_safe", C.c_float), ("seed", C.c_uint64), ("counter", C.c_uint64), ("counter_dev", C.c_void_p),
+        ("counter_inc", C.c_uint64)] + [
+        (n, C.c_void_p) for n in ("eps_in", "u_in", "scratch", "action", "q", "logp", "cand", "z", "pick", "cstar", "n_safe")]
+
+
 _lib = None
 
 
@@ -356,6 +370,8 @@ def _declare(lib):
         "rrl_ens_train_grad_big": (ci, [C.POINTER(rrl_ens_t), ll, vp, vp, vp, ll, vp, vp, vp]),
         "rrl_ens_train_epoch_big": (ci, [C.POINTER(rrl_ens_t), ci, C.POINTER(rrl_adam_seg_t), f32, f32, f32, f32, vp, vp,
                                          vp, ll, ll, ll, vp, vp, vp]),
+        "rrl_sqrl_scratch_floats": (ll, [ll, ci]),
+        "rrl_sqrl_act": (ci, [C.POINTER(rrl_sqrl_act_t), vp]),
         "rrl_episode_log_append": (ci, [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(rrl_episode_log_t), vp]),
     }
     for name, (res, args) in sig.items():

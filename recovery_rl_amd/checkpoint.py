@@ -156,6 +156,8 @@ def loop_state(loop):
     out = {"stats": _cpu(loop.stats), "reward_sums": _cpu(loop.reward_sums), "ep_reward": _cpu(loop.ep_reward),
            "total_numsteps": loop.total_numsteps, "updates": loop.updates, "host_updates": list(loop.host_updates),
            "num_constraint_violations": loop.num_constraint_violations}
+    if getattr(loop, "sqrl_hip", False):
+        out["sqrl_tick"] = _cpu(loop.sqrl_actor().sqrl_tick)     # the rrl_sqrl_act acting pass's Philox tick (RRL_FAST_SQRL=1)
     log = loop.episode_log
     if log is not None:
         out["episode_log"] = {"ep_len": _cpu(log.ep_len), "ep_ret": _cpu(log.ep_ret), "ep_viol": _cpu(log.ep_viol),
@@ -174,6 +176,8 @@ def load_loop_state(loop, sd):
     loop.num_constraint_violations = sd["num_constraint_violations"]
     loop.obs = loop.env.obs
     loop.graph = None                                   # captured graphs hold the old stream position
+    if "sqrl_tick" in sd:
+        loop.sqrl_actor().sqrl_tick.copy_(sd["sqrl_tick"])
     if loop.episode_log is not None and "episode_log" in sd:
         log, e = loop.episode_log, sd["episode_log"]
         for f in ("ep_len", "ep_ret", "ep_viol", "ep_rec", "state"):
@@ -242,6 +246,10 @@ def load_experiment_state(exp, sd):
     if ("flat" in sd["agent"]) != (exp.agent.fast is not None):
         raise ValueError("checkpoint and run disagree on the fused update path (--no_fast_path; the comparison "
                          "algorithms take it under RRL_FAST_BASELINES=1 only)")
+    if ("sqrl_tick" in sd["loop"]) != bool(getattr(exp.loop, "sqrl_hip", False)):
+        raise ValueError("checkpoint and run disagree on SQRL's acting pass: the checkpoint was written with the %s path, this "
+                         "run takes the %s path (RRL_FAST_SQRL=1 with RRL_FAST_BASELINES=1 selects the kernel)"
+                         % (("kernel", "module") if "sqrl_tick" in sd["loop"] else ("module", "kernel")))
     if ("mpc" in sd) != (exp.recovery_policy is not None):
         raise ValueError("checkpoint and run disagree on model-based recovery")
     load_agent_state(exp.agent, sd["agent"])

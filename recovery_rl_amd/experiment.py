@@ -74,6 +74,10 @@ class VectorLoop:
         self.carry_actor = os.environ.get("RRL_CARRY_ACTOR", "1") != "0"
         # the task batch's keys selected one step ahead, no draw launch (FastUpdater.update_pair); RRL_DRAW_AHEAD=0: off
         self.draw_ahead = os.environ.get("RRL_DRAW_AHEAD", "1") != "0"
+        # SQRL's constraint-sampling acting pass on the rrl_sqrl_act kernel (RRL_FAST_SQRL=1, fast_update.sqrl_acting_path)
+        from .fast_update import sqrl_acting_path
+        self.sqrl_hip = bool(getattr(agent, "fast", None) is not None and sqrl_acting_path(cfg) == "hip"
+                             and agent.fast.qrisk.w2p is not None)
         self._graph_ahead = False
         # vectorisation rule 5: at N > 1 an env's CEM warm start does not survive its episode (MPC.forget_plans)
         self.forget_plans = bool(recovery_policy is not None and self.n > 1 and hasattr(recovery_policy, "forget_plans")
@@ -135,11 +139,23 @@ class VectorLoop:
                 self.host_updates[1] += 1
             self.updates += 1
 
+    def sqrl_actor(self):
+        """The FastActor of the rrl_sqrl_act acting pass (sqrl_hip): it owns the pass's device tick, the seed is the loop's."""
+        if self._actor is None:
+            from .fast_update import FastActor
+            self._actor = FastActor(self.agent.fast, self.n)
+            self._actor.sqrl_seed = int(self.cfg.seed) & 0xFFFFFFFFFFFFFFFF
+        return self._actor
+
     def act(self, obs, random_actions=False, train=True):
         """Batched get_action (experiment.py:546-577): (task action, executed action, recovery)."""
         cfg = self.cfg
         fast = getattr(self.agent, "fast", None)
-        # (SQRL's constraint sampling, sac.py:139-161, draws its 100 candidates through SAC.select_action)
+        if self.sqrl_hip and train and not random_actions and obs.shape[0] == self.n:
+            # SQRL's 100 candidates per env scored and picked by one kernel (sac.py:139-161; no recovery policy here)
+            action = self.sqrl_actor().act_sqrl(obs, cfg.eps_safe)
+            return action, action, None
+        # (SQRL's constraint sampling, sac.py:139-161, otherwise draws its 100 candidates through SAC.select_action)
         if (fast is not None and train and not random_actions and obs.shape[0] == self.n
                 and (not cfg.use_recovery or cfg.MF_recovery) and not cfg.use_constraint_sampling):
             if self._actor is None:
@@ -619,6 +635,9 @@ class Experiment:
             self.agent.fast.enable_grad_sync(world_size)
         self.loop = VectorLoop(exp_cfg, self.env, self.agent, self.memory, self.recovery_memory,
                                self.recovery_policy, self.nu_schedule)
+        if exp_cfg.use_constraint_sampling:
+            # which code draws, scores and picks SQRL's candidates in the training loop (RRL_FAST_SQRL=1: the kernel)
+            self.vector_rules["sqrl_acting"] = "hip" if self.loop.sqrl_hip else "modules"
 
     # -- setup -----------------------------------------------------------------------------------
     def experiment_setup(self):
@@ -673,7 +692,8 @@ class Experiment:
         # run_stats.pkl ("vector_rules") and the checkpoint
         self.vector_rules = {"demo_share": share if share > 0 else 0.0, "pinned_demonstrations": int(pinned),
                              **{k: self.vector_rules[k] for k in ("update_path", "replay_capacities", "cover_rows_limit",
-                                                                   "buffers_cover_the_run", "plan_warm_start")}}
+                                                                   "buffers_cover_the_run", "plan_warm_start", "sqrl_acting")
+                                if k in self.vector_rules}}
         if cfg.num_envs > 1:
             print("Q_risk batch: %s (--demo_share; 0 = the reference's single uniform draw, replay_memory.py:54-72)"
                   % ("%d of %d rows from the %d pinned demonstrations, the rest from the online rows"
@@ -1106,7 +1126,7 @@ def run_packed(exp_cfg, rank=0, world_size=1):
     --nu_schedule) and RCPO (--RCPO), each of the last three with or without --use_recovery --MF_recovery and on the fused
     update path (RRL_FAST_BASELINES=1).  RSPO packs with the multiplier the solo lock-step loop uses throughout,
     nu_schedule(1) (the lock-step loop has no episode index; the recorded launches carry that value).  Not packed: SQRL's
-    --use_constraint_sampling (its acting pass draws the candidates through module code), model-based recovery,
+    --use_constraint_sampling (its acting pass is module code, or under RRL_FAST_SQRL=1 a launch without a packed form), model-based recovery,
     --dp_mode env_shard, --resume / --checkpoint_every."""
     import copy
     from .fast_update import fast_baselines_enabled, fast_path_supported, uses_baseline_terms
@@ -1116,7 +1136,8 @@ def run_packed(exp_cfg, rank=0, world_size=1):
         raise ValueError("--seeds_per_gpu needs the lock-step loop (--num_envs > 1)")
     if exp_cfg.use_constraint_sampling:
         raise ValueError("--seeds_per_gpu does not pack --use_constraint_sampling (SQRL's acting pass draws its candidates "
-                         "through module code): run the seeds one at a time")
+                         "through module code, or with RRL_FAST_SQRL=1 in a launch that has no packed form): run the seeds "
+                         "one at a time")
     if exp_cfg.use_recovery and not exp_cfg.MF_recovery:
         raise ValueError("--seeds_per_gpu packs the model-free recovery policy only (--use_recovery needs --MF_recovery; "
                          "model-based recovery and --Q_sampling_recovery run one seed at a time)")

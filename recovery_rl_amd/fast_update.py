@@ -966,6 +966,9 @@ class FastActor:
         self.recovery = torch.zeros(n, dtype=torch.uint8, device=dev)
         self._ride = None
         self.select_for = None          # (task buffer, rows): the next draw's keys are selected in this pass's last forward
+        # SQRL constraint sampling (act_sqrl): Philox seed (the loop sets its own) and the device tick {tick, ticket}
+        self.sqrl_seed = int(getattr(fast.agent, "seed", 0)) & 0xFFFFFFFFFFFFFFFF
+        self.sqrl_tick = torch.zeros(2, dtype=torch.int64, device=dev)
 
     # -- two of the three forwards of act(defer_select=True) as riders of the Q_risk update's launches -----------------------
     def ride_policy(self, obs):
@@ -1058,6 +1061,31 @@ class FastActor:
             return self._deferred(eps_safe, rec_action=self.rec_action)
         return self._gate(eps_safe)
 
+    def act_sqrl(self, obs, eps_safe, k=100, eps=None, u=None, diag=None):
+        """SQRL constraint sampling (SAC._sqrl_action) for the n envs on the fused kernels: the task policy's forward at n rows
+        (its head is the same for an env's k candidates), then ONE rrl_sqrl_act launch -- candidates, twin Q_risk on the
+        n k rows, pick -- that draws on its own Philox streams at this actor's device tick.  -> the persistent task_action
+        buffer.  `eps` [n, k, 2] f32 / `u` [n] f64 inject the draws, `diag` = {name: tensor} asks for the kernel's
+        diagnostic outputs (q, logp, cand, z, pick, cstar, n_safe) -- tests."""
+        f, n = self.f, self.n
+        assert obs.shape == (n, 2) and obs.is_contiguous()
+        self.pending_select = None
+        w2p = f.qrisk.w2_packed()
+        if w2p is None or f.qrisk.H != 256:
+            raise _lib.RRLError("rrl_sqrl_act needs Q_risk at hidden width 256 with its fragment-order W2 copy")
+        f._forwards([(self.pol, obs, dict(save=False))], f.grouped)
+        head, n_part, ps = self.pol.parts
+        p, P, d = _lib.ptr, f.qrisk.p, diag or {}
+        a = _lib.rrl_sqrl_act_t(n=n, k=k, H=f.qrisk.H, d_obs=2, d_act=2, obs=p(obs), head=p(head), n_part=n_part,
+                                part_stride=ps, scale=p(f.scale), bias=p(f.bias), W1=p(P["W1"]), b1=p(P["b1"]), W2p=p(w2p),
+                                b2=p(P["b2"]), W3=p(P["W3"]), b3=p(P["b3"]), eps_safe=float(eps_safe), seed=self.sqrl_seed,
+                                counter=0, counter_dev=p(self.sqrl_tick), counter_inc=1, eps_in=p(eps), u_in=p(u),
+                                action=p(self.task_action), **{name: p(t) for name, t in d.items()})
+        self._sqrl_args = a              # keeps the argument block alive until the launch has been issued (and for profiles/)
+        record("sqrl", a)
+        _lib.check(f.lib.rrl_sqrl_act(C.byref(a), _lib.current_stream()), "rrl_sqrl_act")
+        return self.task_action
+
     def act_gate(self, obs, eps_safe, noise=None):
         """Task action + recovery gate for a controller that acts elsewhere (model-based recovery: MPC.act on the gated rows):
         -> (task action [n,2], recovery u8[n]); persistent buffers."""
@@ -1089,6 +1117,21 @@ BASELINE_FLAGS = ("DGD_constraints", "update_nu", "nu_schedule", "use_constraint
 def fast_baselines_enabled():
     """RRL_FAST_BASELINES=1: the comparison algorithms (LR, RSPO, SQRL, RCPO) take the fused update path too (opt-in)."""
     return os.environ.get("RRL_FAST_BASELINES", "0") == "1"
+
+
+def fast_sqrl_enabled():
+    """RRL_FAST_SQRL=1: SQRL's constraint-sampling acting pass on the rrl_sqrl_act kernel (opt-in; sqrl_acting_path)."""
+    return os.environ.get("RRL_FAST_SQRL", "0") == "1"
+
+
+def sqrl_acting_path(cfg):
+    """Where the training actions of --use_constraint_sampling come from: "hip" (FastActor.act_sqrl) under RRL_FAST_SQRL=1
+    on the fused path (RRL_FAST_BASELINES=1), without a recovery policy, at hidden width 256; else "modules"
+    (SAC._sqrl_action), which evaluation, the one-state call and every other configuration keep."""
+    hip = (fast_sqrl_enabled() and fast_baselines_enabled() and bool(cfg.use_constraint_sampling)
+           and not cfg.use_recovery and int(cfg.hidden_size) == 256 and fast_path_supported(cfg)
+           and not getattr(cfg, "no_fast_path", False) and os.environ.get("RRL_W2_FRAG", "1") != "0")
+    return "hip" if hip else "modules"
 
 
 def uses_baseline_terms(cfg):
