@@ -376,38 +376,56 @@ int rrl_maze_step_push_x(const rrl_step_push_t* a, void* stream);
  * rrl_cem_update : for active envs: elites = the num_elites lowest-cost samples (NaN cost -> 1e6,
  *                  MPC.py:415; ties broken by sample index), mean <- alpha*mean + (1-alpha)*mean(elites),
  *                  var <- alpha*var + (1-alpha)*var(elites)                        (:111-117)
- * pop <= 1024, dim <= 64.
+ * pop <= 1024, dim <= 64.  Missing pointers: RRL_EINVAL (active may be NULL for the update: every problem is updated);
+ * sizes out of range, M * pop > 0xffffffff for the sample: RRL_ERANGE; then num_elites outside 1..pop: RRL_EINVAL;
+ * M == 0: RRL_OK without a launch.  Each entry checks the fields it reads.
  * ------------------------------------------------------------------------------------------ */
-int rrl_cem_sample(int64_t M, int32_t pop, int32_t dim, const double* mean, const double* var,
-                   const double* lb, const double* ub, double epsilon, int sticky, uint8_t* active,
-                   uint64_t seed, uint64_t counter, uint64_t* counter_dev, uint64_t counter_inc,
-                   float* samples, void* stream);
-int rrl_cem_update(int64_t M, int32_t pop, int32_t dim, int32_t num_elites, double alpha,
-                   const float* samples, const float* costs, double* mean, double* var,
-                   const uint8_t* active, void* stream);
+typedef struct {             /* one CEM iteration's two launches on the same buffers */
+    int64_t M;               /* planning problems; with m_dev: the launch bound the buffers are sized for */
+    const int32_t* m_dev;    /* nullable: the live count M = m_dev[0] <= M, read by the kernels (rrl_cem_begin): same Philox
+                              * rows, same bits as the host count; an empty set leaves counter_dev alone */
+    int32_t pop, dim;
+    double *mean, *var;
+    const double *lb, *ub;
+    double epsilon;
+    int sticky;
+    uint8_t* active;
+    uint64_t seed, counter;
+    uint64_t* counter_dev;
+    uint64_t counter_inc;
+    float* samples;
+    int32_t num_elites;      /* update only, like alpha and costs */
+    double alpha;
+    const float* costs;
+} rrl_cem_t;
+int rrl_cem_sample(const rrl_cem_t* c, void* stream);
+int rrl_cem_update(const rrl_cem_t* c, void* stream);
 
-/* The same two steps for a planning set whose size is decided ON THE DEVICE (no host round trip in MPC.act,
- * recovery_rl/MPC.py:322-347; the reference plans for its one env only when Q_risk > eps_safe, experiment.py:568-571):
+/* A planning set whose size is decided ON THE DEVICE (no host round trip in MPC.act, recovery_rl/MPC.py:322-347; the
+ * reference plans for its one env only when Q_risk > eps_safe, experiment.py:568-571): compaction in front of the CEM
+ * iterations (which take count as rrl_cem_t.m_dev), scatter behind them.
  *   rrl_cem_begin   ONE launch: idx[0..count) = rows with mask != 0 in ascending order, count[0] = their number, and the
  *                   planner's inputs of the compacted problems: mean[j] = prev_sol[idx[j]] (prev_sol [n,dim] f64),
  *                   var[j] = init_var [dim], cur_obs[j] = obs[idx[j]] (f32 [n,2]), active[j] = 1      (MPC.py:336-341)
- *   rrl_cem_sample_n / rrl_cem_update_n
- *                   rrl_cem_sample / rrl_cem_update with M = m_dev[0] read by the kernel; m_max >= m_dev[0] bounds the
- *                   launch (buffers are sized for m_max); same Philox rows, same bits as the host-count entries
  *   rrl_cem_finish  action[i, 0..du) = float(mean[j, 0..du)) for i = idx[j], 0 for rows that did not plan;
- *                   prev_sol[i] = mean[j] shifted left by du, zero-filled                              (MPC.py:342-344) */
-int rrl_cem_begin(int64_t n, const uint8_t* mask, int32_t dim, const double* prev_sol, const double* init_var,
-                  const float* obs, int32_t* idx, int32_t* count, double* mean, double* var, float* cur_obs,
-                  uint8_t* active, void* stream);
-int rrl_cem_sample_n(const int32_t* m_dev, int64_t m_max, int32_t pop, int32_t dim, const double* mean,
-                     const double* var, const double* lb, const double* ub, double epsilon, int sticky, uint8_t* active,
-                     uint64_t seed, uint64_t counter, uint64_t* counter_dev, uint64_t counter_inc, float* samples,
-                     void* stream);
-int rrl_cem_update_n(const int32_t* m_dev, int64_t m_max, int32_t pop, int32_t dim, int32_t num_elites, double alpha,
-                     const float* samples, const float* costs, double* mean, double* var, const uint8_t* active,
-                     void* stream);
-int rrl_cem_finish(int64_t n, const uint8_t* mask, int32_t dim, int32_t du, const int32_t* idx, const int32_t* count,
-                   const double* mean, double* prev_sol, float* action, void* stream);
+ *                   prev_sol[i] = mean[j] shifted left by du, zero-filled                              (MPC.py:342-344)
+ * Missing pointers of the fields an entry reads: RRL_EINVAL; n outside 1..2^31-1, dim outside 1..64, du outside 1..dim
+ * (finish): RRL_ERANGE. */
+typedef struct {
+    int64_t n;
+    const uint8_t* mask;
+    int32_t dim, du;         /* du: finish only, like action */
+    double* prev_sol;
+    const double* init_var;  /* begin only, like obs, var, cur_obs, active */
+    const float* obs;
+    int32_t *idx, *count;
+    double *mean, *var;
+    float* cur_obs;
+    uint8_t* active;
+    float* action;
+} rrl_cem_set_t;
+int rrl_cem_begin(const rrl_cem_set_t* s, void* stream);
+int rrl_cem_finish(const rrl_cem_set_t* s, void* stream);
 
 /* --------------------------------------------------------------------------------------------
  * MLP building block.  Replaces the nn.Linear forward/backward of the SAC / Q_risk networks
@@ -444,7 +462,7 @@ int rrl_mlp3_is_split(int M, int H);
  * gradient w.r.t. the stack's output, from.
  *   kind = -1: `out` IS dOut, a plain contiguous tensor; no other field is read.
  *   kind >= 0: dOut is produced in the kernel from the operands named below instead of read from memory, which saves
- *              the stand-alone rrl_*_grad / rrl_*_head_bwd launch in front of every stack backward (same formulas,
+ *              the stand-alone rrl_loss_dout launch in front of every stack backward (same formulas,
  *              bit-identical dOut).  kind selects the formula and the meaning of the fields:
  *   RRL_LOSS_SAC_CRITIC   (G=2,dout=1) out=q, out_t=qt, v0=logp2, v1=r, v2=m, v3=penalty (nullable), alpha,
  *                         f0=gamma; loss[2] = the two MSEs                              (sac.py:192-214)
@@ -607,45 +625,33 @@ int rrl_mlp_backward_pair_multi(int n, const rrl_head_bwd_t* heads, const rrl_hi
  *                            other in ONE launch: a' = pi(s') and pi(s) of one SAC step (sac.py:192-218), the task action
  *                            and the recovery action of the acting pass (experiment.py:546-577).  Every member is validated
  *                            before anything is launched and runs on its own workgroups
- *   rrl_gauss_head_bwd       the backward of GaussianPolicy.sample (recovery_rl/model.py:324-340); head as in the
- *                            RRL_HEAD_GAUSS head; sums d_action over n_heads critic heads (pointer + head_stride, row
- *                            stride ld)
- *   rrl_sac_critic_grad      target r + m gamma (min Q' - alpha log pi') and d(mse1+mse2)/dq
- *                            (recovery_rl/sac.py:192-214); q, qt are [2,B]; loss[2] = the two MSEs
- *   rrl_sac_policy_grad      d mean(alpha log pi - min Q)/dq (sac.py:216-231); loss[1]
- *   rrl_qrisk_critic_grad    target c + m gamma_safe max sigmoid(z') and d(mse1+mse2)/dz on PRE-sigmoid
- *                            outputs (recovery_rl/qrisk.py:118-148)
- *   rrl_qrisk_policy_grad    d mean(max sigmoid(z))/dz (qrisk.py:150-154)
- *   rrl_dgd_qrisk_grad       nu times the same: the Q_risk half of the --DGD_constraints policy loss (sac.py:221-228)
- *   rrl_rcpo_penalty         penalty[b] = lambda[0] max sigmoid(z[.][b]) for rrl_sac_critic_grad's `penalty` (--RCPO,
+ *   rrl_loss_dout            dOut [G,B,dout] of the loss `loss` describes (rrl_loss_t: the formulas and the operand fields of
+ *                            the seven kinds), by the stand-alone kernel of its kind -- the launch a loss description in
+ *                            rrl_head_bwd_t saves, and the reference its fused form is compared against.  RRL_EINVAL: an
+ *                            operand of the kind missing, B <= 0, n_part outside 1..4, n_heads <= 0 or da_parts > 1 (the
+ *                            stand-alone head kernels read a plain d_action) for the head kinds, kind == -1 (nothing to
+ *                            compute); an unknown kind: RRL_ERANGE
+ *   rrl_rcpo_penalty         penalty[b] = lambda[0] max sigmoid(z[.][b]) for RRL_LOSS_SAC_CRITIC's `penalty` (--RCPO,
  *                            sac.py:202-205; lambda read from device memory) and mean[0] = the batch mean of max sigmoid(z)
  *                            (penalty = NULL: the mean only -- the nu step of --update_nu at (s, pi))
- *   rrl_stoch_head_bwd       the backward of StochasticPolicy.sample (model.py:511-525); raw = `head` of RRL_HEAD_STOCH
  *   rrl_recovery_select      recovery gate max sigmoid(z) > eps_safe and action select
  *                            (recovery_rl/experiment.py:546-577)
- * Operands that are stack outputs (head, q, qt, qp, z, zt, zp, raw) take (n_part, part_stride): the value of
+ * Operands that are stack outputs (rrl_loss_t.out / out_t, the penalty's z) take (n_part, part_stride): the value of
  * element i is p[i] + p[part_stride + i] + ... (n_part terms, fixed order) -- the partial last-layer sums of
  * rrl_mlp3_forward(scratch, finalize = 0); n_part = 1 for a plain tensor.
  * ------------------------------------------------------------------------------------------ */
-int rrl_gauss_head_bwd(int B, const float* head, int n_part, long long part_stride, const float* eps,
-                       const float* scale, const float* d_action, int ld, int n_heads, long long head_stride,
-                       float dlogp, float* dhead, void* stream);
-int rrl_sac_critic_grad(int B, const float* q, const float* qt, int n_part, long long part_stride,
-                        const float* logp2, const float* r, const float* m, float gamma, const float* alpha,
-                        const float* penalty, float* dq, float* loss, void* stream);
-int rrl_sac_policy_grad(int B, const float* qp, int n_part, long long part_stride, const float* logp,
-                        const float* alpha, float* dqp, float* loss, void* stream);
-int rrl_qrisk_critic_grad(int B, const float* z, const float* zt, int n_part, long long part_stride,
-                          const float* c, const float* m, float gamma_safe, float* dz, float* loss, void* stream);
-int rrl_qrisk_policy_grad(int B, const float* zp, int n_part, long long part_stride, float* dzp, float* loss,
-                          void* stream);
-int rrl_dgd_qrisk_grad(int B, const float* zp, int n_part, long long part_stride, float nu, float* dzp, float* loss,
-                       void* stream);
-int rrl_rcpo_penalty(int B, const float* z, int n_part, long long part_stride, const float* lambda, float* penalty,
-                     float* mean, void* stream);
-int rrl_stoch_head_bwd(int B, const float* raw, int n_part, long long part_stride, const float* eps,
-                       const float* log_std, float min_log_std, const float* scale, const float* d_action, int ld,
-                       int n_heads, long long head_stride, float* draw, float* dlog_std, void* stream);
+int rrl_loss_dout(const rrl_loss_t* loss, int B, float* dout, void* stream);
+/* The arguments of rrl_rcpo_penalty (one seed's in rrl_rcpo_penalty_packed: same meaning, same checks). */
+typedef struct {
+    int B;
+    const float* z;
+    int n_part;
+    long long part_stride;
+    const float* lambda;  /* read from device memory by the kernel: the dual step of the same iteration writes it */
+    float* penalty;       /* nullable: the mean only */
+    float* mean;
+} rrl_penalty_args_t;
+int rrl_rcpo_penalty(const rrl_penalty_args_t* a, void* stream);
 int rrl_policy_heads_fwd_multi(int n, const rrl_policy_head_t* heads, void* stream);
 /* The optimiser step: torch.optim.Adam over up to RRL_ADAM_MAX_SEGS flat f32 buffers in one launch (e.g. critic + policy
  * of one update; lr, betas and eps of the launch), every segment with its own step counter and optional Polyak target.
@@ -770,30 +776,30 @@ typedef struct {
 int rrl_plan_supported(int hq, int he, int n_nets, int npart, int d_obs, int d_act);
 long long rrl_plan_pack_floats(int hq, int he, int n_nets);
 long long rrl_plan_scratch_floats(int n_nets, long long M, int pop);     /* M * pop * (5 n_nets + 1) */
-int rrl_plan_pack(const rrl_plan_weights_t* w, float* packed, void* stream);
-int rrl_plan_cost(const float* packed, int hq, int he, int n_nets, int npart, long long M, int pop, int plan_hor,
-                  const float* cur_obs, const float* ac_seqs, const float* noise, uint64_t seed, uint64_t counter,
-                  uint64_t* counter_dev, uint64_t counter_inc, float* scratch, float* costs, void* stream);
-
-/* The same evaluation with the three hidden-layer products (Q_risk 256 x 256, ensemble 200 x 200 twice) on the f16 matrix
+/* f16x3 != 0 (opt-in): the three hidden-layer products (Q_risk 256 x 256, ensemble 200 x 200 twice) run on the f16 matrix
  * pipe: every f32 activation and weight is split as hi + lo (two f16 carrying 22 bits of the value) and the product is
  * hi*hi + hi*lo + lo*hi with f32 accumulation -- one v_mfma_f32_16x16x16_f16 (16 cycles) three times instead of four
  * v_mfma_f32_16x16x4_f32 (32 cycles each) per 16-wide k chunk.  Input layers, biases, activations, epilogues and the
- * rollout state stay f32.  Same interface; the packed buffer has the same size but is NOT interchangeable (pack with
- * rrl_plan_pack_f16x3).  Opt-in: results agree with rrl_plan_cost to ~1e-6 relative (tests: the same 2e-4 bound as the
- * f32 kernel against the PyTorch path); values beyond +-65504 in a hidden layer saturate. */
-int rrl_plan_pack_f16x3(const rrl_plan_weights_t* w, float* packed, void* stream);
-int rrl_plan_cost_f16x3(const float* packed, int hq, int he, int n_nets, int npart, long long M, int pop, int plan_hor,
-                        const float* cur_obs, const float* ac_seqs, const float* noise, uint64_t seed, uint64_t counter,
-                        uint64_t* counter_dev, uint64_t counter_inc, float* scratch, float* costs, void* stream);
-
-/* rrl_plan_cost / rrl_plan_cost_f16x3 (f16x3 != 0) for M = m_dev[0] planning problems, M read by the kernel (see
- * rrl_cem_begin); the grid covers m_max problems and workgroups past the live ones exit at once.  cur_obs, ac_seqs,
- * scratch and costs are sized for m_max.  Results for the live problems equal the host-count entries' bit for bit. */
-int rrl_plan_cost_n(int f16x3, const float* packed, int hq, int he, int n_nets, int npart, const int32_t* m_dev,
-                    long long m_max, int pop, int plan_hor, const float* cur_obs, const float* ac_seqs, const float* noise,
-                    uint64_t seed, uint64_t counter, uint64_t* counter_dev, uint64_t counter_inc, float* scratch,
-                    float* costs, void* stream);
+ * rollout state stay f32.  The packed buffer has the same size for both but is NOT interchangeable.  Results agree with
+ * the f32 kernels to ~1e-6 relative (tests: the same 2e-4 bound as the f32 kernel against the PyTorch path); values
+ * beyond +-65504 in a hidden layer saturate. */
+int rrl_plan_pack(const rrl_plan_weights_t* w, int f16x3, float* packed, void* stream);
+typedef struct {
+    const float* packed;
+    int hq, he, n_nets, npart;
+    int f16x3;               /* 0: f32 MFMA kernels, else the hi/lo f16 ones (packed by rrl_plan_pack with the same flag) */
+    long long M;             /* planning problems; with m_dev: the launch bound the buffers are sized for */
+    const int32_t* m_dev;    /* nullable: the live count M = m_dev[0], read by the kernels (rrl_cem_begin); workgroups past
+                              * the live problems exit at once, results for the live ones equal the host count's bit for bit */
+    int pop, plan_hor;
+    const float *cur_obs, *ac_seqs, *noise;
+    uint64_t seed, counter;
+    uint64_t* counter_dev;
+    uint64_t counter_inc;
+    float *scratch, *costs;
+} rrl_plan_cost_t;
+/* Every failed check is RRL_EINVAL, before anything is launched. */
+int rrl_plan_cost(const rrl_plan_cost_t* a, void* stream);
 
 /* --------------------------------------------------------------------------------------------
  * Ensemble fitting.  One optimiser step of MPC.train (recovery_rl/MPC.py:266-292) for the PETS ensemble
@@ -898,16 +904,6 @@ int rrl_maze_step_push_packed(int S, const rrl_step_push_t* a, void* stream);
 int rrl_adam_step_multi_duals_packed(int S, const int* n_seg, const rrl_adam_seg_t* const* segs, const int* n_dual,
                                      const rrl_dual_t* const* duals, const float* lr, float beta1, float beta2, float eps,
                                      void* stream);
-/* One seed's arguments of rrl_rcpo_penalty (same meaning, same checks). */
-typedef struct {
-    int B;
-    const float* z;
-    int n_part;
-    long long part_stride;
-    const float* lambda;  /* read from device memory by the kernel: the dual step of the same iteration writes it */
-    float* penalty;       /* nullable: the mean only */
-    float* mean;
-} rrl_penalty_args_t;
 int rrl_rcpo_penalty_packed(int S, const rrl_penalty_args_t* args, void* stream);
 int rrl_policy_heads_fwd_multi_packed(int S, const int* n, const rrl_policy_head_t* const* heads, void* stream);
 

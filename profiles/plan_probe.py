@@ -40,7 +40,7 @@ def main():
     dt = e0.elapsed_time(e1) * 1e-3 / reps
     row_steps = M * pop * mpc.npart * mpc.plan_hor
     tf = row_steps * FLOPS_PER_ROW_STEP / dt / 1e12
-    print({"M": M, "path": "torch" if use_torch else ("rrl_plan_cost_f16x3" if f16x3 else "rrl_plan_cost"), "ms": dt * 1e3, "row_steps_per_s": row_steps / dt,
+    print({"M": M, "path": "torch" if use_torch else ("rrl_plan_cost f16x3" if f16x3 else "rrl_plan_cost"), "ms": dt * 1e3, "row_steps_per_s": row_steps / dt,
            "tflops": tf, "frac_of_f32_mfma_peak": tf / PEAK_TF})
 
 

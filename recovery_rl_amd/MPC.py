@@ -120,7 +120,7 @@ class MPC:
         self._trainer = None
         self.fused = None                  # FusedPlanner (rrl_plan_cost) when the shapes allow it
         self.device_count = True           # act(obs, t, mask): planning-set size stays on the device (no host sync)
-        self._plan_ws = self._plan_out = self.last_count = None
+        self._plan_ws = self.last_count = None
         self.use_fused_planner = True
         if plan_precision not in (None, "f32", "f16x3"):
             raise ValueError("--plan_precision must be 'f32' or 'f16x3'")
@@ -287,7 +287,7 @@ class MPC:
 
     def _act_device_count(self, obs, mask):
         """act() for a recovery mask without reading the number of planning envs on the host: the mask is compacted on
-        the device (rrl_cem_begin), every kernel of the CEM reads the count from device memory and is launched for the
+        the device (rrl_cem_begin), every kernel of the CEM reads the count from device memory (m_dev) and is launched for the
         upper bound n (workgroups past the live problems exit at once), rrl_cem_finish scatters the actions and the
         shifted solutions.  Same index order, Philox rows and arithmetic as the host-count path."""
         from .optimizers import PlanWorkspace
@@ -295,22 +295,18 @@ class MPC:
         n, dim = obs.shape[0], self.plan_hor * self.dU
         ws = self._plan_ws
         if ws is None or ws.m_max != n:
-            ws = self._plan_ws = PlanWorkspace(n, self.optimizer.popsize, dim, self.device)
-            self._plan_out = torch.zeros(n, self.dU, dtype=torch.float32, device=self.device)
+            ws = self._plan_ws = PlanWorkspace(n, self.optimizer.popsize, dim, self.per * self.dU, self.init_var, self.device)
         mask_u8 = mask if mask.dtype == torch.uint8 else mask.to(torch.uint8)
         obs = obs.to(torch.float32).contiguous()
         lib, st = _lib.load(), _lib.current_stream()
-        p = _lib.ptr
-        _lib.check(lib.rrl_cem_begin(n, p(mask_u8), dim, p(self.prev_sol), p(self.init_var), p(obs), p(ws.idx),
-                                     p(ws.count), p(ws.mean), p(ws.var), p(ws.cur_obs), p(ws.active), st),
-                   "rrl_cem_begin")
+        ws.set.mask, ws.set.obs, ws.set.prev_sol = _lib.ptr(mask_u8), _lib.ptr(obs), _lib.ptr(self.prev_sol)
+        _lib.check(lib.rrl_cem_begin(ws.set, st), "rrl_cem_begin")
         self.fused.pack()                  # weights moved since the last call (Q_risk update / re-fit)
         with trace_range("cem"):
             self.optimizer.obtain_solution_n(ws, ws.count)
-        _lib.check(lib.rrl_cem_finish(n, p(mask_u8), dim, self.per * self.dU, p(ws.idx), p(ws.count), p(ws.mean),
-                                      p(self.prev_sol), p(self._plan_out), st), "rrl_cem_finish")
+        _lib.check(lib.rrl_cem_finish(ws.set, st), "rrl_cem_finish")
         self.last_count = ws.count         # device-side size of the planning set of this call (int32[1])
-        return self._plan_out
+        return ws.action
 
     # -- candidate evaluation (MPC.py:374-416) -------------------------------------------------
     @torch.no_grad()

@@ -42,16 +42,13 @@ EXPORTS = [
     "rrl_mlp_hidden_backward_multi_packed", "rrl_mlp_backward_pair_multi_packed", "rrl_adam_step_multi_packed", "rrl_nav_step_push_packed",
     "rrl_maze_step_push_packed",
     "rrl_adam_step_multi_duals_packed", "rrl_rcpo_penalty_packed", "rrl_policy_heads_fwd_multi_packed",
-    "rrl_cem_sample", "rrl_cem_update", "rrl_cem_begin", "rrl_cem_sample_n", "rrl_cem_update_n", "rrl_cem_finish",
+    "rrl_cem_sample", "rrl_cem_update", "rrl_cem_begin", "rrl_cem_finish",
     "rrl_gemm_f32", "rrl_mlp3_forward", "rrl_mlp3_is_split",
     "rrl_mlp3_forward_multi", "rrl_mlp_head_backward_multi", "rrl_mlp_hidden_backward_multi",
     "rrl_mlp_input_backward_multi", "rrl_mlp_backward_pair_multi", "rrl_policy_heads_fwd_multi",
-    "rrl_gauss_head_bwd", "rrl_sac_critic_grad", "rrl_sac_policy_grad",
-    "rrl_qrisk_critic_grad", "rrl_qrisk_policy_grad", "rrl_stoch_head_bwd",
-    "rrl_dgd_qrisk_grad", "rrl_rcpo_penalty", "rrl_adam_step_multi_duals",
+    "rrl_loss_dout", "rrl_rcpo_penalty", "rrl_adam_step_multi_duals",
     "rrl_adam_step_multi", "rrl_w2_pack", "rrl_normal_fill", "rrl_recovery_select", "rrl_episode_log_append",
-    "rrl_plan_supported", "rrl_plan_pack_floats", "rrl_plan_scratch_floats", "rrl_plan_pack", "rrl_plan_cost", "rrl_plan_pack_f16x3",
-    "rrl_plan_cost_f16x3", "rrl_plan_cost_n",
+    "rrl_plan_supported", "rrl_plan_pack_floats", "rrl_plan_scratch_floats", "rrl_plan_pack", "rrl_plan_cost",
     "rrl_ens_train_supported", "rrl_ens_scratch_floats", "rrl_ens_train_grad", "rrl_ens_train_epoch",
     "rrl_ens_train_big_supported", "rrl_ens_big_scratch_floats", "rrl_ens_train_grad_big", "rrl_ens_train_epoch_big",
     "rrl_sqrl_scratch_floats", "rrl_sqrl_act",
@@ -268,6 +265,26 @@ class rrl_plan_weights_t(C.Structure):
                                         "max_logvar", "min_logvar")]
 
 
+class rrl_plan_cost_t(C.Structure):
+    _fields_ = [("packed", C.c_void_p)] + [(n, C.c_int) for n in ("hq", "he", "n_nets", "npart", "f16x3")] + [
+        ("M", C.c_longlong), ("m_dev", C.c_void_p), ("pop", C.c_int), ("plan_hor", C.c_int), ("cur_obs", C.c_void_p),
+        ("ac_seqs", C.c_void_p), ("noise", C.c_void_p), ("seed", C.c_uint64), ("counter", C.c_uint64),
+        ("counter_dev", C.c_void_p), ("counter_inc", C.c_uint64), ("scratch", C.c_void_p), ("costs", C.c_void_p)]
+
+
+class rrl_cem_t(C.Structure):
+    _fields_ = [("M", C.c_int64), ("m_dev", C.c_void_p), ("pop", C.c_int32), ("dim", C.c_int32), ("mean", C.c_void_p),
+                ("var", C.c_void_p), ("lb", C.c_void_p), ("ub", C.c_void_p), ("epsilon", C.c_double), ("sticky", C.c_int),
+                ("active", C.c_void_p), ("seed", C.c_uint64), ("counter", C.c_uint64), ("counter_dev", C.c_void_p),
+                ("counter_inc", C.c_uint64), ("samples", C.c_void_p), ("num_elites", C.c_int32), ("alpha", C.c_double),
+                ("costs", C.c_void_p)]
+
+
+class rrl_cem_set_t(C.Structure):
+    _fields_ = [("n", C.c_int64), ("mask", C.c_void_p), ("dim", C.c_int32), ("du", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("prev_sol", "init_var", "obs", "idx", "count", "mean", "var", "cur_obs", "active", "action")]
+
+
 STREAM_SQRL, STREAM_SQRL_PICK = 9, 10
 
 
@@ -328,26 +345,18 @@ def _declare(lib):
         "rrl_maze_step_push_packed": (ci, [ci, C.POINTER(rrl_step_push_t), vp]),
         "rrl_nav_step_push_x": (ci, [ci, C.POINTER(rrl_step_push_t), vp]),
         "rrl_maze_step_push_x": (ci, [C.POINTER(rrl_step_push_t), vp]),
-        "rrl_cem_sample": (ci, [i64, i32, i32, vp, vp, vp, vp, f64, ci, vp, u64, u64, vp, u64, vp, vp]),
-        "rrl_cem_update": (ci, [i64, i32, i32, i32, f64, vp, vp, vp, vp, vp, vp]),
-        "rrl_cem_begin": (ci, [i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "rrl_cem_sample_n": (ci, [vp, i64, i32, i32, vp, vp, vp, vp, f64, ci, vp, u64, u64, vp, u64, vp, vp]),
-        "rrl_cem_update_n": (ci, [vp, i64, i32, i32, i32, f64, vp, vp, vp, vp, vp, vp]),
-        "rrl_cem_finish": (ci, [i64, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "rrl_cem_sample": (ci, [C.POINTER(rrl_cem_t), vp]),
+        "rrl_cem_update": (ci, [C.POINTER(rrl_cem_t), vp]),
+        "rrl_cem_begin": (ci, [C.POINTER(rrl_cem_set_t), vp]),
+        "rrl_cem_finish": (ci, [C.POINTER(rrl_cem_set_t), vp]),
         "rrl_gemm_f32": (ci, [ci, ci, ci, ci, ci, vp, ci, C.c_longlong, vp, ci, C.c_longlong, vp, ci,
                               C.c_longlong, vp, C.c_longlong, ci, vp, ci, C.c_longlong, vp, C.c_longlong,
                               ci, vp]),
         "rrl_mlp3_forward": (ci, [ci, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]),
         "rrl_mlp3_is_split": (ci, [ci, ci]),
-        "rrl_gauss_head_bwd": (ci, [ci, vp, ci, ll, vp, vp, vp, ci, ci, ll, f32, vp, vp]),
-        "rrl_sac_critic_grad": (ci, [ci, vp, vp, ci, ll, vp, vp, vp, f32, vp, vp, vp, vp, vp]),
-        "rrl_sac_policy_grad": (ci, [ci, vp, ci, ll, vp, vp, vp, vp, vp]),
-        "rrl_qrisk_critic_grad": (ci, [ci, vp, vp, ci, ll, vp, vp, f32, vp, vp, vp]),
-        "rrl_qrisk_policy_grad": (ci, [ci, vp, ci, ll, vp, vp, vp]),
-        "rrl_dgd_qrisk_grad": (ci, [ci, vp, ci, ll, f32, vp, vp, vp]),
-        "rrl_rcpo_penalty": (ci, [ci, vp, ci, ll, vp, vp, vp, vp]),
+        "rrl_loss_dout": (ci, [C.POINTER(rrl_loss_t), ci, vp, vp]),
+        "rrl_rcpo_penalty": (ci, [C.POINTER(rrl_penalty_args_t), vp]),
         "rrl_adam_step_multi_duals": (ci, [ci, C.POINTER(rrl_adam_seg_t), ci, C.POINTER(rrl_dual_t), f32, f32, f32, f32, vp]),
-        "rrl_stoch_head_bwd": (ci, [ci, vp, ci, ll, vp, vp, f32, vp, vp, ci, ci, ll, vp, vp, vp]),
         "rrl_adam_step_multi": (ci, [ci, C.POINTER(rrl_adam_seg_t), f32, f32, f32, f32, vp]),
         "rrl_w2_pack": (ci, [ci, ci, vp, vp, vp]),
         "rrl_normal_fill": (ci, [ll, u64, u64, vp, u64, vp, vp]),
@@ -355,11 +364,8 @@ def _declare(lib):
         "rrl_plan_supported": (ci, [ci, ci, ci, ci, ci, ci]),
         "rrl_plan_pack_floats": (ll, [ci, ci, ci]),
         "rrl_plan_scratch_floats": (ll, [ci, ll, ci]),
-        "rrl_plan_pack": (ci, [C.POINTER(rrl_plan_weights_t), vp, vp]),
-        "rrl_plan_cost": (ci, [vp, ci, ci, ci, ci, ll, ci, ci, vp, vp, vp, u64, u64, vp, u64, vp, vp, vp]),
-        "rrl_plan_pack_f16x3": (ci, [C.POINTER(rrl_plan_weights_t), vp, vp]),
-        "rrl_plan_cost_f16x3": (ci, [vp, ci, ci, ci, ci, ll, ci, ci, vp, vp, vp, u64, u64, vp, u64, vp, vp, vp]),
-        "rrl_plan_cost_n": (ci, [ci, vp, ci, ci, ci, ci, vp, ll, ci, ci, vp, vp, vp, u64, u64, vp, u64, vp, vp, vp]),
+        "rrl_plan_pack": (ci, [C.POINTER(rrl_plan_weights_t), ci, vp, vp]),
+        "rrl_plan_cost": (ci, [C.POINTER(rrl_plan_cost_t), vp]),
         "rrl_ens_train_supported": (ci, [ci, ci, ci, ci]),
         "rrl_ens_scratch_floats": (ll, [ci]),
         "rrl_ens_train_epoch": (ci, [C.POINTER(rrl_ens_t), ci, C.POINTER(rrl_adam_seg_t), f32, f32, f32, f32, vp, vp,

@@ -195,82 +195,51 @@ __global__ __launch_bounds__(kBlock) void cem_finish_kernel(int64_t n, const uin
 
 extern "C" {
 
-static int cem_sample_impl(int64_t M, int32_t pop, int32_t dim, const double* mean, const double* var,
-                           const double* lb, const double* ub, double epsilon, int sticky, uint8_t* active,
-                           uint64_t seed, uint64_t counter, uint64_t* counter_dev, uint64_t counter_inc,
-                           float* samples, const int32_t* m_dev, void* stream) {
-    if (!mean || !var || !lb || !ub || !active || !samples) return RRL_EINVAL;
+int rrl_cem_sample(const rrl_cem_t* c, void* stream) {
+    if (!c || !c->mean || !c->var || !c->lb || !c->ub || !c->active || !c->samples) return RRL_EINVAL;
+    const int64_t M = c->M;
+    const int32_t pop = c->pop, dim = c->dim;
     if (M < 0 || pop <= 0 || pop > 1024 || dim <= 0 || dim > 64) return RRL_ERANGE;
     if (M * pop > 0xffffffffLL) return RRL_ERANGE;
     if (M == 0) return RRL_OK;
     hipLaunchKernelGGL(cem_sample_kernel, dim3(grid_for(M * pop * dim)), dim3(kBlock), 0,
-                       (hipStream_t)stream, M, pop, dim, mean, var, lb, ub, epsilon, sticky, active, seed,
-                       counter, counter_dev, counter_inc, samples, m_dev);
+                       (hipStream_t)stream, M, pop, dim, c->mean, c->var, c->lb, c->ub, c->epsilon, c->sticky,
+                       c->active, c->seed, c->counter, c->counter_dev, c->counter_inc, c->samples, c->m_dev);
     return check_launch();
 }
 
-static int cem_update_impl(int64_t M, int32_t pop, int32_t dim, int32_t num_elites, double alpha,
-                           const float* samples, const float* costs, double* mean, double* var,
-                           const uint8_t* active, const int32_t* m_dev, void* stream) {
-    if (!samples || !costs || !mean || !var) return RRL_EINVAL;
+int rrl_cem_update(const rrl_cem_t* c, void* stream) {
+    if (!c || !c->samples || !c->costs || !c->mean || !c->var) return RRL_EINVAL;
+    const int64_t M = c->M;
+    const int32_t pop = c->pop, dim = c->dim;
     if (M < 0 || pop <= 0 || pop > 1024 || dim <= 0 || dim > 64) return RRL_ERANGE;
-    if (num_elites <= 0 || num_elites > pop) return RRL_EINVAL;   // optimizers.py:66-68 raises ValueError
+    if (c->num_elites <= 0 || c->num_elites > pop) return RRL_EINVAL;   // optimizers.py:66-68 raises ValueError
     if (M == 0) return RRL_OK;
     int padded = 1;
     while (padded < pop) padded <<= 1;
     hipLaunchKernelGGL(cem_update_kernel, dim3((unsigned)M), dim3(kBlock), size_t(padded) * 8,
-                       (hipStream_t)stream, pop, dim, num_elites, padded, alpha, samples, costs, mean, var,
-                       active, m_dev);
+                       (hipStream_t)stream, pop, dim, c->num_elites, padded, c->alpha, c->samples, c->costs, c->mean,
+                       c->var, c->active, c->m_dev);
     return check_launch();
 }
 
-int rrl_cem_sample(int64_t M, int32_t pop, int32_t dim, const double* mean, const double* var,
-                   const double* lb, const double* ub, double epsilon, int sticky, uint8_t* active,
-                   uint64_t seed, uint64_t counter, uint64_t* counter_dev, uint64_t counter_inc,
-                   float* samples, void* stream) {
-    return cem_sample_impl(M, pop, dim, mean, var, lb, ub, epsilon, sticky, active, seed, counter, counter_dev,
-                           counter_inc, samples, nullptr, stream);
-}
-
-int rrl_cem_update(int64_t M, int32_t pop, int32_t dim, int32_t num_elites, double alpha,
-                   const float* samples, const float* costs, double* mean, double* var,
-                   const uint8_t* active, void* stream) {
-    return cem_update_impl(M, pop, dim, num_elites, alpha, samples, costs, mean, var, active, nullptr, stream);
-}
-
-int rrl_cem_sample_n(const int32_t* m_dev, int64_t m_max, int32_t pop, int32_t dim, const double* mean,
-                     const double* var, const double* lb, const double* ub, double epsilon, int sticky, uint8_t* active,
-                     uint64_t seed, uint64_t counter, uint64_t* counter_dev, uint64_t counter_inc, float* samples,
-                     void* stream) {
-    if (!m_dev) return RRL_EINVAL;
-    return cem_sample_impl(m_max, pop, dim, mean, var, lb, ub, epsilon, sticky, active, seed, counter, counter_dev,
-                           counter_inc, samples, m_dev, stream);
-}
-
-int rrl_cem_update_n(const int32_t* m_dev, int64_t m_max, int32_t pop, int32_t dim, int32_t num_elites, double alpha,
-                     const float* samples, const float* costs, double* mean, double* var, const uint8_t* active,
-                     void* stream) {
-    if (!m_dev) return RRL_EINVAL;
-    return cem_update_impl(m_max, pop, dim, num_elites, alpha, samples, costs, mean, var, active, m_dev, stream);
-}
-
-int rrl_cem_begin(int64_t n, const uint8_t* mask, int32_t dim, const double* prev_sol, const double* init_var,
-                  const float* obs, int32_t* idx, int32_t* count, double* mean, double* var, float* cur_obs,
-                  uint8_t* active, void* stream) {
-    if (!mask || !prev_sol || !init_var || !obs || !idx || !count || !mean || !var || !cur_obs || !active)
+int rrl_cem_begin(const rrl_cem_set_t* s, void* stream) {
+    if (!s || !s->mask || !s->prev_sol || !s->init_var || !s->obs || !s->idx || !s->count || !s->mean || !s->var ||
+        !s->cur_obs || !s->active)
         return RRL_EINVAL;
-    if (n <= 0 || n > 0x7fffffffLL || dim <= 0 || dim > 64) return RRL_ERANGE;
-    hipLaunchKernelGGL(cem_begin_kernel, dim3(1), dim3(kBeginBlock), 0, (hipStream_t)stream, n, mask, dim, prev_sol,
-                       init_var, (const float2*)obs, idx, count, mean, var, (float2*)cur_obs, active);
+    if (s->n <= 0 || s->n > 0x7fffffffLL || s->dim <= 0 || s->dim > 64) return RRL_ERANGE;
+    hipLaunchKernelGGL(cem_begin_kernel, dim3(1), dim3(kBeginBlock), 0, (hipStream_t)stream, s->n, s->mask, s->dim,
+                       s->prev_sol, s->init_var, (const float2*)s->obs, s->idx, s->count, s->mean, s->var,
+                       (float2*)s->cur_obs, s->active);
     return check_launch();
 }
 
-int rrl_cem_finish(int64_t n, const uint8_t* mask, int32_t dim, int32_t du, const int32_t* idx, const int32_t* count,
-                   const double* mean, double* prev_sol, float* action, void* stream) {
-    if (!mask || !idx || !count || !mean || !prev_sol || !action) return RRL_EINVAL;
-    if (n <= 0 || n > 0x7fffffffLL || dim <= 0 || dim > 64 || du <= 0 || du > dim) return RRL_ERANGE;
-    hipLaunchKernelGGL(cem_finish_kernel, dim3(grid_for(n * dim)), dim3(kBlock), 0, (hipStream_t)stream, n, mask, dim,
-                       du, idx, count, mean, prev_sol, action);
+int rrl_cem_finish(const rrl_cem_set_t* s, void* stream) {
+    if (!s || !s->mask || !s->idx || !s->count || !s->mean || !s->prev_sol || !s->action) return RRL_EINVAL;
+    if (s->n <= 0 || s->n > 0x7fffffffLL || s->dim <= 0 || s->dim > 64 || s->du <= 0 || s->du > s->dim)
+        return RRL_ERANGE;
+    hipLaunchKernelGGL(cem_finish_kernel, dim3(grid_for(s->n * s->dim)), dim3(kBlock), 0, (hipStream_t)stream, s->n,
+                       s->mask, s->dim, s->du, s->idx, s->count, s->mean, s->prev_sol, s->action);
     return check_launch();
 }
 

@@ -874,7 +874,7 @@ int rrl_pack_clear(void) { return rrl_pack::clear(); }
 // 5: the positional forms of the fused env step (plain and with the recovery gate) are gone: rrl_step_push_t is its one form;
 // 6: likewise the stack backward and the optimiser step (rrl_*_bwd_t, rrl_adam_seg_t); 7: the replay draws and the policy-head
 // forwards (rrl_draw_t through rrl_sample_multi, rrl_policy_head_t through rrl_policy_heads_fwd_multi)
-int rrl_abi_version(void) { return 7; }
+int rrl_abi_version(void) { return 8; }
 
 int rrl_last_hip_error(void) { return rrl_host::last_hip_error; }
 

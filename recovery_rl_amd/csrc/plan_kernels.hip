@@ -763,7 +763,7 @@ int rrl_plan_supported(int hq, int he, int n_nets, int npart, int d_obs, int d_a
            d_act == 2;
 }
 
-static int plan_pack_impl(const rrl_plan_weights_t* w, float* packed, void* stream_, bool f16x3) {
+int rrl_plan_pack(const rrl_plan_weights_t* w, int f16x3, float* packed, void* stream_) {
     if (!w || !packed || !rrl_plan_supported(w->hq, w->he, w->n_nets, 4 * w->n_nets, 2, 2)) return RRL_EINVAL;
     hipStream_t st = (hipStream_t)stream_;
     const dim3 b(kBlock);
@@ -806,25 +806,21 @@ static int plan_pack_impl(const rrl_plan_weights_t* w, float* packed, void* stre
     return check_launch();
 }
 
-int rrl_plan_pack(const rrl_plan_weights_t* w, float* packed, void* stream) {
-    return plan_pack_impl(w, packed, stream, false);
-}
-
-int rrl_plan_pack_f16x3(const rrl_plan_weights_t* w, float* packed, void* stream) {
-    return plan_pack_impl(w, packed, stream, true);
-}
-
 long long rrl_plan_scratch_floats(int n_nets, long long M, int pop) {
     if (n_nets <= 0 || M <= 0 || pop <= 0) return RRL_EINVAL;
     return M * pop * (5LL * n_nets + 1);
 }
 
-static int plan_cost_impl(bool f16x3, const float* packed, int hq, int he, int n_nets, int npart, long long M, int pop,
-                          int plan_hor, const float* cur_obs, const float* ac_seqs, const float* noise, uint64_t seed,
-                          uint64_t counter, uint64_t* counter_dev, uint64_t counter_inc, float* scratch, float* costs,
-                          void* stream_, const int32_t* m_dev = nullptr) {
-    if (!packed || !cur_obs || !ac_seqs || !scratch || !costs || M <= 0 || pop <= 0 || plan_hor <= 0 ||
-        plan_hor > 16 || !rrl_plan_supported(hq, he, n_nets, npart, 2, 2))
+int rrl_plan_cost(const rrl_plan_cost_t* a, void* stream_) {
+    if (!a) return RRL_EINVAL;
+    const float *packed = a->packed, *cur_obs = a->cur_obs, *ac_seqs = a->ac_seqs, *noise = a->noise;
+    const int n_nets = a->n_nets, npart = a->npart, pop = a->pop, plan_hor = a->plan_hor;
+    const long long M = a->M;
+    const int32_t* m_dev = a->m_dev;
+    uint64_t* counter_dev = a->counter_dev;
+    float* costs = a->costs;
+    if (!packed || !cur_obs || !ac_seqs || !a->scratch || !costs || M <= 0 || pop <= 0 || plan_hor <= 0 ||
+        plan_hor > 16 || !rrl_plan_supported(a->hq, a->he, n_nets, npart, 2, 2))
         return RRL_EINVAL;
     const long long n_groups = M * pop;
     if (n_groups * npart >= (1LL << 32)) return RRL_EINVAL;      // Philox row index is 32 bits
@@ -832,7 +828,7 @@ static int plan_cost_impl(bool f16x3, const float* packed, int hq, int he, int n
     const long long first_tiles = ((n_groups + kRows - 1) / kRows) * (n_nets + 1);
     if (tiles >= (1LL << 31)) return RRL_EINVAL;
     // scratch (rrl_plan_scratch_floats): e0 [n_groups][n_nets][4] | partial [n_groups][n_nets] | q0 [n_groups]
-    float* e0 = scratch;
+    float* e0 = a->scratch;
     float* partial = e0 + n_groups * n_nets * 4;
     float* q0 = partial + n_groups * n_nets;
     hipStream_t st = (hipStream_t)stream_;
@@ -847,45 +843,22 @@ static int plan_cost_impl(bool f16x3, const float* packed, int hq, int he, int n
             }
         lds_set = true;
     }
-    if (f16x3) {
+    if (a->f16x3) {
         hipLaunchKernelGGL(plan_first_step_kernel<true>, dim3((unsigned)first_tiles), dim3(kThreads), kLdsBytes, st, packed,
                            n_nets, n_groups, pop, plan_hor, cur_obs, ac_seqs, q0, e0, m_dev);
         hipLaunchKernelGGL(plan_cost_kernel<true>, dim3((unsigned)tiles), dim3(kThreads), kLdsBytes, st, packed, n_nets,
-                           npart, n_groups, pop, plan_hor, cur_obs, ac_seqs, noise, seed, counter, counter_dev, q0, e0,
-                           partial, m_dev);
+                           npart, n_groups, pop, plan_hor, cur_obs, ac_seqs, noise, a->seed, a->counter, counter_dev, q0,
+                           e0, partial, m_dev);
     } else {
         hipLaunchKernelGGL(plan_first_step_kernel<false>, dim3((unsigned)first_tiles), dim3(kThreads), kLdsBytes, st, packed,
                            n_nets, n_groups, pop, plan_hor, cur_obs, ac_seqs, q0, e0, m_dev);
         hipLaunchKernelGGL(plan_cost_kernel<false>, dim3((unsigned)tiles), dim3(kThreads), kLdsBytes, st, packed, n_nets,
-                           npart, n_groups, pop, plan_hor, cur_obs, ac_seqs, noise, seed, counter, counter_dev, q0, e0,
-                           partial, m_dev);
+                           npart, n_groups, pop, plan_hor, cur_obs, ac_seqs, noise, a->seed, a->counter, counter_dev, q0,
+                           e0, partial, m_dev);
     }
     hipLaunchKernelGGL(plan_finish_kernel, dim3(grid_for(n_groups)), dim3(kBlock), 0, st, n_groups, n_nets, npart,
-                       partial, costs, counter_dev, counter_inc, m_dev, pop);
+                       partial, costs, counter_dev, a->counter_inc, m_dev, pop);
     return check_launch();
-}
-
-int rrl_plan_cost(const float* packed, int hq, int he, int n_nets, int npart, long long M, int pop, int plan_hor,
-                  const float* cur_obs, const float* ac_seqs, const float* noise, uint64_t seed, uint64_t counter,
-                  uint64_t* counter_dev, uint64_t counter_inc, float* scratch, float* costs, void* stream) {
-    return plan_cost_impl(false, packed, hq, he, n_nets, npart, M, pop, plan_hor, cur_obs, ac_seqs, noise, seed, counter,
-                          counter_dev, counter_inc, scratch, costs, stream);
-}
-
-int rrl_plan_cost_f16x3(const float* packed, int hq, int he, int n_nets, int npart, long long M, int pop, int plan_hor,
-                        const float* cur_obs, const float* ac_seqs, const float* noise, uint64_t seed, uint64_t counter,
-                        uint64_t* counter_dev, uint64_t counter_inc, float* scratch, float* costs, void* stream) {
-    return plan_cost_impl(true, packed, hq, he, n_nets, npart, M, pop, plan_hor, cur_obs, ac_seqs, noise, seed, counter,
-                          counter_dev, counter_inc, scratch, costs, stream);
-}
-
-int rrl_plan_cost_n(int f16x3, const float* packed, int hq, int he, int n_nets, int npart, const int32_t* m_dev,
-                    long long m_max, int pop, int plan_hor, const float* cur_obs, const float* ac_seqs, const float* noise,
-                    uint64_t seed, uint64_t counter, uint64_t* counter_dev, uint64_t counter_inc, float* scratch,
-                    float* costs, void* stream) {
-    if (!m_dev) return RRL_EINVAL;
-    return plan_cost_impl(f16x3 != 0, packed, hq, he, n_nets, npart, m_max, pop, plan_hor, cur_obs, ac_seqs, noise, seed,
-                          counter, counter_dev, counter_inc, scratch, costs, stream, m_dev);
 }
 
 }  // extern "C"

@@ -771,75 +771,66 @@ int rrl_policy_heads_fwd_multi_packed(int S, const int* n, const rrl_policy_head
     return check_launch();
 }
 
-int rrl_gauss_head_bwd(int B, const float* head, int n_part, long long part_stride, const float* eps,
-                       const float* scale, const float* d_action, int ld, int n_heads, long long head_stride,
-                       float dlogp, float* dhead, void* stream) {
-    if (!head || !eps || !scale || !d_action || !dhead || B <= 0 || n_heads <= 0 || n_part <= 0 || n_part > 4) return RRL_EINVAL;
-    hipLaunchKernelGGL(gauss_head_bwd_kernel, rows_grid(B), dim3(kBlock), 0, (hipStream_t)stream, B, head, n_part,
-                       part_stride, eps, scale, d_action, ld, n_heads, head_stride, dlogp, dhead);
+int rrl_loss_dout(const rrl_loss_t* loss, int B, float* dout, void* stream) {
+    if (!loss) return RRL_EINVAL;
+    const rrl_loss_t& L = *loss;
+    if (L.kind == -1) return RRL_EINVAL;        // `out` already is dOut: nothing to compute
+    if (L.kind < RRL_LOSS_SAC_CRITIC || L.kind > RRL_LOSS_DGD_QRISK) return RRL_ERANGE;
+    if (!L.out || !dout || B <= 0 || L.n_part <= 0 || L.n_part > 4) return RRL_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    switch (L.kind) {
+    case RRL_LOSS_SAC_CRITIC:
+        if (!L.out_t || !L.v0 || !L.v1 || !L.v2 || !L.alpha) return RRL_EINVAL;
+        hipLaunchKernelGGL(sac_critic_grad_kernel, dim3(1), dim3(kBlock), 0, st, B, L.out, L.out_t, L.n_part,
+                           L.part_stride, L.v0, L.v1, L.v2, L.f0, L.alpha, L.v3, dout, L.loss);
+        break;
+    case RRL_LOSS_SAC_POLICY:
+        if (!L.v0 || !L.alpha) return RRL_EINVAL;
+        hipLaunchKernelGGL(sac_policy_grad_kernel, dim3(1), dim3(kBlock), 0, st, B, L.out, L.n_part, L.part_stride, L.v0,
+                           L.alpha, dout, L.loss);
+        break;
+    case RRL_LOSS_QRISK_CRITIC:
+        if (!L.out_t || !L.v0 || !L.v1) return RRL_EINVAL;
+        hipLaunchKernelGGL(qrisk_critic_grad_kernel, dim3(1), dim3(kBlock), 0, st, B, L.out, L.out_t, L.n_part,
+                           L.part_stride, L.v0, L.v1, L.f0, dout, L.loss);
+        break;
+    case RRL_LOSS_QRISK_POLICY:
+    case RRL_LOSS_DGD_QRISK:
+        hipLaunchKernelGGL(qrisk_policy_grad_kernel, dim3(1), dim3(kBlock), 0, st, B, L.out, L.n_part, L.part_stride,
+                           L.kind == RRL_LOSS_DGD_QRISK ? L.f0 : 1.f, dout, L.loss);
+        break;
+    case RRL_LOSS_GAUSS_HEAD:
+        // the stand-alone head kernels read d_action as a plain tensor, not as partials
+        if (!L.v0 || !L.v1 || !L.d_action || L.n_heads <= 0 || L.da_parts > 1) return RRL_EINVAL;
+        hipLaunchKernelGGL(gauss_head_bwd_kernel, rows_grid(B), dim3(kBlock), 0, st, B, L.out, L.n_part, L.part_stride,
+                           L.v0, L.v1, L.d_action, L.ld, L.n_heads, L.head_stride, L.f0, dout);
+        break;
+    default:  // RRL_LOSS_STOCH_HEAD
+        if (!L.v0 || !L.v1 || !L.v2 || !L.d_action || !L.loss || L.n_heads <= 0 || L.da_parts > 1) return RRL_EINVAL;
+        hipLaunchKernelGGL(stoch_head_bwd_kernel, dim3(1), dim3(kBlock), 0, st, B, L.out, L.n_part, L.part_stride, L.v0,
+                           L.v1, L.f0, L.v2, L.d_action, L.ld, L.n_heads, L.head_stride, dout, L.loss);
+        break;
+    }
     return check_launch();
 }
 
-int rrl_sac_critic_grad(int B, const float* q, const float* qt, int n_part, long long part_stride,
-                        const float* logp2, const float* r, const float* m, float gamma, const float* alpha,
-                        const float* penalty, float* dq, float* loss, void* stream) {
-    if (!q || !qt || !logp2 || !r || !m || !alpha || !dq || B <= 0 || n_part <= 0 || n_part > 4) return RRL_EINVAL;
-    hipLaunchKernelGGL(sac_critic_grad_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, B, q, qt, n_part,
-                       part_stride, logp2, r, m, gamma, alpha, penalty, dq, loss);
-    return check_launch();
+static bool penalty_args_ok(const rrl_penalty_args_t& a) {
+    return a.z && (!a.penalty || a.lambda) && (a.penalty || a.mean) && a.B > 0 && a.n_part > 0 && a.n_part <= 4;
 }
 
-int rrl_sac_policy_grad(int B, const float* qp, int n_part, long long part_stride, const float* logp,
-                        const float* alpha, float* dqp, float* loss, void* stream) {
-    if (!qp || !logp || !alpha || !dqp || B <= 0 || n_part <= 0 || n_part > 4) return RRL_EINVAL;
-    hipLaunchKernelGGL(sac_policy_grad_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, B, qp, n_part,
-                       part_stride, logp, alpha, dqp, loss);
-    return check_launch();
-}
-
-int rrl_qrisk_critic_grad(int B, const float* z, const float* zt, int n_part, long long part_stride,
-                          const float* c, const float* m, float gamma_safe, float* dz, float* loss, void* stream) {
-    if (!z || !zt || !c || !m || !dz || B <= 0 || n_part <= 0 || n_part > 4) return RRL_EINVAL;
-    hipLaunchKernelGGL(qrisk_critic_grad_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, B, z, zt, n_part,
-                       part_stride, c, m, gamma_safe, dz, loss);
-    return check_launch();
-}
-
-int rrl_qrisk_policy_grad(int B, const float* zp, int n_part, long long part_stride, float* dzp, float* loss,
-                          void* stream) {
-    if (!zp || !dzp || B <= 0 || n_part <= 0 || n_part > 4) return RRL_EINVAL;
-    hipLaunchKernelGGL(qrisk_policy_grad_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, B, zp, n_part,
-                       part_stride, 1.f, dzp, loss);
-    return check_launch();
-}
-
-int rrl_dgd_qrisk_grad(int B, const float* zp, int n_part, long long part_stride, float nu, float* dzp, float* loss,
-                       void* stream) {
-    if (!zp || !dzp || B <= 0 || n_part <= 0 || n_part > 4) return RRL_EINVAL;
-    hipLaunchKernelGGL(qrisk_policy_grad_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, B, zp, n_part,
-                       part_stride, nu, dzp, loss);
-    return check_launch();
-}
-
-int rrl_rcpo_penalty(int B, const float* z, int n_part, long long part_stride, const float* lambda, float* penalty,
-                     float* mean, void* stream) {
-    if (!z || (penalty && !lambda) || (!penalty && !mean) || B <= 0 || n_part <= 0 || n_part > 4) return RRL_EINVAL;
-    hipLaunchKernelGGL(rcpo_penalty_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, B, z, n_part, part_stride,
-                       lambda, penalty, mean);
+int rrl_rcpo_penalty(const rrl_penalty_args_t* a, void* stream) {
+    if (!a || !penalty_args_ok(*a)) return RRL_EINVAL;
+    hipLaunchKernelGGL(rcpo_penalty_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, a->B, a->z, a->n_part,
+                       a->part_stride, a->lambda, a->penalty, a->mean);
     return check_launch();
 }
 
 int rrl_rcpo_penalty_packed(int S, const rrl_penalty_args_t* args, void* stream) {
     if (S <= 0 || S > rrl_pack::kMaxSeeds || !args) return RRL_EINVAL;
-    for (int s = 0; s < S; ++s) {
-        const rrl_penalty_args_t& a = args[s];
-        if (!a.z || (a.penalty && !a.lambda) || (!a.penalty && !a.mean) || a.B <= 0 || a.n_part <= 0 || a.n_part > 4)
-            return RRL_EINVAL;
-    }
+    for (int s = 0; s < S; ++s)
+        if (!penalty_args_ok(args[s])) return RRL_EINVAL;
     // one seed: the packed launch IS the solo launch
-    if (S == 1)
-        return rrl_rcpo_penalty(args[0].B, args[0].z, args[0].n_part, args[0].part_stride, args[0].lambda, args[0].penalty,
-                                args[0].mean, stream);
+    if (S == 1) return rrl_rcpo_penalty(args, stream);
     rrl_pack::Key key;
     key.pod(9);
     key.pod(S);
@@ -852,18 +843,6 @@ int rrl_rcpo_penalty_packed(int S, const rrl_penalty_args_t* args, void* stream)
         plan->grid = S;
     }
     hipLaunchKernelGGL(rcpo_penalty_pack_kernel, dim3(plan->grid), dim3(kBlock), 0, st, (const rrl_penalty_args_t*)plan->dev);
-    return check_launch();
-}
-
-int rrl_stoch_head_bwd(int B, const float* raw, int n_part, long long part_stride, const float* eps,
-                       const float* log_std, float min_log_std, const float* scale, const float* d_action, int ld,
-                       int n_heads, long long head_stride, float* draw, float* dlog_std, void* stream) {
-    if (!raw || !eps || !log_std || !scale || !d_action || !draw || !dlog_std || B <= 0 || n_heads <= 0 ||
-        n_part <= 0 || n_part > 4)
-        return RRL_EINVAL;
-    hipLaunchKernelGGL(stoch_head_bwd_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, B, raw, n_part,
-                       part_stride, eps, log_std, min_log_std, scale, d_action, ld, n_heads, head_stride, draw,
-                       dlog_std);
     return check_launch();
 }
 

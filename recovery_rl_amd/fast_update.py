@@ -388,31 +388,11 @@ def heads_multi(heads):
 
 def loss_dout(loss, B, dout):
     """The gradient an rrl_loss_t describes, written into the tensor `dout` [G, B, dout] by the stand-alone launch of its
-    kind (rrl_*_grad for the critic-loss kinds, rrl_*_head_bwd for the policy-head kinds) instead of inside the
-    head-backward kernel: what FastUpdater.fuse_loss = False runs.  -> dout, for Stack.backward to read."""
-    lib, st, L, d = _lib.load(), _lib.current_stream(), loss, dout.data_ptr()
-    out = (L.out, L.n_part, L.part_stride)
-    if L.kind == _lib.LOSS_SAC_CRITIC:
-        rc, what = lib.rrl_sac_critic_grad(B, L.out, L.out_t, L.n_part, L.part_stride, L.v0, L.v1, L.v2, L.f0, L.alpha,
-                                           L.v3, d, L.loss, st), "rrl_sac_critic_grad"
-    elif L.kind == _lib.LOSS_SAC_POLICY:
-        rc, what = lib.rrl_sac_policy_grad(B, *out, L.v0, L.alpha, d, L.loss, st), "rrl_sac_policy_grad"
-    elif L.kind == _lib.LOSS_QRISK_CRITIC:
-        rc, what = lib.rrl_qrisk_critic_grad(B, L.out, L.out_t, L.n_part, L.part_stride, L.v0, L.v1, L.f0, d, L.loss,
-                                             st), "rrl_qrisk_critic_grad"
-    elif L.kind == _lib.LOSS_QRISK_POLICY:
-        rc, what = lib.rrl_qrisk_policy_grad(B, *out, d, L.loss, st), "rrl_qrisk_policy_grad"
-    elif L.kind == _lib.LOSS_DGD_QRISK:
-        rc, what = lib.rrl_dgd_qrisk_grad(B, *out, L.f0, d, L.loss, st), "rrl_dgd_qrisk_grad"
-    else:
-        # the head kernels read d_action as a plain tensor: the producing backward must have written dx, not partials
-        assert L.da_parts <= 1, "fuse_loss = False needs set_fuse_first(False)"
-        da = (L.d_action, L.ld, L.n_heads, L.head_stride)
-        if L.kind == _lib.LOSS_GAUSS_HEAD:
-            rc, what = lib.rrl_gauss_head_bwd(B, *out, L.v0, L.v1, *da, L.f0, d, st), "rrl_gauss_head_bwd"
-        else:
-            rc, what = lib.rrl_stoch_head_bwd(B, *out, L.v0, L.v1, L.f0, L.v2, *da, d, L.loss, st), "rrl_stoch_head_bwd"
-    _lib.check(rc, what)
+    kind (rrl_loss_dout) instead of inside the head-backward kernel: what FastUpdater.fuse_loss = False runs.
+    -> dout, for Stack.backward to read."""
+    # the head kernels read d_action as a plain tensor: the producing backward must have written dx, not partials
+    assert loss.da_parts <= 1, "fuse_loss = False needs set_fuse_first(False)"
+    _lib.check(_lib.load().rrl_loss_dout(C.byref(loss), B, dout.data_ptr(), _lib.current_stream()), "rrl_loss_dout")
     return dout
 
 
@@ -578,8 +558,7 @@ class FastUpdater:
         a = _lib.rrl_penalty_args_t(self.B, p(t), n_part, ps, p(self.agent.lambda_RCPO) if want_penalty else None,
                                     p(self.penalty) if want_penalty else None, p(mean))
         record("penalty", a)
-        _lib.check(self.lib.rrl_rcpo_penalty(a.B, a.z, a.n_part, a.part_stride, a.lambda_, a.penalty, a.mean,
-                                             _lib.current_stream()), "rrl_rcpo_penalty")
+        _lib.check(self.lib.rrl_rcpo_penalty(C.byref(a), _lib.current_stream()), "rrl_rcpo_penalty")
 
     def policy_loss(self):
         """The SAC policy loss statistic of the last update (with the Lagrangian term under --DGD_constraints, put together

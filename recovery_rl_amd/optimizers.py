@@ -1,7 +1,7 @@
 """Cross-entropy-method optimiser (reference: recovery_rl/optimizers.py:28-124), batched over M
 independent problems and resident on the GPU: sampling and the elite update are the HIP kernels
-rrl_cem_sample / rrl_cem_update; the cost function is called once per iteration on
-[M, popsize, sol_dim]."""
+rrl_cem_sample / rrl_cem_update on one rrl_cem_t per call (host or device count of problems); the
+cost function is called once per iteration on [M, popsize, sol_dim]."""
 import numpy as np
 import torch
 
@@ -35,6 +35,21 @@ class CEMOptimizer(Optimizer):
     def reset(self):
         pass
 
+    def _describe(self, M, m_dev, mean, var, active, samples):
+        """rrl_cem_t of one call: M problems, or with m_dev (int32[1] on the device) the first m_dev[0] of at most M."""
+        p = _lib.ptr
+        return _lib.rrl_cem_t(M, p(m_dev), self.popsize, self.sol_dim, p(mean), p(var), p(self.lb), p(self.ub), self.epsilon,
+                              1, p(active), self.seed, 0, p(self.tick), 1, p(samples), self.num_elites, self.alpha, None)
+
+    def _iterate(self, cem, cost, iters):
+        """The CEM iterations on the buffers `cem` (rrl_cem_t) names: sample, cost() -> [M, popsize] f32, update."""
+        stream = _lib.current_stream()
+        for _ in range(self.max_iters if iters is None else iters):
+            _lib.check(self.lib.rrl_cem_sample(cem, stream), "rrl_cem_sample")
+            costs = cost()
+            cem.costs = _lib.ptr(costs)
+            _lib.check(self.lib.rrl_cem_update(cem, stream), "rrl_cem_update")
+
     def obtain_solution(self, init_mean, init_var, iters=None):
         """init_mean / init_var: [M, sol_dim] (or a single 1-D numpy problem).  Returns the final
         mean, same container type.  Iterates while t < max_iters and max(var) > epsilon, per problem
@@ -49,18 +64,8 @@ class CEMOptimizer(Optimizer):
         assert dim == self.sol_dim
         samples = torch.zeros(M, self.popsize, dim, dtype=torch.float32, device=self.device)
         active = torch.ones(M, dtype=torch.uint8, device=self.device)
-        stream = _lib.current_stream()
-        for _ in range(self.max_iters if iters is None else iters):
-            rc = self.lib.rrl_cem_sample(M, self.popsize, dim, _lib.ptr(mean), _lib.ptr(var),
-                                         _lib.ptr(self.lb), _lib.ptr(self.ub), self.epsilon, 1,
-                                         _lib.ptr(active), self.seed, 0, _lib.ptr(self.tick), 1,
-                                         _lib.ptr(samples), stream)
-            _lib.check(rc, "rrl_cem_sample")
-            costs = self.cost_function(samples).to(torch.float32).contiguous()
-            rc = self.lib.rrl_cem_update(M, self.popsize, dim, self.num_elites, self.alpha,
-                                         _lib.ptr(samples), _lib.ptr(costs), _lib.ptr(mean), _lib.ptr(var),
-                                         _lib.ptr(active), stream)
-            _lib.check(rc, "rrl_cem_update")
+        self._iterate(self._describe(M, None, mean, var, active, samples),
+                      lambda: self.cost_function(samples).to(torch.float32).contiguous(), iters)
         return mean[0].cpu().numpy() if single else mean
 
     def obtain_solution_n(self, ws, count, iters=None):
@@ -68,26 +73,16 @@ class CEMOptimizer(Optimizer):
         MPC.act with a recovery mask): mean / var / samples are the caller's persistent workspace `ws`, the cost function
         is called as cost_function(samples, count=count) and must not synchronise.  Same Philox rows, same arithmetic as
         obtain_solution on the compacted problems."""
-        stream = _lib.current_stream()
-        dim = self.sol_dim
-        for _ in range(self.max_iters if iters is None else iters):
-            rc = self.lib.rrl_cem_sample_n(_lib.ptr(count), ws.m_max, self.popsize, dim, _lib.ptr(ws.mean),
-                                           _lib.ptr(ws.var), _lib.ptr(self.lb), _lib.ptr(self.ub), self.epsilon, 1,
-                                           _lib.ptr(ws.active), self.seed, 0, _lib.ptr(self.tick), 1,
-                                           _lib.ptr(ws.samples), stream)
-            _lib.check(rc, "rrl_cem_sample_n")
-            costs = self.cost_function(ws.samples, count=count)
-            rc = self.lib.rrl_cem_update_n(_lib.ptr(count), ws.m_max, self.popsize, dim, self.num_elites, self.alpha,
-                                           _lib.ptr(ws.samples), _lib.ptr(costs), _lib.ptr(ws.mean), _lib.ptr(ws.var),
-                                           _lib.ptr(ws.active), stream)
-            _lib.check(rc, "rrl_cem_update_n")
+        self._iterate(self._describe(ws.m_max, count, ws.mean, ws.var, ws.active, ws.samples),
+                      lambda: self.cost_function(ws.samples, count=count), iters)
         return ws.mean
 
 
 class PlanWorkspace:
-    """Persistent buffers of the device-count planning path, sized for m_max problems."""
+    """Persistent buffers of the device-count planning path, sized for m_max problems, and the rrl_cem_set_t over them
+    (`set`: the caller fills in mask, obs and prev_sol per call)."""
 
-    def __init__(self, m_max, popsize, sol_dim, device):
+    def __init__(self, m_max, popsize, sol_dim, du, init_var, device):
         self.m_max = int(m_max)
         z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=device)
         self.idx, self.count = z(m_max, dt=torch.int32), z(1, dt=torch.int32)
@@ -96,3 +91,8 @@ class PlanWorkspace:
         self.cur_obs = z(m_max, 2)
         self.active = z(m_max, dt=torch.uint8)
         self.costs = z(m_max, popsize)
+        self.action = z(m_max, du)
+        self.init_var = init_var
+        p = _lib.ptr
+        self.set = _lib.rrl_cem_set_t(self.m_max, None, sol_dim, du, None, p(init_var), None, p(self.idx), p(self.count),
+                                      p(self.mean), p(self.var), p(self.cur_obs), p(self.active), p(self.action))

@@ -1,6 +1,7 @@
-"""Fused candidate evaluation for the model-based recovery controller: `rrl_plan_cost` behind
-`MPC._compile_cost` (recovery_rl/MPC.py:374-416).  The PyTorch path in MPC.py stays as the general
-path (other widths) and as the cross-check (tests/test_plan_gpu.py)."""
+"""Fused candidate evaluation for the model-based recovery controller: `rrl_plan_cost` (one rrl_plan_cost_t per
+launch: either precision, host or device count of problems) behind `MPC._compile_cost`
+(recovery_rl/MPC.py:374-416).  The PyTorch path in MPC.py stays as the general path (other widths) and as the
+cross-check (tests/test_plan_gpu.py)."""
 import ctypes as C
 import os
 
@@ -13,7 +14,7 @@ class FusedPlanner:
     """Packs the live Q_risk and ensemble weights into MFMA fragment order and evaluates CEM candidates."""
 
     def __init__(self, mpc, f16x3=None):
-        """f16x3: evaluate the hidden layers as three f16 MFMA products of hi/lo splits (rrl_plan_cost_f16x3) instead of
+        """f16x3: evaluate the hidden layers as three f16 MFMA products of hi/lo splits (rrl_plan_cost_t.f16x3) instead of
         f32 MFMA; default from RRL_PLAN_F16X3 (off)."""
         self.mpc = mpc
         self.lib = _lib.load()
@@ -29,7 +30,7 @@ class FusedPlanner:
         self.packed = torch.zeros(int(n), dtype=torch.float32, device=self.device)
         self.tick = torch.zeros(2, dtype=torch.int64, device=self.device)
         self.seed = (int(mpc.optimizer.seed) ^ 0x706C616E) & 0xFFFFFFFFFFFFFFFF
-        self._scratch = None
+        self._scratch = []               # every buffer ever handed out; the last one is current
 
     @staticmethod
     def supported(mpc):
@@ -52,17 +53,26 @@ class FusedPlanner:
                model.lin3_b, model.inputs_mu, model.inputs_sigma, model.max_logvar, model.min_logvar]
         ens = [t.detach().to(torch.float32).contiguous() for t in ens]
         w = _lib.rrl_plan_weights_t(self.hq, self.he, self.n_nets, *[t.data_ptr() for t in keep + ens])
-        pack = self.lib.rrl_plan_pack_f16x3 if self.f16x3 else self.lib.rrl_plan_pack
-        _lib.check(pack(C.byref(w), _lib.ptr(self.packed), _lib.current_stream()), "rrl_plan_pack")
+        _lib.check(self.lib.rrl_plan_pack(C.byref(w), int(self.f16x3), _lib.ptr(self.packed), _lib.current_stream()),
+                   "rrl_plan_pack")
         self._keep = keep + ens        # the pack kernels read them asynchronously
 
     def _scratch_for(self, M, pop):
-        """First-step values + per-member cost sums of M planning problems (rrl_plan_scratch_floats); grows, never shrinks
-        (a captured graph holds its address)."""
+        """First-step values + per-member cost sums of M planning problems (rrl_plan_scratch_floats); grows, never shrinks,
+        and an outgrown buffer stays referenced (a captured graph holds its address)."""
         need = int(self.lib.rrl_plan_scratch_floats(self.n_nets, M, pop))
-        if self._scratch is None or self._scratch.numel() < need:
-            self._scratch = torch.empty(need, dtype=torch.float32, device=self.device)
-        return self._scratch
+        if not self._scratch or self._scratch[-1].numel() < need:
+            self._scratch.append(torch.empty(need, dtype=torch.float32, device=self.device))
+        return self._scratch[-1]
+
+    def _launch(self, M, count, pop, cur_obs, ac_seqs, noise, costs):
+        """rrl_plan_cost for M problems, or with `count` (int32[1] on the device) for the first count[0] of at most M."""
+        mpc, p = self.mpc, _lib.ptr
+        a = _lib.rrl_plan_cost_t(p(self.packed), self.hq, self.he, self.n_nets, mpc.npart, int(self.f16x3), M, p(count), pop,
+                                 mpc.plan_hor, p(cur_obs), p(ac_seqs), p(noise), self.seed, 0, p(self.tick), 1,
+                                 p(self._scratch_for(M, pop)), p(costs))
+        _lib.check(self.lib.rrl_plan_cost(C.byref(a), _lib.current_stream()), "rrl_plan_cost")
+        return costs
 
     def cost(self, ac_seqs, cur_obs, noise=None):
         """ac_seqs [M, pop, plan_hor*2], cur_obs [M, 2] -> costs [M, pop] (f32)."""
@@ -73,25 +83,10 @@ class FusedPlanner:
         if noise is not None:
             noise = noise.to(torch.float32).contiguous()
             assert tuple(noise.shape) == (mpc.plan_hor, M * pop * mpc.npart, 2)
-        scratch = self._scratch_for(M, pop)
-        costs = torch.empty(M, pop, dtype=torch.float32, device=self.device)
-        entry = self.lib.rrl_plan_cost_f16x3 if self.f16x3 else self.lib.rrl_plan_cost
-        rc = entry(_lib.ptr(self.packed), self.hq, self.he, self.n_nets, mpc.npart, M, pop,
-                                    mpc.plan_hor, _lib.ptr(cur_obs), _lib.ptr(ac_seqs), _lib.ptr(noise), self.seed, 0,
-                                    _lib.ptr(self.tick), 1, _lib.ptr(scratch), _lib.ptr(costs),
-                                    _lib.current_stream())
-        _lib.check(rc, "rrl_plan_cost")
-        return costs
+        return self._launch(M, None, pop, cur_obs, ac_seqs, noise,
+                            torch.empty(M, pop, dtype=torch.float32, device=self.device))
 
     def cost_n(self, ws, count, costs):
-        """cost() for the first count[0] problems of the workspace (count on the device; rrl_plan_cost_n): no host
-        synchronisation, the launch covers ws.m_max problems and the workgroups past the live ones exit at once."""
-        mpc = self.mpc
-        pop = int(ws.samples.shape[1])
-        scratch = self._scratch_for(ws.m_max, pop)
-        rc = self.lib.rrl_plan_cost_n(int(self.f16x3), _lib.ptr(self.packed), self.hq, self.he, self.n_nets, mpc.npart,
-                                      _lib.ptr(count), ws.m_max, pop, mpc.plan_hor, _lib.ptr(ws.cur_obs),
-                                      _lib.ptr(ws.samples), None, self.seed, 0, _lib.ptr(self.tick), 1,
-                                      _lib.ptr(scratch), _lib.ptr(costs), _lib.current_stream())
-        _lib.check(rc, "rrl_plan_cost_n")
-        return costs
+        """cost() for the first count[0] problems of the workspace (count on the device): no host synchronisation, the
+        launch covers ws.m_max problems and the workgroups past the live ones exit at once."""
+        return self._launch(ws.m_max, count, int(ws.samples.shape[1]), ws.cur_obs, ws.samples, None, costs)

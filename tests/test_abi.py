@@ -457,6 +457,156 @@ def test_draw_and_policy_head_descriptor_validation_without_gpu():
     assert lib.rrl_policy_heads_fwd_multi(1, None, None) == EINVAL
 
 
+def _plan_cost(**fields):
+    """A well-formed rrl_plan_cost_t of the supported shape (5 members, 20 particles); dummy non-null device pointers."""
+    d = 0x1000
+    return _with(_lib.rrl_plan_cost_t(packed=d, hq=256, he=200, n_nets=5, npart=20, f16x3=0, M=3, pop=40, plan_hor=5,
+                                      cur_obs=d, ac_seqs=d, noise=d, seed=1, counter_dev=d, counter_inc=1, scratch=d,
+                                      costs=d), **fields)
+
+
+def _cem(**fields):
+    d = 0x1000
+    return _with(_lib.rrl_cem_t(M=3, pop=40, dim=10, mean=d, var=d, lb=d, ub=d, epsilon=1e-3, sticky=1, active=d, seed=1,
+                                counter_dev=d, counter_inc=1, samples=d, num_elites=4, alpha=0.25, costs=d), **fields)
+
+
+def _cem_set(**fields):
+    d = 0x1000
+    return _with(_lib.rrl_cem_set_t(n=64, mask=d, dim=10, du=2, prev_sol=d, init_var=d, obs=d, idx=d, count=d, mean=d,
+                                    var=d, cur_obs=d, active=d, action=d), **fields)
+
+
+def _loss(kind, **fields):
+    """A well-formed rrl_loss_t of `kind` for rrl_loss_dout: the operands the header assigns to the kind, nothing else."""
+    d = 0x1000
+    L = _lib
+    operands = {L.LOSS_SAC_CRITIC: dict(out_t=d, v0=d, v1=d, v2=d, alpha=d, loss=d),
+                L.LOSS_SAC_POLICY: dict(v0=d, alpha=d, loss=d),
+                L.LOSS_QRISK_CRITIC: dict(out_t=d, v0=d, v1=d, loss=d),
+                L.LOSS_QRISK_POLICY: dict(loss=d),
+                L.LOSS_DGD_QRISK: dict(loss=d, f0=0.5),
+                L.LOSS_GAUSS_HEAD: dict(v0=d, v1=d, d_action=d, ld=4, n_heads=2),
+                L.LOSS_STOCH_HEAD: dict(v0=d, v1=d, v2=d, d_action=d, ld=4, n_heads=2, loss=d)}
+    return _with(_lib.rrl_loss_t(kind=kind, n_part=1, out=d, **operands.get(kind, {})), **fields)
+
+
+def test_planner_cem_and_loss_descriptor_validation_without_gpu():
+    """What rrl_plan_cost, rrl_plan_pack, rrl_cem_sample / update / begin / finish and rrl_loss_dout answer to a malformed
+    descriptor: every call returns before any launch (dummy non-null device pointers are never followed).  The codes are
+    those of ABI version 7, recorded on a machine without a GPU by calling that library's positional entries (the _f16x3 /
+    _n forms where the descriptor sets f16x3 / m_dev; the seven rrl_*_grad / rrl_*_head_bwd entries for the seven kinds)
+    with the same values.  Three answers have no positional counterpart: a NULL descriptor, kind == -1 / an unknown kind
+    (RRL_EINVAL: nothing to compute / RRL_ERANGE as in rrl_head_bwd_t), and da_parts > 1 (the positional head entries
+    had no such argument: the stand-alone kernels read a plain d_action).  The only calls here that are not refused are
+    the CEM steps on M == 0 problems, which answer RRL_OK without a launch.  rrl_rcpo_penalty's cases stand beside the
+    packed entry's in tests/test_packed_baselines_cpu.py."""
+    lib = _lib.load()
+    OK, EINVAL, ERANGE = 0, -1, -3
+    d = 0x1000
+    ref = ctypes.byref
+
+    # -- planner: every failure is RRL_EINVAL; either precision, host or device count
+    plans = [
+        ("packed missing", dict(packed=None)), ("cur_obs missing", dict(cur_obs=None)), ("ac_seqs missing", dict(ac_seqs=None)),
+        ("scratch missing", dict(scratch=None)), ("costs missing", dict(costs=None)),
+        ("M 0", dict(M=0)), ("M < 0", dict(M=-1)), ("pop 0", dict(pop=0)), ("plan_hor 0", dict(plan_hor=0)),
+        ("plan_hor 17", dict(plan_hor=17)), ("hq 128", dict(hq=128)), ("he 256", dict(he=256)), ("n_nets 0", dict(n_nets=0)),
+        ("npart != 4 n_nets", dict(npart=10)), ("rows >= 2^32", dict(M=1 << 22, pop=400)),
+        ("noise missing and pop 0", dict(noise=None, pop=0)),
+    ]
+    for what, f in plans:
+        for f16x3 in (0, 1):
+            for m_dev in (None, d):
+                assert lib.rrl_plan_cost(ref(_plan_cost(f16x3=f16x3, m_dev=m_dev, **f)), None) == EINVAL, (what, f16x3, m_dev)
+    assert lib.rrl_plan_cost(None, None) == EINVAL
+    w = _lib.rrl_plan_weights_t(256, 200, 5, *([d] * 18))
+    for f16x3 in (0, 1):
+        assert lib.rrl_plan_pack(None, f16x3, d, None) == EINVAL
+        assert lib.rrl_plan_pack(ref(w), f16x3, None, None) == EINVAL
+        for f in (dict(hq=128), dict(he=256), dict(n_nets=0)):
+            assert lib.rrl_plan_pack(ref(_with(_lib.rrl_plan_weights_t(256, 200, 5, *([d] * 18)), **f)), f16x3, d, None) == EINVAL
+
+    # -- CEM: pointers (RRL_EINVAL), then sizes (RRL_ERANGE), then num_elites (RRL_EINVAL), then M == 0 (RRL_OK)
+    sizes = [("M < 0", dict(M=-1)), ("pop 0", dict(pop=0)), ("pop 1025", dict(pop=1025)), ("dim 0", dict(dim=0)),
+             ("dim 65", dict(dim=65))]
+    sample = [(n + " missing", {n: None}, EINVAL) for n in ("mean", "var", "lb", "ub", "active", "samples")]
+    sample += [(what, f, ERANGE) for what, f in sizes]
+    sample += [
+        ("M pop > 0xffffffff", dict(M=1 << 23, pop=1024), ERANGE),
+        ("M pop == 2^32 with pop 1024", dict(M=1 << 22, pop=1024), ERANGE),
+        ("mean missing and pop 0", dict(mean=None, pop=0), EINVAL),
+        ("samples missing and M pop > 0xffffffff", dict(samples=None, M=1 << 23, pop=1024), EINVAL),
+        ("costs missing (not read) and dim 65", dict(costs=None, dim=65), ERANGE),
+        ("num_elites 0 (not read) and M 0", dict(num_elites=0, M=0), OK),
+        ("M 0", dict(M=0), OK),
+    ]
+    update = [(n + " missing", {n: None}, EINVAL) for n in ("samples", "costs", "mean", "var")]
+    update += [(what, f, ERANGE) for what, f in sizes]
+    update += [
+        ("num_elites 0", dict(num_elites=0), EINVAL),
+        ("num_elites pop + 1", dict(num_elites=41), EINVAL),
+        ("costs missing and pop 1025", dict(costs=None, pop=1025), EINVAL),
+        ("pop 0 and num_elites 0", dict(pop=0, num_elites=0), ERANGE),
+        ("dim 65 and num_elites pop + 1", dict(dim=65, num_elites=41), ERANGE),
+        ("num_elites 0 and M 0", dict(num_elites=0, M=0), EINVAL),
+        ("active missing (nullable) and dim 0", dict(active=None, dim=0), ERANGE),
+        ("active, lb, ub missing (nullable / not read) and M 0", dict(active=None, lb=None, ub=None, M=0), OK),
+        ("M 0", dict(M=0), OK),
+    ]
+    for entry, cases in ((lib.rrl_cem_sample, sample), (lib.rrl_cem_update, update)):
+        for what, f, want in cases:
+            for m_dev in (None, d):
+                assert entry(ref(_cem(m_dev=m_dev, **f)), None) == want, (entry.__name__, what, m_dev)
+        assert entry(None, None) == EINVAL
+
+    set_sizes = [("n 0", dict(n=0)), ("n < 0", dict(n=-1)), ("n 2^31", dict(n=1 << 31)), ("dim 0", dict(dim=0)),
+                 ("dim 65", dict(dim=65))]
+    begin = [(n + " missing", {n: None}, EINVAL) for n in ("mask", "prev_sol", "init_var", "obs", "idx", "count", "mean", "var",
+                                                           "cur_obs", "active")]
+    begin += [(what, f, ERANGE) for what, f in set_sizes]
+    begin += [("obs missing and n 0", dict(obs=None, n=0), EINVAL),
+              ("action missing, du 0 (not read) and n 0", dict(action=None, du=0, n=0), ERANGE)]
+    finish = [(n + " missing", {n: None}, EINVAL) for n in ("mask", "idx", "count", "mean", "prev_sol", "action")]
+    finish += [(what, f, ERANGE) for what, f in set_sizes]
+    finish += [("du 0", dict(du=0), ERANGE), ("du dim + 1", dict(du=11), ERANGE),
+               ("action missing and du 0", dict(action=None, du=0), EINVAL),
+               ("begin's inputs missing (not read) and n 0", dict(init_var=None, obs=None, var=None, cur_obs=None, active=None,
+                                                                  n=0), ERANGE)]
+    for entry, cases in ((lib.rrl_cem_begin, begin), (lib.rrl_cem_finish, finish)):
+        for what, f, want in cases:
+            assert entry(ref(_cem_set(**f)), None) == want, (entry.__name__, what)
+        assert entry(None, None) == EINVAL
+
+    # -- stand-alone loss gradients: everything the kind's positional entry refused is RRL_EINVAL
+    L = _lib
+    required = {L.LOSS_SAC_CRITIC: ("out", "out_t", "v0", "v1", "v2", "alpha"),
+                L.LOSS_SAC_POLICY: ("out", "v0", "alpha"),
+                L.LOSS_QRISK_CRITIC: ("out", "out_t", "v0", "v1"),
+                L.LOSS_QRISK_POLICY: ("out",),
+                L.LOSS_DGD_QRISK: ("out",),
+                L.LOSS_GAUSS_HEAD: ("out", "v0", "v1", "d_action"),
+                L.LOSS_STOCH_HEAD: ("out", "v0", "v1", "v2", "d_action", "loss")}
+    dout = lambda loss, B=64, out=d: lib.rrl_loss_dout(ref(loss), B, out, None)
+    for kind, names in required.items():
+        for n in names:
+            assert dout(_loss(kind, **{n: None})) == EINVAL, (kind, n + " missing")
+        assert dout(_loss(kind), out=None) == EINVAL, (kind, "dout missing")
+        for B in (0, -64):
+            assert dout(_loss(kind), B=B) == EINVAL, (kind, "B", B)
+        for n_part in (0, 5, -1):
+            assert dout(_loss(kind, n_part=n_part)) == EINVAL, (kind, "n_part", n_part)
+        if kind in (L.LOSS_GAUSS_HEAD, L.LOSS_STOCH_HEAD):
+            for n_heads in (0, -1):
+                assert dout(_loss(kind, n_heads=n_heads)) == EINVAL, (kind, "n_heads", n_heads)
+            assert dout(_loss(kind, da_parts=2, da_part_stride=256)) == EINVAL, (kind, "d_action as partials")
+            assert dout(_loss(kind, da_parts=16, da_part_stride=256, da_group=4)) == EINVAL, (kind, "d_action as tile partials")
+    assert dout(_loss(-1)) == EINVAL                       # `out` already is dOut
+    for kind in (7, -2, 1 << 20):
+        assert dout(_loss(kind)) == ERANGE, ("kind", kind)
+    assert lib.rrl_loss_dout(None, 64, d, None) == EINVAL
+
+
 def test_product_has_no_cpu_fallback():
     import pytest
     import torch

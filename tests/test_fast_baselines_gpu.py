@@ -159,6 +159,32 @@ def test_grouped_baseline_launches_equal_the_separate_ones(config):
     assert float(dual_state(loops[0].agent, dual)["step"]) > 4       # the dual stepped in the replays too
 
 
+def test_lagrangian_qrisk_gradient_fused_equals_its_stand_alone_kernel():
+    """RRL_LOSS_DGD_QRISK inside the head-backward kernel against rrl_loss_dout's launch of its own (fuse_loss = False), the
+    one kind tests/test_fast_update_gpu.py's fused / unfused comparison never sends there: the LR line at hidden 32, batch
+    64, member by member with the first layer as its own launch on both sides.  Every parameter and gradient after two
+    updates bit-identical, the logged losses and dual statistics close."""
+    _, a, args = make_pair(32, CONFIGS["LR"])
+    _, b, _ = make_pair(32, CONFIGS["LR"])
+    B, nu = 64, nu_of(args)
+    for ag, fuse in ((a, True), (b, False)):
+        ag.enable_fast_path(B)
+        ag.fast.fuse_loss = fuse
+        ag.fast.set_fuse_first(False)
+    for step in range(2):
+        b_sac, b_qr, e1, e2 = batch(B, 60 + step)
+        for ag in (a, b):
+            ag.update_parameters(None, B, step, nu=nu, safety_critic=ag.safety_critic, batch=b_sac, eps_next=e1, eps_pi=e2)
+            ag.safety_critic.update_parameters(policy=ag.policy, batch=b_qr, eps_next=e1, eps_pi=e2)
+        for name in ("critic", "critic_target", "policy", "qrisk", "qrisk_target", "recpolicy"):
+            fa, fb = getattr(a.fast, name), getattr(b.fast, name)
+            assert torch.equal(fa.flat, fb.flat), (step, name)
+            assert torch.equal(fa.grad, fb.grad), (step, name)
+        assert torch.equal(a.log_nu, b.log_nu)
+        torch.testing.assert_close(a.fast.losses, b.fast.losses, rtol=1e-5, atol=1e-7)
+        torch.testing.assert_close(a.fast.dual_stats, b.fast.dual_stats, rtol=1e-5, atol=1e-7)
+
+
 def _cfg(tmp, num_eps, extra=()):
     return arg_utils.get_args(["--env-name", "navigation1", "--cuda", "--hidden_size", "32", "--logdir", str(tmp),
                                "--seed", "5", "--num_unsafe_transitions", "2000", "--critic_safe_pretraining_steps",

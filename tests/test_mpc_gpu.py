@@ -29,15 +29,20 @@ def T(x, dt=None):
         torch.as_tensor(np.ascontiguousarray(x, dtype=dt), device=DEV)
 
 
+def cem_desc(M, pop, dim, m_dev=None, **tensors):
+    """rrl_cem_t over `tensors` (field name -> device tensor); what is not given stays NULL / 0."""
+    return _lib.rrl_cem_t(M=M, m_dev=_lib.ptr(m_dev), pop=pop, dim=dim, **{k: _lib.ptr(t) for k, t in tensors.items()})
+
+
 def hip_cem_sample(mean, var, lb, ub, pop, epsilon=1e-3, sticky=False, active=None, seed=0, counter=0):
     lib = _lib.load()
     M, dim = mean.shape
     mean_t, var_t, lb_t, ub_t = T(mean, np.float64), T(var, np.float64), T(lb, np.float64), T(ub, np.float64)
     act = T(np.ones(M, np.uint8) if active is None else active, np.uint8)
     samples = torch.zeros(M, pop, dim, device=DEV)
-    rc = lib.rrl_cem_sample(M, pop, dim, _lib.ptr(mean_t), _lib.ptr(var_t), _lib.ptr(lb_t), _lib.ptr(ub_t),
-                            epsilon, int(sticky), _lib.ptr(act), seed, counter, None, 0, _lib.ptr(samples),
-                            _lib.current_stream())
+    c = cem_desc(M, pop, dim, mean=mean_t, var=var_t, lb=lb_t, ub=ub_t, active=act, samples=samples)
+    c.epsilon, c.sticky, c.seed, c.counter = epsilon, int(sticky), seed, counter
+    rc = lib.rrl_cem_sample(c, _lib.current_stream())
     assert rc == 0
     return samples.cpu().numpy(), act.cpu().numpy()
 
@@ -48,28 +53,74 @@ def hip_cem_update(samples, costs, mean, var, ne, alpha, active=None):
     s, c = T(samples, np.float32), T(costs, np.float32)
     m, v = T(mean, np.float64).clone(), T(var, np.float64).clone()
     a = None if active is None else T(active, np.uint8)
-    rc = lib.rrl_cem_update(M, pop, dim, ne, alpha, _lib.ptr(s), _lib.ptr(c), _lib.ptr(m), _lib.ptr(v),
-                            _lib.ptr(a), _lib.current_stream())
+    desc = cem_desc(M, pop, dim, samples=s, costs=c, mean=m, var=v, active=a)
+    desc.num_elites, desc.alpha = ne, alpha
+    rc = lib.rrl_cem_update(desc, _lib.current_stream())
     assert rc == 0
     return m.cpu().numpy(), v.cpu().numpy()
 
 
-@pytest.mark.parametrize("M,pop,dim", ((1, 400, 10), (37, 400, 10), (5, 400, 30), (300, 64, 4), (2, 1000, 7)))
-def test_cem_kernels_match_oracle_bit_exact(M, pop, dim):
+def cem_device_count(mean, var, lb, ub, pop, costs, ne, alpha, live, seed, counter):
+    """Sample, then update on the sample kernel's own output, with the number of problems read from device memory
+    (m_dev[0] = live) and every buffer sized for three problems more than `mean` has, sentinels everywhere.
+    -> (samples, active, mean, var) of all M + 3 rows after the sample and (mean, var) after the update, the tick."""
+    lib, st = _lib.load(), _lib.current_stream()
+    M, dim = mean.shape
+    pad = lambda x, fill, dt: T(np.concatenate([x, np.full((3,) + x.shape[1:], fill, x.dtype)]), dt)
+    mean_t, var_t = pad(mean, -5.0, np.float64), pad(var, -5.0, np.float64)
+    act = T(np.full(M + 3, 9, np.uint8))
+    samples = torch.full((M + 3, pop, dim), 7.0, device=DEV)
+    costs_t = pad(costs, 0.0, np.float32)
+    m_dev = T(np.array([live], np.int32))
+    tick = torch.zeros(2, dtype=torch.int64, device=DEV)
+    c = cem_desc(M + 3, pop, dim, m_dev, mean=mean_t, var=var_t, lb=T(lb, np.float64), ub=T(ub, np.float64), active=act,
+                 samples=samples, costs=costs_t, counter_dev=tick)
+    c.epsilon, c.seed, c.counter, c.counter_inc, c.num_elites, c.alpha = 1e-3, seed, counter, 1, ne, alpha
+    assert lib.rrl_cem_sample(c, st) == 0
+    sampled = [t.cpu().numpy().copy() for t in (samples, act, mean_t, var_t)]
+    assert lib.rrl_cem_update(c, st) == 0
+    return sampled, (mean_t.cpu().numpy(), var_t.cpu().numpy()), int(tick[0].item())
+
+
+CEM_SHAPES = ((1, 400, 10), (37, 400, 10), (5, 400, 30), (300, 64, 4), (2, 1000, 7))
+
+
+@pytest.mark.parametrize("M,pop,dim,device_count", [pytest.param(*s, False, id="%d-%d-%d" % s) for s in CEM_SHAPES] + [
+    pytest.param(*s, True, id="%d-%d-%d-device_count" % s) for s in ((1, 400, 10), (37, 400, 10), (2, 1000, 7))])
+def test_cem_kernels_match_oracle_bit_exact(M, pop, dim, device_count):
     rng = np.random.RandomState(M * 1000 + pop + dim)
     mean = rng.uniform(-0.9, 0.9, (M, dim))
     var = rng.uniform(0.0, 0.3, (M, dim))
     var[M // 2] = 1e-5
     lb, ub = -np.ones(dim), np.ones(dim)
     ref_s, ref_a = co.cem_sample(mean, var, lb, ub, pop, seed=9, counter=4)
-    got_s, got_a = hip_cem_sample(mean, var, lb, ub, pop, seed=9, counter=4)
-    assert np.array_equal(got_a, ref_a) and np.array_equal(got_s, ref_s)
     costs = rng.randn(M, pop).astype(np.float32)
     costs[0, :3] = np.nan                                   # NaN -> 1e6
     costs[-1, 5] = costs[-1, 6]                             # tie -> lower index first
     ne = max(1, pop // 10)
     ref_m, ref_v = co.cem_update(ref_s, costs, mean, var, ne, 0.1, active=ref_a)
-    got_m, got_v = hip_cem_update(ref_s, costs, mean, var, ne, 0.1, active=ref_a)
+    if device_count:
+        (got_s, got_a, m0, v0), (got_m, got_v), tick = cem_device_count(mean, var, lb, ub, pop, costs, ne, 0.1, M, 9, 4)
+        assert np.array_equal(m0[:M], mean) and np.array_equal(v0[:M], var)         # the sample step writes neither
+        # the three rows past the count keep their sentinels through both steps
+        assert (got_s[M:] == 7.0).all() and (got_a[M:] == 9).all()
+        assert (got_m[M:] == -5.0).all() and (got_v[M:] == -5.0).all() and (m0[M:] == -5.0).all() and (v0[M:] == -5.0).all()
+        assert tick == 1
+        got_s, got_a, got_m, got_v = got_s[:M], got_a[:M], got_m[:M], got_v[:M]
+        # an inactive problem's samples are not drawn: the oracle leaves zeros, this buffer its sentinel
+        assert (got_s[ref_a == 0] == 7.0).all()
+        got_s = np.where((ref_a == 0)[:, None, None], ref_s, got_s)
+        # an empty set: nothing is written, the tick stays
+        (s_, a_, m_, v_), (m2, v2), tick = cem_device_count(mean, var, lb, ub, pop, costs, ne, 0.1, 0, 9, 4)
+        assert (s_ == 7.0).all() and (a_ == 9).all() and tick == 0
+        for got_mean, got_var in ((m_, v_), (m2, v2)):
+            assert np.array_equal(got_mean[:M], mean) and np.array_equal(got_var[:M], var)
+            assert (got_mean[M:] == -5.0).all() and (got_var[M:] == -5.0).all()
+    else:
+        got_s, got_a = hip_cem_sample(mean, var, lb, ub, pop, seed=9, counter=4)
+    assert np.array_equal(got_a, ref_a) and np.array_equal(got_s, ref_s)
+    if not device_count:
+        got_m, got_v = hip_cem_update(ref_s, costs, mean, var, ne, 0.1, active=ref_a)
     assert np.array_equal(got_m, ref_m) and np.array_equal(got_v, ref_v)
     assert np.array_equal(got_m[M // 2], mean[M // 2])      # inactive env untouched
 

@@ -210,6 +210,8 @@ def test_packed_entry_points_validate_every_seed_without_gpu():
     for bad in (pen(z=None), pen(B=0), pen(n_part=0), pen(n_part=5), pen(penalty=d), pen(mean=None)):
         assert lib.rrl_rcpo_penalty_packed(2, arr(pen(), bad), None) == EINVAL
         assert lib.rrl_rcpo_penalty_packed(1, arr(bad), None) == EINVAL
+        assert lib.rrl_rcpo_penalty(C.byref(bad), None) == EINVAL                                 # the solo entry: the same check
+    assert lib.rrl_rcpo_penalty(None, None) == EINVAL
 
     gauss = lambda **k: _lib.rrl_policy_head_t(**dict(dict(kind=_lib.HEAD_GAUSS, B=8, head=d, n_part=1, eps=d, scale=d, bias=d,
                                                            action=d, ld_action=2), **k))

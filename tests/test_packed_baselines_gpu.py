@@ -52,8 +52,8 @@ def test_packed_penalty_equals_the_stand_alone_launches(S):
         pen, mean = outs[0]
         args[s] = _lib.rrl_penalty_args_t(B, p(z), n_part, z.stride(0), p(lam) if want else None, p(pen) if want else None, p(mean))
         pen, mean = outs[1]
-        assert lib.rrl_rcpo_penalty(B, p(z), n_part, z.stride(0), p(lam) if want else None, p(pen) if want else None, p(mean),
-                                    stream()) == 0
+        solo = _lib.rrl_penalty_args_t(B, p(z), n_part, z.stride(0), p(lam) if want else None, p(pen) if want else None, p(mean))
+        assert lib.rrl_rcpo_penalty(solo, stream()) == 0
     assert lib.rrl_rcpo_penalty_packed(S, args, stream()) == 0
     torch.cuda.synchronize()
     for s, (B, n_part, z, lam, want, outs) in enumerate(seeds):

@@ -37,7 +37,7 @@ def build(seed=0, weight_scale=2.5, f16x3=False):
     mpc.has_been_trained = True
     mpc.update_value_func(agent.safety_critic)
     assert mpc.fused is not None
-    if f16x3:                  # the hidden layers as three f16 MFMA products of hi / lo splits (rrl_plan_cost_f16x3)
+    if f16x3:                  # the hidden layers as three f16 MFMA products of hi / lo splits (rrl_plan_cost_t.f16x3)
         from recovery_rl_amd.planner import FusedPlanner
         mpc.fused = FusedPlanner(mpc, f16x3=True)
     assert mpc.fused.f16x3 == f16x3
@@ -149,8 +149,8 @@ def test_fused_cost_at_config4_scale_4096_planning_envs(f16x3):
 @pytest.mark.parametrize("f16x3", [False, True])
 @pytest.mark.parametrize("n,frac", [(64, 0.3), (64, 0.0), (64, 1.0), (700, 0.05)])
 def test_act_with_the_planning_set_counted_on_the_device_equals_the_host_count_path(n, frac, f16x3):
-    """MPC.act(obs, t, mask): the device-count path (rrl_cem_begin -> rrl_cem_sample_n / rrl_plan_cost_n /
-    rrl_cem_update_n -> rrl_cem_finish; no host synchronisation) against the path that compacts with mask.nonzero() on the
+    """MPC.act(obs, t, mask): the device-count path (rrl_cem_begin -> rrl_cem_sample / rrl_plan_cost /
+    rrl_cem_update with m_dev -> rrl_cem_finish; no host synchronisation) against the path that compacts with mask.nonzero() on the
     host: same actions, same shifted solutions, same RNG ticks, bit for bit -- incl. an empty and a full planning set, over
     two consecutive calls (prev_sol carried between them)."""
     _, mpc, agent = build(seed=5, f16x3=f16x3)

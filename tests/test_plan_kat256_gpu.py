@@ -1,4 +1,4 @@
-"""rrl_plan_cost / rrl_plan_cost_f16x3 against numbers the REFERENCE produced at the kernel's only supported shape
+"""rrl_plan_cost (f32 and f16x3) against numbers the REFERENCE produced at the kernel's only supported shape
 (Q_risk hidden 256, 5 x 200 ensemble, 400 candidates x 20 particles x 5 steps; tests/golden/mpc_golden_256.npz from
 gen_mpc_golden_256.py, which imports recovery_rl/MPC.py:374-416,421-439, config/navigation2.py:71-96,
 recovery_rl/qrisk.py:184-196).  Weights, candidates, observations and particle noise are re-created from the seeded streams
