@@ -1086,9 +1086,10 @@ __device__ __forceinline__ void head_bwd_loss_body(const HeadBwdArgs& hb, int bx
     constexpr bool per_head = KIND == RRL_LOSS_SAC_CRITIC || KIND == RRL_LOSS_QRISK_CRITIC;
     const bool want_loss = KIND != kPlainDOut && KIND != RRL_LOSS_GAUSS_HEAD && la.loss && (per_head || g == 0);
     float* tail = dsh + 1024 * 4 - 6 * 16;            // dsh holds B * dout <= 4096 floats only when B = 1024, dout = 4:
-    const bool tail_free = B * dout <= 1024 * 4 - 6 * 16;   // then the scalars take the slow path below
+    const bool tail_free = B * dout <= 1024 * 4 - 6 * 16;   // then the scalars go through red[] below
+    constexpr bool big_dsh = DOUT == 0 || DOUT == 4;        // only four outputs can fill dsh: the other kinds never get there
     float part[6] = {0.f, 0.f, 0.f, 0.f, lsum[0], lsum[1]};
-    if (bx == 0 && tail_free) {
+    if (bx == 0 && (tail_free || big_dsh)) {
         for (int e = threadIdx.x; e < B; e += 256) {
 #pragma unroll
             for (int o = 0; o < 4; ++o)
@@ -1124,8 +1125,29 @@ __device__ __forceinline__ void head_bwd_loss_body(const HeadBwdArgs& hb, int bx
         }
         return;
     }
-    // B * dout too large for the LDS tail (B = 1024 with four outputs): serial sums by single threads
-    if (need_w && threadIdx.x >= 128 && threadIdx.x < 128 + (unsigned)dout) {
+    // B * dout too large for the LDS tail (B = 1024 with four outputs): the same sums in the same order (per-thread partial
+    // sums, DPP sums inside the 16-lane rows, the 16 row sums one after the other) with red[], which the dW3 reduction above
+    // has finished with, in the tail's place.  (One thread adding the 1024 terms one after the other was 5.7 times the error
+    // of torch's tree sum on the tanh-Gaussian head's bias gradient: tests/test_update_pieces_gpu.py.)
+    float* r0 = &red[0][0][0];          // 1024 floats: two arrays of 256
+    if constexpr (big_dsh) {
+        __syncthreads();
+        if (need_w) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float rsum = row16_sum(part[k]);
+                if ((threadIdx.x & 15) == 0) r0[k * 16 + (threadIdx.x >> 4)] = rsum;
+            }
+            __syncthreads();
+            if ((int)threadIdx.x < dout) {
+                float tot = 0.f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tot += r0[threadIdx.x * 16 + r];
+                db3[g * dout + threadIdx.x] = tot;
+            }
+        }
+    } else if (need_w && threadIdx.x >= 128 && threadIdx.x < 128 + (unsigned)dout) {
+        // (one or two outputs: B <= 1024 keeps them on the tail path above; never reached, the code of these kinds as it was)
         const int o = threadIdx.x - 128;
         float sum = 0.f;
         for (int b = 0; b < B; ++b) sum += dsh[b * dout + o];
@@ -1133,7 +1155,6 @@ __device__ __forceinline__ void head_bwd_loss_body(const HeadBwdArgs& hb, int bx
     }
     if (!want_loss) return;
     __syncthreads();
-    float* r0 = &red[0][0][0];          // 1024 floats: two arrays of 256
     r0[threadIdx.x] = lsum[0];
     r0[256 + threadIdx.x] = lsum[1];
     __syncthreads();
