@@ -877,6 +877,12 @@ int rrl_ens_train_epoch_big(const rrl_ens_t* m, int n_seg, const rrl_adam_seg_t*
  *                                          penalty == NULL, i.e. the mean-only form)
  *   rrl_policy_heads_fwd_multi_packed      rrl_policy_heads_fwd_multi  (n[s] heads heads[s][0..n[s]), either kind; flat grid
  *                                          over (seed, member, row block))
+ * SQRL's constraint-sampling acting pass (declared with its descriptor below):
+ *   rrl_sqrl_act_packed                    rrl_sqrl_act                (args[s]: seed s's stand-alone descriptor; n[s] workgroups
+ *                                          per seed, its tick advanced by the last of them; ONE k for all seeds of a call --
+ *                                          the row tiles ceil(k / 16) are a template parameter of the kernel -- else RRL_EINVAL;
+ *                                          n, weights, eps_safe, seed, tick, n_part, injected draws and the diagnostics that are
+ *                                          asked for may differ by seed)
  * Every seed's arguments are checked before anything is stored or launched (the stand-alone entry's codes); S outside
  * 1 .. 16 or a NULL array: RRL_EINVAL.  S == 1 is the stand-alone launch.
  * ------------------------------------------------------------------------------------------ */
@@ -953,6 +959,10 @@ typedef struct {
 } rrl_sqrl_act_t;
 long long rrl_sqrl_scratch_floats(long long n, int k);
 int rrl_sqrl_act(const rrl_sqrl_act_t* a, void* stream);
+/* ... for S seeds in one launch (the packed-launch table above): args[s] is checked as rrl_sqrl_act checks it (same codes), all
+ * seeds before anything is stored or launched; S outside 1 .. 16, args == NULL or seeds that differ in k: RRL_EINVAL; S == 1 is
+ * rrl_sqrl_act(args). */
+int rrl_sqrl_act_packed(int S, const rrl_sqrl_act_t* args, void* stream);
 
 #ifdef __cplusplus
 }

@@ -51,7 +51,7 @@ EXPORTS = [
     "rrl_plan_supported", "rrl_plan_pack_floats", "rrl_plan_scratch_floats", "rrl_plan_pack", "rrl_plan_cost",
     "rrl_ens_train_supported", "rrl_ens_scratch_floats", "rrl_ens_train_grad", "rrl_ens_train_epoch",
     "rrl_ens_train_big_supported", "rrl_ens_big_scratch_floats", "rrl_ens_train_grad_big", "rrl_ens_train_epoch_big",
-    "rrl_sqrl_scratch_floats", "rrl_sqrl_act",
+    "rrl_sqrl_scratch_floats", "rrl_sqrl_act", "rrl_sqrl_act_packed",
 ]
 
 class RRLError(RuntimeError):
@@ -378,6 +378,7 @@ def _declare(lib):
                                          vp, ll, ll, ll, vp, vp, vp]),
         "rrl_sqrl_scratch_floats": (ll, [ll, ci]),
         "rrl_sqrl_act": (ci, [C.POINTER(rrl_sqrl_act_t), vp]),
+        "rrl_sqrl_act_packed": (ci, [ci, C.POINTER(rrl_sqrl_act_t), vp]),
         "rrl_episode_log_append": (ci, [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(rrl_episode_log_t), vp]),
     }
     for name, (res, args) in sig.items():

@@ -11,6 +11,7 @@
 // The matrix helpers are restated from plan_kernels.hip, not shared: a shared header would move that file's kernels.
 #include "rrl_device.hpp"
 #include "rrl_host.hpp"
+#include "pack.hpp"
 
 using namespace rrl_host;
 
@@ -43,6 +44,7 @@ static_assert(kOffW % 2 == 0 && kOffPick % 2 == 0, "doubles and 64-bit masks nee
 
 struct SqrlArgs {
     int k, n_part;
+    int n;                                    // the envs of THIS learner (a packed grid holds several learners' workgroups)
     long long part_stride;
     const float *obs, *head, *scale, *bias;
     const float *W1, *b1, *W2p, *b2, *W3, *b3;
@@ -227,20 +229,19 @@ __device__ __forceinline__ void score_pass(float* lds, const SqrlArgs& a, long l
         if (a.q) a.q[env * k + c] = qm;
         if (a.z) {
             a.z[env * k + c] = zv[0];
-            a.z[((long long)gridDim.x + env) * k + c] = zv[1];
+            a.z[((long long)a.n + env) * k + c] = zv[1];
         }
     }
     // xs and qpart are rewritten only behind the next pass's barriers
 }
 
+// One env of one learner: candidates, scores, pick.  Stated once; the stand-alone and the packed kernel differ only in where
+// `a` and `env` come from (and in how many workgroups share the learner's tick).
 // NT = row tiles of 16 candidates (ceil(k / 16), 1..8): pass 0 takes min(NT, 4) of them, pass 1 the rest
 template <int NT>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
-void sqrl_act_kernel(const SqrlArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
+__device__ __forceinline__ void sqrl_env(const SqrlArgs& a, const long long env, float* lds) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const long long env = blockIdx.x;
     const int k = a.k;
     const uint64_t ctr = rrl::effective_counter(a.counter, a.counter_dev);
 
@@ -372,22 +373,76 @@ void sqrl_act_kernel(const SqrlArgs a) {
         if (a.cstar) a.cstar[env] = cs;
         if (a.n_safe) a.n_safe[env] = n_safe;
     }
+}
+
+template <int NT>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void sqrl_act_kernel(const SqrlArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    sqrl_env<NT>(a, blockIdx.x, lds);
     rrl::advance_counter(a.counter_dev, a.counter_inc);
+}
+
+// S learners side by side (pack.hpp): workgroup b serves env `local` of seed s, on seed s's own argument block.  All seeds share
+// NT (one k per call).  A seed's tick is advanced by the last of ITS n workgroups -- the grid's size says nothing about it --
+// and a padding workgroup of a pinned mapping leaves before it touches anything, the ticket included.
+template <int NT>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void sqrl_act_pack_kernel(const SqrlArgs* __restrict__ blocks, rrl_pack::Idx ix) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int s, local;
+    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
+    SqrlArgs a = blocks[s];
+    rrl_pack::to_global_all(a.obs, a.head, a.scale, a.bias, a.W1, a.b1, a.W2p, a.b2, a.W3, a.b3, a.counter_dev, a.eps_in, a.u_in,
+                            a.action, a.q, a.logp, a.cand, a.z, a.pick, a.cstar, a.n_safe);
+    sqrl_env<NT>(a, local, lds);
+    rrl::advance_counter_blocks(a.counter_dev, a.counter_inc, unsigned(a.n));
+}
+
+template <class K>
+int grant_lds(K kernel, bool& done) {       // > 64 KB of LDS has to be granted explicitly, once per kernel
+    if (done) return RRL_OK;
+    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes) != hipSuccess) {
+        last_hip_error = int(hipGetLastError());
+        return RRL_ELAUNCH;
+    }
+    done = true;
+    return RRL_OK;
 }
 
 template <int NT>
 int launch(const SqrlArgs& a, int n, hipStream_t st) {
     static bool lds_set = false;
-    if (!lds_set) {       // > 64 KB of LDS has to be granted explicitly
-        if (hipFuncSetAttribute((const void*)sqrl_act_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes) !=
-            hipSuccess) {
-            last_hip_error = int(hipGetLastError());
-            return RRL_ELAUNCH;
-        }
-        lds_set = true;
-    }
+    const int rc = grant_lds(sqrl_act_kernel<NT>, lds_set);
+    if (rc != RRL_OK) return rc;
     hipLaunchKernelGGL(sqrl_act_kernel<NT>, dim3((unsigned)n), dim3(kThreads), kLdsBytes, st, a);
     return check_launch();
+}
+
+template <int NT>
+int launch_pack(const rrl_pack::Plan& plan, hipStream_t st) {
+    static bool lds_set = false;
+    const int rc = grant_lds(sqrl_act_pack_kernel<NT>, lds_set);
+    if (rc != RRL_OK) return rc;
+    hipLaunchKernelGGL(sqrl_act_pack_kernel<NT>, dim3((unsigned)plan.grid), dim3(kThreads), kLdsBytes, st,
+                       (const SqrlArgs*)plan.dev, plan.ix);
+    return check_launch();
+}
+
+// the checks of one descriptor, before any launch (rrl_hip.h)
+int check_desc(const rrl_sqrl_act_t* p) {
+    if (!p || !p->obs || !p->head || !p->scale || !p->bias || !p->W1 || !p->b1 || !p->W2p || !p->b2 || !p->W3 || !p->b3 ||
+        !p->action || p->n <= 0 || p->H != kH || p->d_obs != 2 || p->d_act != 2 || p->n_part < 1 || p->n_part > 4 ||
+        (reinterpret_cast<uintptr_t>(p->W2p) & 15))
+        return RRL_EINVAL;
+    if (p->k < 1 || p->k > kMaxK || (long long)p->n * p->k >= (1LL << 32)) return RRL_ERANGE;
+    return RRL_OK;
+}
+
+SqrlArgs block_of(const rrl_sqrl_act_t* p) {
+    return SqrlArgs{p->k, p->n_part, p->n, p->part_stride, p->obs, p->head, p->scale, p->bias, p->W1, p->b1, p->W2p, p->b2,
+                    p->W3, p->b3, p->eps_safe, p->seed, p->counter, p->counter_dev, p->counter_inc, p->eps_in, p->u_in,
+                    p->action, p->q, p->logp, p->cand, p->z, p->pick, p->cstar, p->n_safe};
 }
 
 }  // namespace
@@ -401,14 +456,9 @@ long long rrl_sqrl_scratch_floats(long long n, int k) {
 }
 
 int rrl_sqrl_act(const rrl_sqrl_act_t* p, void* stream) {
-    if (!p || !p->obs || !p->head || !p->scale || !p->bias || !p->W1 || !p->b1 || !p->W2p || !p->b2 || !p->W3 || !p->b3 ||
-        !p->action || p->n <= 0 || p->H != kH || p->d_obs != 2 || p->d_act != 2 || p->n_part < 1 || p->n_part > 4 ||
-        (reinterpret_cast<uintptr_t>(p->W2p) & 15))
-        return RRL_EINVAL;
-    if (p->k < 1 || p->k > kMaxK || (long long)p->n * p->k >= (1LL << 32)) return RRL_ERANGE;
-    const SqrlArgs a{p->k, p->n_part, p->part_stride, p->obs, p->head, p->scale, p->bias, p->W1, p->b1, p->W2p, p->b2,
-                     p->W3, p->b3, p->eps_safe, p->seed, p->counter, p->counter_dev, p->counter_inc, p->eps_in, p->u_in,
-                     p->action, p->q, p->logp, p->cand, p->z, p->pick, p->cstar, p->n_safe};
+    const int rc = check_desc(p);
+    if (rc != RRL_OK) return rc;
+    const SqrlArgs a = block_of(p);
     hipStream_t st = (hipStream_t)stream;
     switch ((p->k + 15) / 16) {
         case 1: return launch<1>(a, p->n, st);
@@ -419,6 +469,51 @@ int rrl_sqrl_act(const rrl_sqrl_act_t* p, void* stream) {
         case 6: return launch<6>(a, p->n, st);
         case 7: return launch<7>(a, p->n, st);
         default: return launch<8>(a, p->n, st);
+    }
+}
+
+int rrl_sqrl_act_packed(int S, const rrl_sqrl_act_t* args, void* stream) {
+    if (S <= 0 || S > rrl_pack::kMaxSeeds || !args) return RRL_EINVAL;
+    for (int s = 0; s < S; ++s) {               // every seed's descriptor is checked before anything is stored or launched
+        const int rc = check_desc(args + s);
+        if (rc != RRL_OK) return rc;
+    }
+    for (int s = 1; s < S; ++s)                 // NT is a template parameter of the kernel: one k per call
+        if (args[s].k != args[0].k) return RRL_EINVAL;
+    // one seed: the packed launch IS the solo launch (argument block in the kernel arguments, no plan)
+    if (S == 1) return rrl_sqrl_act(args, stream);
+    rrl_pack::Key key;
+    key.pod(11);
+    key.pod(S);
+    key.add(args, sizeof(rrl_sqrl_act_t) * S);
+    hipStream_t st = (hipStream_t)stream;
+    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    if (!plan) {
+        std::vector<SqrlArgs> blocks(S);
+        rrl_pack::Idx ix;
+        ix.S = S;
+        ix.first[0] = 0;
+        for (int s = 0; s < S; ++s) {           // one workgroup per env, as in the solo kernel
+            if (args[s].n > INT32_MAX / rrl_pack::kMaxSeeds) return RRL_ERANGE;     // the grid of any mapping fits an int
+            blocks[s] = block_of(args + s);
+            ix.first[s + 1] = ix.first[s] + args[s].n;
+        }
+        for (int s = S; s < rrl_pack::kMaxSeeds; ++s) ix.first[s + 1] = ix.first[S];
+        plan = rrl_pack::store(key, blocks.data(), sizeof(SqrlArgs) * S, st);
+        if (!plan) return rrl_pack::store_error();
+        plan->grid = rrl_pack::finish(ix);
+        plan->ix = ix;
+        plan->i0 = (args[0].k + 15) / 16;
+    }
+    switch (plan->i0) {
+        case 1: return launch_pack<1>(*plan, st);
+        case 2: return launch_pack<2>(*plan, st);
+        case 3: return launch_pack<3>(*plan, st);
+        case 4: return launch_pack<4>(*plan, st);
+        case 5: return launch_pack<5>(*plan, st);
+        case 6: return launch_pack<6>(*plan, st);
+        case 7: return launch_pack<7>(*plan, st);
+        default: return launch_pack<8>(*plan, st);
     }
 }
 

@@ -1125,19 +1125,43 @@ def run_packed(exp_cfg, rank=0, world_size=1):
     SAC and the reward penalty (no recovery, no baseline flags), LR (--DGD_constraints --update_nu), RSPO (--DGD_constraints
     --nu_schedule) and RCPO (--RCPO), each of the last three with or without --use_recovery --MF_recovery and on the fused
     update path (RRL_FAST_BASELINES=1).  RSPO packs with the multiplier the solo lock-step loop uses throughout,
-    nu_schedule(1) (the lock-step loop has no episode index; the recorded launches carry that value).  Not packed: SQRL's
-    --use_constraint_sampling (its acting pass is module code, or under RRL_FAST_SQRL=1 a launch without a packed form), model-based recovery,
-    --dp_mode env_shard, --resume / --checkpoint_every."""
+    nu_schedule(1) (the lock-step loop has no episode index; the recorded launches carry that value).  SQRL
+    (--DGD_constraints --use_constraint_sampling --update_nu) packs under RRL_PACK_SQRL=1 (opt-in): its update is LR's, its
+    acting pass one rrl_sqrl_act_packed launch -- so it needs that pass on the kernel (RRL_FAST_SQRL=1 with
+    RRL_FAST_BASELINES=1, no recovery policy, --hidden_size 256: fast_update.sqrl_acting_path) and at most 8 seeds (the launch
+    reads Q_risk's fragment-order W2 copy, which packed runs keep up to 8 seeds); every seed's run_stats.pkl then records
+    vector_rules["sqrl_acting"] == "hip".  Not packed: --use_constraint_sampling without that switch or outside those limits
+    (its acting pass is module code then), model-based recovery, --dp_mode env_shard, --resume / --checkpoint_every."""
     import copy
-    from .fast_update import fast_baselines_enabled, fast_path_supported, uses_baseline_terms
+    from .fast_update import (fast_baselines_enabled, fast_path_supported, fast_sqrl_enabled, pack_sqrl_enabled, sqrl_acting_path,
+                              uses_baseline_terms)
     from .packed import PackedLoop
     S = int(exp_cfg.seeds_per_gpu)
     if exp_cfg.num_envs < 2:
         raise ValueError("--seeds_per_gpu needs the lock-step loop (--num_envs > 1)")
-    if exp_cfg.use_constraint_sampling:
+    if exp_cfg.use_constraint_sampling and not pack_sqrl_enabled():
         raise ValueError("--seeds_per_gpu does not pack --use_constraint_sampling (SQRL's acting pass draws its candidates "
                          "through module code, or with RRL_FAST_SQRL=1 in a launch that has no packed form): run the seeds "
                          "one at a time")
+    if exp_cfg.use_constraint_sampling:
+        # RRL_PACK_SQRL=1: the acting pass has to be the kernel (one packed launch), within the limits of its packed form
+        missing = None
+        if not fast_sqrl_enabled():
+            missing = "the acting pass on the rrl_sqrl_act kernel: set RRL_FAST_SQRL=1"
+        elif not fast_baselines_enabled():
+            missing = "the fused update path: set RRL_FAST_BASELINES=1"
+        elif exp_cfg.use_recovery:
+            missing = "a run without a recovery policy (--use_recovery takes SQRL's acting pass through module code)"
+        elif int(exp_cfg.hidden_size) != 256:
+            missing = "--hidden_size 256 (the kernel's Q_risk width; got %d)" % int(exp_cfg.hidden_size)
+        elif sqrl_acting_path(exp_cfg) != "hip":
+            missing = ("the acting pass on the rrl_sqrl_act kernel (Gaussian policy, fixed alpha, --target_update_interval 1, "
+                       "no --no_fast_path, RRL_W2_FRAG not 0)")
+        elif S > PackedLoop.FRAG_MAX_SEEDS:
+            missing = ("at most %d seeds per GPU (its launch reads Q_risk's fragment-order W2 copy, which packed runs keep up "
+                       "to that many seeds; got %d)" % (PackedLoop.FRAG_MAX_SEEDS, S))
+        if missing:
+            raise ValueError("--seeds_per_gpu with RRL_PACK_SQRL=1 packs --use_constraint_sampling only with " + missing)
     if exp_cfg.use_recovery and not exp_cfg.MF_recovery:
         raise ValueError("--seeds_per_gpu packs the model-free recovery policy only (--use_recovery needs --MF_recovery; "
                          "model-based recovery and --Q_sampling_recovery run one seed at a time)")

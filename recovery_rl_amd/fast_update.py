@@ -1103,6 +1103,12 @@ def fast_sqrl_enabled():
     return os.environ.get("RRL_FAST_SQRL", "0") == "1"
 
 
+def pack_sqrl_enabled():
+    """RRL_PACK_SQRL=1: --seeds_per_gpu packs SQRL (--use_constraint_sampling), its acting pass as one rrl_sqrl_act_packed
+    launch (opt-in; needs sqrl_acting_path(cfg) == "hip" and at most 8 seeds: experiment.run_packed)."""
+    return os.environ.get("RRL_PACK_SQRL", "0") == "1"
+
+
 def sqrl_acting_path(cfg):
     """Where the training actions of --use_constraint_sampling come from: "hip" (FastActor.act_sqrl) under RRL_FAST_SQRL=1
     on the fused path (RRL_FAST_BASELINES=1), without a recovery policy, at hidden width 256; else "modules"

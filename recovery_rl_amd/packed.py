@@ -33,6 +33,12 @@ class PackedLoop:
             raise ValueError("1 .. %d seeds per GPU" % self.MAX_SEEDS)
         self.loops = list(loops)
         self.S = len(loops)
+        # SQRL's packed acting launch (rrl_sqrl_act_packed) reads Q_risk's fragment-order W2 copy, which the nets give up
+        # beyond FRAG_MAX_SEEDS (below)
+        if self.S > self.FRAG_MAX_SEEDS and any(getattr(loop, "sqrl_hip", False) for loop in self.loops):
+            raise ValueError("SQRL's constraint-sampling acting pass (rrl_sqrl_act_packed) packs at most %d seeds per GPU: it "
+                             "reads the fragment-order W2 copy of Q_risk, which packed runs keep up to that many seeds only "
+                             "(got %d)" % (self.FRAG_MAX_SEEDS, self.S))
         self.online_qrisk = online_qrisk
         self.lib = _lib.load()
         self.graph = None
@@ -124,6 +130,10 @@ class PackedLoop:
                 n = (C.c_int * S)(*[op[2] for op in ops])
                 heads = (p(_lib.rrl_policy_head_t) * S)(*[C.cast(op[1], p(_lib.rrl_policy_head_t)) for op in ops])
                 stages.append((self.lib.rrl_policy_heads_fwd_multi_packed, (S, n, heads), ops))
+            elif kind == "sqrl":
+                # SQRL's constraint-sampling acting pass: every seed's stand-alone descriptor, one launch (one k for all seeds)
+                args = (_lib.rrl_sqrl_act_t * S)(*[op[1] for op in ops])
+                stages.append((self.lib.rrl_sqrl_act_packed, (S, args), ops))
             elif kind == "step":
                 env_name, env_kind = ops[0][1], ops[0][2]
                 assert all(op[1] == env_name and op[2] == env_kind for op in ops), "one env per packed run"
@@ -145,7 +155,7 @@ class PackedLoop:
         """Kernel launches of one packed iteration: a head + hidden backward stage is ONE launch when its stacks share a loss
         class and there are at most PAIR_MAX_SEEDS seeds (rrl_mlp_backward_pair_multi_packed: tile form up to two seeds,
         block form beyond), two otherwise; per-seed calls count once per seed; every other kind (the comparison algorithms'
-        "adam_duals", "penalty" and "heads" included) is one launch."""
+        "adam_duals", "penalty" and "heads" and SQRL's acting launch "sqrl" included) is one launch."""
         total = 0
         for fn, args, ops in self.stages:
             if ops[0][0] == "pair_bwd":
