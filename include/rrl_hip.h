@@ -964,6 +964,45 @@ int rrl_sqrl_act(const rrl_sqrl_act_t* a, void* stream);
  * rrl_sqrl_act(args). */
 int rrl_sqrl_act_packed(int S, const rrl_sqrl_act_t* args, void* stream);
 
+/* --------------------------------------------------------------------------------------------
+ * Q-sampling recovery.  Replaces QRiskWrapper.select_action (recovery_rl/qrisk.py:214-225: --Q_sampling_recovery draws 1000
+ * uniform actions and executes the one with the smallest Q_risk) for the envs whose recovery gate fired.  Per env e with
+ * mask == NULL || mask[e] != 0:
+ *   candidate  b = Philox (seed, row e k + c, RRL_STREAM_QSAMPLE, counter + tick); u_0, u_1 = the open-unit doubles of its low
+ *              and high 64 bits (the pairing of the maze reset); a_j = float(double(lo_j) + (double(hi_j) - double(lo_j)) u_j):
+ *              double arithmetic without contraction, rounded once.  With cand_in the candidate is cand_in[e, c].
+ *   score      as rrl_sqrl_act: z_h = head h of Q_risk on [obs_e | a_ec], exact-f32 MFMA; q = max(sigmoid z_0, sigmoid z_1),
+ *              NaN propagates
+ *   pick       argmin_c q: the lowest index wins ties and NaN counts as the smallest (torch.argmin); action[e] = a[e, pick]
+ * Nothing of an env whose gate did not fire is written (no action, no diagnostic), and its workgroups leave before they read
+ * a weight.  Two kernels: n x ceil(k / 128) workgroups score up to 128 candidates each (two 64-row passes, the tile of
+ * rrl_sqrl_act) and leave a partial (smallest q, its index, that candidate) in `scratch`; a small second kernel folds an env's
+ * partials in ascending chunk order with a strict <, writes action / pick, and does tick += counter_inc -- once per call,
+ * whatever the mask holds; the score kernel only reads the tick (the ticket word of counter_dev is not used).
+ * Weights as rrl_sqrl_act_t.  Checks before any launch: NULL descriptor or required pointer (obs, lo, hi, W1 .. b3, scratch,
+ * action), n <= 0, H != 256, d_obs or d_act != 2, misaligned W2p: RRL_EINVAL; k outside 1..1024 or n k >= 2^32: RRL_ERANGE
+ * (an invalid field wins).  rrl_qsample_scratch_floats(n, k) = 4 n ceil(k / 128), with the same range checks.
+ * ------------------------------------------------------------------------------------------ */
+enum { RRL_STREAM_QSAMPLE = 11 };   /* Q-sampling recovery candidates */
+typedef struct {
+    int n, k;                       /* envs; candidates per env, 1..1024 (the reference: 1000) */
+    int H, d_obs, d_act;            /* 256, 2, 2 */
+    const float* obs;               /* [n, 2] */
+    const uint8_t* mask;            /* nullable [n]: the recovery gate; NULL = every env */
+    const float *lo, *hi;           /* [2] action box on the device */
+    const float *W1, *b1, *W2p, *b2, *W3, *b3;   /* as rrl_sqrl_act_t */
+    uint64_t seed, counter;
+    uint64_t* counter_dev;          /* nullable {tick, unused} */
+    uint64_t counter_inc;
+    const float* cand_in;           /* nullable [n, k, 2]: replaces the draws */
+    float* scratch;                 /* [rrl_qsample_scratch_floats(n, k)] */
+    float* action;                  /* [n, 2]: written for gated envs only */
+    float *q, *z, *cand;            /* nullable diagnostics [n,k], [2,n,k], [n,k,2]; gated envs only */
+    int32_t* pick;                  /* nullable diagnostic [n]; gated envs only */
+} rrl_qsample_act_t;
+long long rrl_qsample_scratch_floats(long long n, int k);
+int rrl_qsample_act(const rrl_qsample_act_t* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
 HIP_SOURCES = ["nav_kernels.hip", "replay_kernels.hip", "maze_kernels.hip", "cem_kernels.hip",
                "mlp_kernels.hip", "mlp_fwd_kernels.hip", "update_kernels.hip", "log_kernels.hip", "plan_kernels.hip", "ens_train_kernels.hip",
-               "ens_train_big_kernels.hip", "sqrl_kernels.hip"]
+               "ens_train_big_kernels.hip", "sqrl_kernels.hip", "qsample_kernels.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-ffp-contract=off", "-Wall", "-Wno-unused-function",
                "-Wno-bitwise-instead-of-logical"]
@@ -52,6 +52,7 @@ EXPORTS = [
     "rrl_ens_train_supported", "rrl_ens_scratch_floats", "rrl_ens_train_grad", "rrl_ens_train_epoch",
     "rrl_ens_train_big_supported", "rrl_ens_big_scratch_floats", "rrl_ens_train_grad_big", "rrl_ens_train_epoch_big",
     "rrl_sqrl_scratch_floats", "rrl_sqrl_act", "rrl_sqrl_act_packed",
+    "rrl_qsample_scratch_floats", "rrl_qsample_act",
 ]
 
 class RRLError(RuntimeError):
@@ -297,6 +298,16 @@ class rrl_sqrl_act_t(C.Structure):
         (n, C.c_void_p) for n in ("eps_in", "u_in", "scratch", "action", "q", "logp", "cand", "z", "pick", "cstar", "n_safe")]
 
 
+STREAM_QSAMPLE = 11
+
+
+class rrl_qsample_act_t(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n", "k", "H", "d_obs", "d_act")] + [
+        (n, C.c_void_p) for n in ("obs", "mask", "lo", "hi", "W1", "b1", "W2p", "b2", "W3", "b3")] + [
+        ("seed", C.c_uint64), ("counter", C.c_uint64), ("counter_dev", C.c_void_p), ("counter_inc", C.c_uint64)] + [
+        (n, C.c_void_p) for n in ("cand_in", "scratch", "action", "q", "z", "cand", "pick")]
+
+
 _lib = None
 
 
@@ -379,6 +390,8 @@ def _declare(lib):
         "rrl_sqrl_scratch_floats": (ll, [ll, ci]),
         "rrl_sqrl_act": (ci, [C.POINTER(rrl_sqrl_act_t), vp]),
         "rrl_sqrl_act_packed": (ci, [ci, C.POINTER(rrl_sqrl_act_t), vp]),
+        "rrl_qsample_scratch_floats": (ll, [ll, ci]),
+        "rrl_qsample_act": (ci, [C.POINTER(rrl_qsample_act_t), vp]),
         "rrl_episode_log_append": (ci, [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(rrl_episode_log_t), vp]),
     }
     for name, (res, args) in sig.items():

@@ -158,6 +158,8 @@ def loop_state(loop):
            "num_constraint_violations": loop.num_constraint_violations}
     if getattr(loop, "sqrl_hip", False):
         out["sqrl_tick"] = _cpu(loop.sqrl_actor().sqrl_tick)     # the rrl_sqrl_act acting pass's Philox tick (RRL_FAST_SQRL=1)
+    if getattr(loop, "qsample_hip", False):
+        out["qsample_tick"] = _cpu(loop.qsample_actor().qsample_tick)     # the rrl_qsample_act acting pass's tick (RRL_FAST_QSAMPLE=1)
     log = loop.episode_log
     if log is not None:
         out["episode_log"] = {"ep_len": _cpu(log.ep_len), "ep_ret": _cpu(log.ep_ret), "ep_viol": _cpu(log.ep_viol),
@@ -178,6 +180,8 @@ def load_loop_state(loop, sd):
     loop.graph = None                                   # captured graphs hold the old stream position
     if "sqrl_tick" in sd:
         loop.sqrl_actor().sqrl_tick.copy_(sd["sqrl_tick"])
+    if "qsample_tick" in sd:
+        loop.qsample_actor().qsample_tick.copy_(sd["qsample_tick"])
     if loop.episode_log is not None and "episode_log" in sd:
         log, e = loop.episode_log, sd["episode_log"]
         for f in ("ep_len", "ep_ret", "ep_viol", "ep_rec", "state"):
@@ -250,6 +254,10 @@ def load_experiment_state(exp, sd):
         raise ValueError("checkpoint and run disagree on SQRL's acting pass: the checkpoint was written with the %s path, this "
                          "run takes the %s path (RRL_FAST_SQRL=1 with RRL_FAST_BASELINES=1 selects the kernel)"
                          % (("kernel", "module") if "sqrl_tick" in sd["loop"] else ("module", "kernel")))
+    if ("qsample_tick" in sd["loop"]) != bool(getattr(exp.loop, "qsample_hip", False)):
+        raise ValueError("checkpoint and run disagree on the acting pass of --Q_sampling_recovery: the checkpoint was written "
+                         "with the %s path, this run takes the %s path (RRL_FAST_QSAMPLE=1 selects the kernel)"
+                         % (("kernel", "module") if "qsample_tick" in sd["loop"] else ("module", "kernel")))
     if ("mpc" in sd) != (exp.recovery_policy is not None):
         raise ValueError("checkpoint and run disagree on model-based recovery")
     load_agent_state(exp.agent, sd["agent"])

@@ -78,6 +78,10 @@ class VectorLoop:
         from .fast_update import sqrl_acting_path
         self.sqrl_hip = bool(getattr(agent, "fast", None) is not None and sqrl_acting_path(cfg) == "hip"
                              and agent.fast.qrisk.w2p is not None)
+        # the acting pass of --Q_sampling_recovery on the rrl_qsample_act kernels (RRL_FAST_QSAMPLE=1, fast_update.qsample_acting_path)
+        from .fast_update import qsample_acting_path
+        self.qsample_hip = bool(getattr(agent, "fast", None) is not None and qsample_acting_path(cfg) == "hip"
+                                and agent.fast.qrisk.w2p is not None)
         self._graph_ahead = False
         # vectorisation rule 5: at N > 1 an env's CEM warm start does not survive its episode (MPC.forget_plans)
         self.forget_plans = bool(recovery_policy is not None and self.n > 1 and hasattr(recovery_policy, "forget_plans")
@@ -147,10 +151,22 @@ class VectorLoop:
             self._actor.sqrl_seed = int(self.cfg.seed) & 0xFFFFFFFFFFFFFFFF
         return self._actor
 
+    def qsample_actor(self):
+        """The FastActor of the rrl_qsample_act acting pass (qsample_hip): it owns the pass's device tick, the seed is the loop's."""
+        if self._actor is None:
+            from .fast_update import FastActor
+            self._actor = FastActor(self.agent.fast, self.n)
+        self._actor.qsample_seed = int(self.cfg.seed) & 0xFFFFFFFFFFFFFFFF
+        return self._actor
+
     def act(self, obs, random_actions=False, train=True):
         """Batched get_action (experiment.py:546-577): (task action, executed action, recovery)."""
         cfg = self.cfg
         fast = getattr(self.agent, "fast", None)
+        if self.qsample_hip and train and not random_actions and obs.shape[0] == self.n:
+            # task action and the Q_risk gate on the fused kernels, then the gated envs' 1000 uniform candidates scored and the
+            # argmin taken by one rrl_qsample_act call (qrisk.py:214-225); ungated envs cost nothing
+            return self.qsample_actor().act_qsample(obs, cfg.eps_safe)
         if self.sqrl_hip and train and not random_actions and obs.shape[0] == self.n:
             # SQRL's 100 candidates per env scored and picked by one kernel (sac.py:139-161; no recovery policy here)
             action = self.sqrl_actor().act_sqrl(obs, cfg.eps_safe)
@@ -638,6 +654,9 @@ class Experiment:
         if exp_cfg.use_constraint_sampling:
             # which code draws, scores and picks SQRL's candidates in the training loop (RRL_FAST_SQRL=1: the kernel)
             self.vector_rules["sqrl_acting"] = "hip" if self.loop.sqrl_hip else "modules"
+        if exp_cfg.use_recovery and exp_cfg.Q_sampling_recovery and not exp_cfg.MF_recovery:
+            # which code draws and scores the 1000 candidates of Q-sampling recovery in the training loop (RRL_FAST_QSAMPLE=1: the kernels)
+            self.vector_rules["qsample_acting"] = "hip" if self.loop.qsample_hip else "modules"
 
     # -- setup -----------------------------------------------------------------------------------
     def experiment_setup(self):
@@ -692,7 +711,8 @@ class Experiment:
         # run_stats.pkl ("vector_rules") and the checkpoint
         self.vector_rules = {"demo_share": share if share > 0 else 0.0, "pinned_demonstrations": int(pinned),
                              **{k: self.vector_rules[k] for k in ("update_path", "replay_capacities", "cover_rows_limit",
-                                                                   "buffers_cover_the_run", "plan_warm_start", "sqrl_acting")
+                                                                   "buffers_cover_the_run", "plan_warm_start", "sqrl_acting",
+                                                                   "qsample_acting")
                                 if k in self.vector_rules}}
         if cfg.num_envs > 1:
             print("Q_risk batch: %s (--demo_share; 0 = the reference's single uniform draw, replay_memory.py:54-72)"

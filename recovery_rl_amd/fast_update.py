@@ -948,6 +948,13 @@ class FastActor:
         # SQRL constraint sampling (act_sqrl): Philox seed (the loop sets its own) and the device tick {tick, ticket}
         self.sqrl_seed = int(getattr(fast.agent, "seed", 0)) & 0xFFFFFFFFFFFFFFFF
         self.sqrl_tick = torch.zeros(2, dtype=torch.int64, device=dev)
+        # Q-sampling recovery (act_qsample): seed and device tick likewise, the action box on the device, the launch's scratch
+        self.qsample_seed = self.sqrl_seed
+        self.qsample_tick = torch.zeros(2, dtype=torch.int64, device=dev)
+        ac = getattr(fast.qr, "ac_space", None)
+        self.qsample_box = None if ac is None else tuple(
+            torch.as_tensor(b, dtype=torch.float32, device=dev).contiguous() for b in (ac.low, ac.high))
+        self._qsample_scratch = None
 
     # -- two of the three forwards of act(defer_select=True) as riders of the Q_risk update's launches -----------------------
     def ride_policy(self, obs):
@@ -1065,6 +1072,36 @@ class FastActor:
         _lib.check(f.lib.rrl_sqrl_act(C.byref(a), _lib.current_stream()), "rrl_sqrl_act")
         return self.task_action
 
+    def act_qsample(self, obs, eps_safe, k=1000, cand=None, diag=None):
+        """Q-sampling recovery (QRiskWrapper.select_action, qrisk.py:214-225) for the n envs on the fused kernels: the sequence of
+        act_gate -- the task policy's forward and head, the Q_risk gate -- which leaves task_action, real_action = task_action
+        and recovery, then ONE rrl_qsample_act call on the gated envs: k uniform candidates from the action box on the
+        actor's own Philox stream and device tick, the twin Q_risk on each, the argmin into real_action.
+        -> (task action, executed action, recovery u8[n]); persistent buffers.  `cand` [n, k, 2] f32 injects the candidates,
+        `diag` = {name: tensor} asks for the launch's diagnostic outputs (q, z, cand, pick) -- tests."""
+        f, n = self.f, self.n
+        assert obs.shape == (n, 2) and obs.is_contiguous()
+        w2p = f.qrisk.w2_packed()
+        if w2p is None or f.qrisk.H != 256:
+            raise _lib.RRLError("rrl_qsample_act needs Q_risk at hidden width 256 with its fragment-order W2 copy")
+        self.act_gate(obs, eps_safe)
+        floats = int(f.lib.rrl_qsample_scratch_floats(n, k))
+        if floats < 0:
+            _lib.check(floats, "rrl_qsample_scratch_floats")
+        if self._qsample_scratch is None or self._qsample_scratch.numel() < floats:
+            self._qsample_scratch = torch.empty(max(floats, 1), dtype=torch.float32, device=f.dev)
+        lo, hi = self.qsample_box
+        p, P, d = _lib.ptr, f.qrisk.p, diag or {}
+        a = _lib.rrl_qsample_act_t(n=n, k=k, H=f.qrisk.H, d_obs=2, d_act=2, obs=p(obs), mask=p(self.recovery), lo=p(lo), hi=p(hi),
+                                   W1=p(P["W1"]), b1=p(P["b1"]), W2p=p(w2p), b2=p(P["b2"]), W3=p(P["W3"]), b3=p(P["b3"]),
+                                   seed=self.qsample_seed, counter=0, counter_dev=p(self.qsample_tick), counter_inc=1,
+                                   cand_in=p(cand), scratch=p(self._qsample_scratch), action=p(self.real_action),
+                                   **{name: p(t) for name, t in d.items()})
+        self._qsample_args = a           # keeps the argument block alive until the launch has been issued (and for profiles/)
+        record("qsample", a)
+        _lib.check(f.lib.rrl_qsample_act(C.byref(a), _lib.current_stream()), "rrl_qsample_act")
+        return self.task_action, self.real_action, self.recovery
+
     def act_gate(self, obs, eps_safe, noise=None):
         """Task action + recovery gate for a controller that acts elsewhere (model-based recovery: MPC.act on the gated rows):
         -> (task action [n,2], recovery u8[n]); persistent buffers."""
@@ -1115,6 +1152,22 @@ def sqrl_acting_path(cfg):
     (SAC._sqrl_action), which evaluation, the one-state call and every other configuration keep."""
     hip = (fast_sqrl_enabled() and fast_baselines_enabled() and bool(cfg.use_constraint_sampling)
            and not cfg.use_recovery and int(cfg.hidden_size) == 256 and fast_path_supported(cfg)
+           and not getattr(cfg, "no_fast_path", False) and os.environ.get("RRL_W2_FRAG", "1") != "0")
+    return "hip" if hip else "modules"
+
+
+def fast_qsample_enabled():
+    """RRL_FAST_QSAMPLE=1: the acting pass of --Q_sampling_recovery on the rrl_qsample_act kernels (opt-in; qsample_acting_path)."""
+    return os.environ.get("RRL_FAST_QSAMPLE", "0") == "1"
+
+
+def qsample_acting_path(cfg):
+    """Where the recovery actions of --use_recovery --Q_sampling_recovery come from in the training loop: "hip"
+    (FastActor.act_qsample) under RRL_FAST_QSAMPLE=1 on the fused path at hidden width 256; else "modules"
+    (QRiskWrapper.select_action), which evaluation, the one-state call and every other configuration keep.  --MF_recovery wins
+    over --Q_sampling_recovery in the module code, so it does here."""
+    hip = (fast_qsample_enabled() and bool(cfg.use_recovery) and bool(cfg.Q_sampling_recovery) and not cfg.MF_recovery
+           and not cfg.use_constraint_sampling and int(cfg.hidden_size) == 256 and fast_path_supported(cfg)
            and not getattr(cfg, "no_fast_path", False) and os.environ.get("RRL_W2_FRAG", "1") != "0")
     return "hip" if hip else "modules"
 
