@@ -883,6 +883,12 @@ int rrl_ens_train_epoch_big(const rrl_ens_t* m, int n_seg, const rrl_adam_seg_t*
  *                                          the row tiles ceil(k / 16) are a template parameter of the kernel -- else RRL_EINVAL;
  *                                          n, weights, eps_safe, seed, tick, n_part, injected draws and the diagnostics that are
  *                                          asked for may differ by seed)
+ * The Q-sampling recovery acting call (declared with its descriptors below):
+ *   rrl_qsample_act_packed                 rrl_qsample_act / rrl_qsample_act_gated   (args[s], gates[s] or gates == NULL; the
+ *                                          score kernel gives seed s its n[s] ceil(k[s] / 128) workgroups, the fold kernel one
+ *                                          thread per env; the tick of seed s is advanced by the fold thread of ITS env 0; the
+ *                                          chunk count is not a template parameter, so k may differ by seed, as may n, weights,
+ *                                          eps_safe, seed, tick, injected candidates and the diagnostics that are asked for)
  * Every seed's arguments are checked before anything is stored or launched (the stand-alone entry's codes); S outside
  * 1 .. 16 or a NULL array: RRL_EINVAL.  S == 1 is the stand-alone launch.
  * ------------------------------------------------------------------------------------------ */
@@ -1002,6 +1008,33 @@ typedef struct {
 } rrl_qsample_act_t;
 long long rrl_qsample_scratch_floats(long long n, int k);
 int rrl_qsample_act(const rrl_qsample_act_t* a, void* stream);
+
+/* The same call with the recovery gate evaluated inside it, from Q_risk(s, a_task) as a stack forward left it: the launches of
+ * rrl_recovery_select (and of the sum of the partials before it) disappear, and the acting pass is made of launches that have
+ * packed forms.  a->mask must be NULL.  recovery[e] = max(sigmoid z0, sigmoid z1) > eps_safe with z_h the f32 sum of the n_part
+ * partials in order -- the device helper of rrl_recovery_select and of rrl_step_push_t.sel_*, same bits, NaN included.  Every
+ * workgroup of the score kernel evaluates its env's gate first (the 2 n_part partials, requested as 8 loads: partial 0 stands
+ * in for an absent one) and leaves if it did not fire; the fold kernel
+ * writes, for EVERY env, recovery_out[e], task_out[e] (if asked) and action[e] = the pick of a gated env, else the env's task
+ * action: together what rrl_recovery_select followed by rrl_qsample_act leave.  Diagnostics for gated envs only; the tick
+ * advances once per call.  Checks, before any launch: the descriptor's (same codes); g, g->z, g->task_action or
+ * g->recovery_out NULL, n_part outside 1..4, ld_task < 2 or odd, a->mask given: RRL_EINVAL (wins over RRL_ERANGE). */
+typedef struct {
+    const float* z;           /* [2, n] pre-sigmoid twin Q_risk(s, a_task): n_part partial sums part_stride floats apart */
+    int n_part;               /* 1..4, summed in the fixed order every consumer of a stack output uses */
+    long long part_stride;
+    float eps_safe;
+    const float* task_action; /* row e at task_action + e * ld_task; ld_task >= 2 and even */
+    int ld_task;
+    float* task_out;          /* nullable [n, 2]: the task action, as rrl_recovery_select's task_out */
+    uint8_t* recovery_out;    /* [n]: the gate, as rrl_recovery_select writes it */
+} rrl_qsample_gate_t;
+int rrl_qsample_act_gated(const rrl_qsample_act_t* a, const rrl_qsample_gate_t* g, void* stream);
+/* ... and for S seeds in two launches (the packed-launch table above).  gates == NULL: every seed uses its own mask, as
+ * rrl_qsample_act; otherwise gates[s] is seed s's gate.  Every seed is checked as the stand-alone entry checks it (same
+ * codes), all before anything is stored or launched; S outside 1 .. 16 or args == NULL: RRL_EINVAL; a seed with more than
+ * INT32_MAX / 16 score workgroups: RRL_ERANGE; S == 1 is the stand-alone (or gated) call. */
+int rrl_qsample_act_packed(int S, const rrl_qsample_act_t* args, const rrl_qsample_gate_t* gates, void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,15 @@ Two measurements per share:
     quantile of Q_risk(obs, task action) that gates that share when the graph is captured (0: eps_safe = 1, 1: eps_safe = -1);
     the share the timed replays really gated is recorded beside the time (the envs move and Q_risk trains).
 Rates are against the FLOPs the algorithm needs for the GATED rows (267 264 per candidate row of the twin 4-256-256-1
-network) and against the rows executed with the padding of the last chunk to 16-row tiles."""
+network) and against the rows executed with the padding of the last chunk to 16-row tiles.
+
+    python profiles/qsample_iteration.py --packed [--seeds 2,4,8] [--out profiles/packed_qsample.json]
+
+Seed packing of this line (RRL_PACK_QSAMPLE=1: the gate evaluated inside the qsample call, the call as one
+rrl_qsample_act_packed stage): the captured iteration at eps_safe = 1 (nothing gated) and -1 (everything gated), the two
+shares that are exact under graph replay -- the parent's path solo (RRL_FAST_QSAMPLE=1 alone), the gated form solo, and the
+packed iteration of S seeds, as a multiple of S parent-path solo iterations.  Legs with their own learners, alternated in one
+process; the realised share is recorded per round."""
 import argparse
 import ctypes as C
 import json
@@ -42,10 +50,10 @@ def time_it(fn, iters):
     return (time.perf_counter() - t0) / iters * 1e3
 
 
-def build(path, envs, dev):
+def build(path, envs, dev, seed=1):
     """One loop on `path`: hip = RRL_FAST_QSAMPLE=1 (read when the loop is built), modules = the switch unset."""
     cfg = arg_utils.get_args(["--env-name", "navigation1", "--cuda", "--gamma_safe", "0.8", "--eps_safe", "0.3", "--hidden_size",
-                              "256", "--num_envs", str(envs), "--seed", "1", "--num_unsafe_transitions", "4000",
+                              "256", "--num_envs", str(envs), "--seed", str(seed), "--num_unsafe_transitions", "4000",
                               "--use_recovery", "--Q_sampling_recovery"])
     saved = os.environ.pop("RRL_FAST_QSAMPLE", None)
     if path == "hip":
@@ -114,14 +122,85 @@ def set_share(loop, share):
     return eps
 
 
+class gate_in_launch:
+    """RRL_PACK_QSAMPLE for the loops built inside the block (VectorLoop reads it once, when it is built)."""
+
+    def __init__(self, on):
+        self.on = on
+
+    def __enter__(self):
+        self.saved = os.environ.pop("RRL_PACK_QSAMPLE", None)
+        if self.on:
+            os.environ["RRL_PACK_QSAMPLE"] = "1"
+
+    def __exit__(self, *exc):
+        os.environ.pop("RRL_PACK_QSAMPLE", None)
+        if self.saved is not None:
+            os.environ["RRL_PACK_QSAMPLE"] = self.saved
+
+
+def packed_main(a):
+    from recovery_rl_amd.packed import PackedLoop
+    dev = torch.device("cuda:0")
+    seeds = [int(x) for x in a.seeds.split(",")]
+    with gate_in_launch(False):
+        parent = build("hip", a.envs, dev)
+    with gate_in_launch(True):
+        gated = build("hip", a.envs, dev)
+        members = [build("hip", a.envs, dev, seed=1 + s) for s in range(max(seeds))]
+    assert not parent.qsample_gated and gated.qsample_gated and all(m.qsample_gated for m in members)
+    share_of = lambda loop: float(loop._last_recovery.float().mean())
+    res = {}
+    for name, eps in (("0", 1.0), ("1", -1.0)):
+        for loop in [parent, gated] + members:
+            loop.cfg.eps_safe = eps
+        parent.capture(online_qrisk=True)
+        gated.capture(online_qrisk=True)
+        out = {"eps_safe": eps, "parent_solo_ms": [], "parent_solo_share": [], "gated_solo_ms": [], "gated_solo_share": []}
+        for S in seeds:
+            packed = PackedLoop(members[:S], online_qrisk=True)
+            packed.capture()
+            kinds = [op[0] for op in packed.tapes[0]]
+            assert kinds.count("qsample") == 1 and "unsupported" not in kinds
+            key = "packed_S%d" % S
+            out[key + "_ms"], out[key + "_share"], out[key + "_launches"] = [], [], packed.launches
+            for _ in range(a.rounds):                  # alternating with the two solo legs
+                out["parent_solo_ms"].append(time_it(parent.replay, a.iters))
+                out["parent_solo_share"].append(share_of(parent))
+                out["gated_solo_ms"].append(time_it(gated.replay, a.iters))
+                out["gated_solo_share"].append(share_of(gated))
+                out[key + "_ms"].append(time_it(packed.replay, a.iters))
+                out[key + "_share"].append([share_of(loop) for loop in packed.loops])
+            packed.close()
+        solo = sorted(out["parent_solo_ms"])[len(out["parent_solo_ms"]) // 2]
+        out["parent_solo_median_ms"] = solo
+        out["parent_solo_spread"] = (max(out["parent_solo_ms"]) - min(out["parent_solo_ms"])) / solo
+        out["gated_solo_over_parent"] = sorted(out["gated_solo_ms"])[len(out["gated_solo_ms"]) // 2] / solo
+        for S in seeds:
+            ms = sorted(out["packed_S%d_ms" % S])[a.rounds // 2]
+            out["packed_S%d_over_S_solo" % S] = ms / (S * solo)
+            out["packed_S%d_env_steps_per_s" % S] = S * a.envs / ms * 1e3
+        res[name] = json.loads(json.dumps(out), parse_float=lambda x: round(float(x), 4))
+        print(name, json.dumps(res[name]), flush=True)
+    res["setup"] = {"envs_per_seed": a.envs, "hidden": 256, "batch": 256, "k": K, "iters": a.iters, "rounds": a.rounds,
+                    "seeds": seeds, "device": torch.cuda.get_device_name(0)}
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--packed", action="store_true")
+    ap.add_argument("--seeds", default="2,4,8")
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.packed:
+        return packed_main(a)
     dev = torch.device("cuda:0")
     paths = ("hip", "modules")
     loops = {path: build(path, a.envs, dev) for path in paths}

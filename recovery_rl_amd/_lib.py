@@ -52,7 +52,7 @@ EXPORTS = [
     "rrl_ens_train_supported", "rrl_ens_scratch_floats", "rrl_ens_train_grad", "rrl_ens_train_epoch",
     "rrl_ens_train_big_supported", "rrl_ens_big_scratch_floats", "rrl_ens_train_grad_big", "rrl_ens_train_epoch_big",
     "rrl_sqrl_scratch_floats", "rrl_sqrl_act", "rrl_sqrl_act_packed",
-    "rrl_qsample_scratch_floats", "rrl_qsample_act",
+    "rrl_qsample_scratch_floats", "rrl_qsample_act", "rrl_qsample_act_gated", "rrl_qsample_act_packed",
 ]
 
 class RRLError(RuntimeError):
@@ -308,6 +308,11 @@ class rrl_qsample_act_t(C.Structure):
         (n, C.c_void_p) for n in ("cand_in", "scratch", "action", "q", "z", "cand", "pick")]
 
 
+class rrl_qsample_gate_t(C.Structure):
+    _fields_ = [("z", C.c_void_p), ("n_part", C.c_int), ("part_stride", C.c_longlong), ("eps_safe", C.c_float),
+                ("task_action", C.c_void_p), ("ld_task", C.c_int), ("task_out", C.c_void_p), ("recovery_out", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -392,6 +397,8 @@ def _declare(lib):
         "rrl_sqrl_act_packed": (ci, [ci, C.POINTER(rrl_sqrl_act_t), vp]),
         "rrl_qsample_scratch_floats": (ll, [ll, ci]),
         "rrl_qsample_act": (ci, [C.POINTER(rrl_qsample_act_t), vp]),
+        "rrl_qsample_act_gated": (ci, [C.POINTER(rrl_qsample_act_t), C.POINTER(rrl_qsample_gate_t), vp]),
+        "rrl_qsample_act_packed": (ci, [ci, C.POINTER(rrl_qsample_act_t), C.POINTER(rrl_qsample_gate_t), vp]),
         "rrl_episode_log_append": (ci, [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(rrl_episode_log_t), vp]),
     }
     for name, (res, args) in sig.items():

@@ -177,6 +177,7 @@ struct Key {
 struct Plan {
     void* dev = nullptr;          // S argument blocks in device memory
     Idx ix{};
+    Idx ix2{};                    // block ranges of a call's second kernel (rrl_qsample_act_packed: the fold kernel)
     int grid = 0;                 // workgroups of the launch (finish(ix))
     int i0 = 0, i1 = 0;           // kernel-specific launch parameters (path, threads, ...)
     size_t z0 = 0;                // ... dynamic LDS bytes

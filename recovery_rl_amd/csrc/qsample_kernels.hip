@@ -9,7 +9,13 @@
 // (smallest q, its index, that candidate) in scratch; a second small kernel folds an env's P partials in ascending chunk
 // order, writes action[e] and advances the tick.
 //
+// The recovery gate is either a mask (rrl_qsample_act) or evaluated here from Q_risk's partial last-layer sums
+// (rrl_qsample_act_gated: what rrl_recovery_select would have left, without its launch and without the summing one).  Both
+// kernels have ONE body (score_chunk, fold_envs); the stand-alone and the packed kernels (rrl_qsample_act_packed: S seeds side
+// by side, pack.hpp) differ only in where the argument block and (env, chunk) come from.
+//
 // The matrix helpers are restated from sqrl_kernels.hip, not shared: a shared header would move that file's kernels.
+#include "pack.hpp"
 #include "rrl_device.hpp"
 #include "rrl_host.hpp"
 
@@ -52,7 +58,38 @@ struct QsArgs {
     float* action;
     float *q, *z, *cand;
     int32_t* pick;
+    // the gate evaluated in the launch (gz != nullptr; mask is NULL then): rrl_qsample_gate_t
+    const float* gz;
+    int g_np;
+    long long g_ps;
+    float g_eps;
+    const float* g_task;
+    int g_ld;
+    float* g_task_out;
+    uint8_t* g_rec_out;
 };
+
+// Did env e's gate fire?  From the mask, or from the 2 x n_part partial sums of z = Q_risk(s, a_task), added in the fixed order
+// every consumer of a stack output uses.  Eight loads are requested together whatever n_part is -- partial 0 is read again in
+// the place of an absent one, as the env-step kernel does: no branch between the requests.
+__device__ __forceinline__ bool gate_fired(const QsArgs& a, long long e) {
+    if (!a.gz) return !a.mask || a.mask[e];
+    const int np = a.g_np;
+    float zu[4], zw[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long long off = np > k ? k * a.g_ps : 0;
+        zu[k] = a.gz[off + e];
+        zw[k] = a.gz[off + a.n + e];
+    }
+    float z0 = zu[0], z1 = zw[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) {
+        z0 = np > k ? z0 + zu[k] : z0;
+        z1 = np > k ? z1 + zw[k] : z1;
+    }
+    return rrl::recovery_gate(z0, z1, a.g_eps);
+}
 
 __device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -218,14 +255,12 @@ __device__ __forceinline__ void score_pass(float* lds, const QsArgs& a, long lon
     // xs and qpart are rewritten only behind the next pass's barriers
 }
 
-// Workgroup b = env b / P, chunk b % P: candidates [128 chunk, 128 chunk + rows) of a gated env -> scratch[b] = its partial.
-// Reads the tick, never writes it (the fold kernel advances it).
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
-void qsample_score_kernel(const QsArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const long long env = blockIdx.x / (unsigned)a.P;
-    if (a.mask && !a.mask[env]) return;           // the gate did not fire: nothing read, nothing written
-    const int chunk = blockIdx.x % (unsigned)a.P;
+// Workgroup b = env b / P, chunk b % P of the argument block's own grid: candidates [128 chunk, 128 chunk + rows) of a gated
+// env -> scratch[b] = its partial.  Reads the tick, never writes it (the fold kernel advances it).
+__device__ __forceinline__ void score_chunk(const QsArgs& a, unsigned b, float* lds) {
+    const long long env = b / (unsigned)a.P;
+    if (!gate_fired(a, env)) return;              // the gate did not fire: nothing else read, nothing written
+    const int chunk = b % (unsigned)a.P;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int k = a.k, c0 = chunk * kChunk;
@@ -298,7 +333,7 @@ void qsample_score_kernel(const QsArgs a) {
             }
         }
         if (lane == 0) {
-            float* part = a.scratch + (size_t)blockIdx.x * kPartial;
+            float* part = a.scratch + (size_t)b * kPartial;
             part[0] = best;
             part[1] = __int_as_float(c0 + bidx);
             part[2] = lds[kOffCand + 2 * bidx];
@@ -307,11 +342,50 @@ void qsample_score_kernel(const QsArgs a) {
     }
 }
 
-// One thread per env: the P partials of a gated env in ascending chunk order (strict <: the lowest index wins), then
-// action[e] (and pick[e]).  Thread 0 advances the tick: every reader of it ran in the score kernel before this one.
-__global__ __launch_bounds__(kBlock) void qsample_fold_kernel(const QsArgs a) {
-    for (long long e = (long long)blockIdx.x * kBlock + threadIdx.x; e < a.n; e += (long long)gridDim.x * kBlock) {
-        if (a.mask && !a.mask[e]) continue;
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void qsample_score_kernel(const QsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    score_chunk(a, blockIdx.x, lds);
+}
+
+// The copied argument block's pointers as global ones (pack.hpp: to_global)
+__device__ __forceinline__ void globalize(QsArgs& a) {
+    rrl_pack::to_global_all(a.obs, a.mask, a.lo, a.hi, a.W1, a.b1, a.W2p, a.b2, a.W3, a.b3, a.counter_dev, a.cand_in, a.scratch,
+                            a.action, a.q, a.z, a.cand, a.pick, a.gz, a.g_task, a.g_task_out, a.g_rec_out);
+}
+
+// S learners side by side (pack.hpp): workgroup b serves workgroup `local` of seed s's own n x P grid, on seed s's argument
+// block.  A padding workgroup of a pinned mapping leaves before it touches anything.
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void qsample_score_pack_kernel(const QsArgs* __restrict__ blocks, rrl_pack::Idx ix) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int s, local;
+    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
+    QsArgs a = blocks[s];
+    globalize(a);
+    score_chunk(a, unsigned(local), lds);
+}
+
+// One thread per env (envs e0, e0 + stride, ...): with a gate in the launch, recovery_out[e], task_out[e] and the task action
+// into action[e] of an env whose gate did not fire -- what rrl_recovery_select leaves; then the P partials of a gated env in
+// ascending chunk order (strict <: the lowest index wins) -> action[e] (and pick[e]).  The thread of env 0 advances the tick:
+// every reader of it ran in the score kernel before this one.
+__device__ __forceinline__ void fold_envs(const QsArgs& a, long long e0, long long stride) {
+    for (long long e = e0; e < a.n; e += stride) {
+        const bool rec = gate_fired(a, e);
+        if (a.gz) {
+            const float t0 = a.g_task[e * a.g_ld], t1 = a.g_task[e * a.g_ld + 1];
+            a.g_rec_out[e] = uint8_t(rec);
+            if (a.g_task_out) {
+                a.g_task_out[2 * e] = t0;
+                a.g_task_out[2 * e + 1] = t1;
+            }
+            if (!rec) {
+                a.action[2 * e] = t0;
+                a.action[2 * e + 1] = t1;
+            }
+        }
+        if (!rec) continue;
         const float* part = a.scratch + (size_t)e * a.P * kPartial;
         float best = part[0];
         int p = 0;
@@ -324,7 +398,21 @@ __global__ __launch_bounds__(kBlock) void qsample_fold_kernel(const QsArgs a) {
         a.action[2 * e + 1] = part[p * kPartial + 3];
         if (a.pick) a.pick[e] = __float_as_int(part[p * kPartial + 1]);
     }
-    if (a.counter_dev && a.counter_inc && blockIdx.x == 0 && threadIdx.x == 0) a.counter_dev[0] += a.counter_inc;
+    if (e0 == 0 && a.counter_dev && a.counter_inc) a.counter_dev[0] += a.counter_inc;
+}
+
+__global__ __launch_bounds__(kBlock) void qsample_fold_kernel(const QsArgs a) {
+    fold_envs(a, (long long)blockIdx.x * kBlock + threadIdx.x, (long long)gridDim.x * kBlock);
+}
+
+// ... of S seeds: seed s's envs on its own ix.first[s + 1] - ix.first[s] = grid_for(n[s]) workgroups; its tick is advanced by the
+// thread of ITS env 0, whatever the grid holds
+__global__ __launch_bounds__(kBlock) void qsample_fold_pack_kernel(const QsArgs* __restrict__ blocks, rrl_pack::Idx ix) {
+    int s, local;
+    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
+    QsArgs a = blocks[s];
+    globalize(a);
+    fold_envs(a, (long long)local * kBlock + threadIdx.x, (long long)(ix.first[s + 1] - ix.first[s]) * kBlock);
 }
 
 int chunks_of(int k) { return (k + kChunk - 1) / kChunk; }
@@ -338,6 +426,60 @@ int check_desc(const rrl_qsample_act_t* p) {
     return RRL_OK;
 }
 
+// ... and of a gate given with it
+int check_both(const rrl_qsample_act_t* p, const rrl_qsample_gate_t* g) {
+    const int rc = check_desc(p);
+    if (!g || rc == RRL_EINVAL) return rc;
+    if (p->mask || !g->z || !g->task_action || !g->recovery_out || g->n_part < 1 || g->n_part > 4 || g->ld_task < 2 ||
+        (g->ld_task & 1))
+        return RRL_EINVAL;                  // an invalid field wins over a size out of range
+    return rc;
+}
+
+QsArgs block_of(const rrl_qsample_act_t* p, const rrl_qsample_gate_t* g) {
+    QsArgs a{p->k, p->n, chunks_of(p->k), p->obs, p->mask, p->lo, p->hi, p->W1, p->b1, p->W2p, p->b2, p->W3, p->b3,
+             p->seed, p->counter, p->counter_dev, p->counter_inc, p->cand_in, p->scratch, p->action, p->q, p->z,
+             p->cand, p->pick, nullptr, 1, 0, 0.f, nullptr, 2, nullptr, nullptr};
+    if (g) {
+        a.gz = g->z;
+        a.g_np = g->n_part;
+        a.g_ps = g->part_stride;
+        a.g_eps = g->eps_safe;
+        a.g_task = g->task_action;
+        a.g_ld = g->ld_task;
+        a.g_task_out = g->task_out;
+        a.g_rec_out = g->recovery_out;
+    }
+    return a;
+}
+
+template <class K>
+int grant_lds(K kernel, bool& done) {       // > 64 KB of LDS has to be granted explicitly, once per kernel
+    if (done) return RRL_OK;
+    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes) != hipSuccess) {
+        last_hip_error = int(hipGetLastError());
+        return RRL_ELAUNCH;
+    }
+    done = true;
+    return RRL_OK;
+}
+
+// rrl_qsample_act (g == nullptr) and rrl_qsample_act_gated: the two kernels on one argument block
+int launch_solo(const rrl_qsample_act_t* p, const rrl_qsample_gate_t* g, void* stream) {
+    const int rc = check_both(p, g);
+    if (rc != RRL_OK) return rc;
+    const QsArgs a = block_of(p, g);
+    hipStream_t st = (hipStream_t)stream;
+    static bool lds_set = false;
+    const int rl = grant_lds(qsample_score_kernel, lds_set);
+    if (rl != RRL_OK) return rl;
+    hipLaunchKernelGGL(qsample_score_kernel, dim3((unsigned)((long long)a.n * a.P)), dim3(kThreads), kLdsBytes, st, a);
+    const int rs = check_launch();
+    if (rs != RRL_OK) return rs;
+    hipLaunchKernelGGL(qsample_fold_kernel, dim3((unsigned)grid_for(a.n)), dim3(kBlock), 0, st, a);
+    return check_launch();
+}
+
 }  // namespace
 
 extern "C" {
@@ -348,26 +490,62 @@ long long rrl_qsample_scratch_floats(long long n, int k) {
     return n * chunks_of(k) * kPartial;      // one partial per workgroup of the score kernel
 }
 
-int rrl_qsample_act(const rrl_qsample_act_t* p, void* stream) {
-    const int rc = check_desc(p);
-    if (rc != RRL_OK) return rc;
-    const QsArgs a{p->k, p->n, chunks_of(p->k), p->obs, p->mask, p->lo, p->hi, p->W1, p->b1, p->W2p, p->b2, p->W3, p->b3,
-                   p->seed, p->counter, p->counter_dev, p->counter_inc, p->cand_in, p->scratch, p->action, p->q, p->z,
-                   p->cand, p->pick};
-    hipStream_t st = (hipStream_t)stream;
-    static bool lds_set = false;            // > 64 KB of LDS has to be granted explicitly, once
-    if (!lds_set) {
-        if (hipFuncSetAttribute((const void*)qsample_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes) !=
-            hipSuccess) {
-            last_hip_error = int(hipGetLastError());
-            return RRL_ELAUNCH;
-        }
-        lds_set = true;
+int rrl_qsample_act(const rrl_qsample_act_t* p, void* stream) { return launch_solo(p, nullptr, stream); }
+
+int rrl_qsample_act_gated(const rrl_qsample_act_t* p, const rrl_qsample_gate_t* g, void* stream) {
+    if (!g) return RRL_EINVAL;
+    return launch_solo(p, g, stream);
+}
+
+int rrl_qsample_act_packed(int S, const rrl_qsample_act_t* args, const rrl_qsample_gate_t* gates, void* stream) {
+    if (S <= 0 || S > rrl_pack::kMaxSeeds || !args) return RRL_EINVAL;
+    for (int s = 0; s < S; ++s) {               // every seed is checked before anything is stored or launched
+        const int rc = check_both(args + s, gates ? gates + s : nullptr);
+        if (rc != RRL_OK) return rc;
     }
-    hipLaunchKernelGGL(qsample_score_kernel, dim3((unsigned)((long long)a.n * a.P)), dim3(kThreads), kLdsBytes, st, a);
+    // one seed: the packed launch IS the solo launch (argument block in the kernel arguments, no plan)
+    if (S == 1) return launch_solo(args, gates, stream);
+    for (int s = 0; s < S; ++s)                 // the grid of any mapping fits an int
+        if ((long long)args[s].n * chunks_of(args[s].k) > INT32_MAX / rrl_pack::kMaxSeeds) return RRL_ERANGE;
+    rrl_pack::Key key;
+    key.pod(12);
+    key.pod(S);
+    key.pod(int(gates != nullptr));
+    key.add(args, sizeof(rrl_qsample_act_t) * S);
+    if (gates) key.add(gates, sizeof(rrl_qsample_gate_t) * S);
+    hipStream_t st = (hipStream_t)stream;
+    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    if (!plan) {
+        std::vector<QsArgs> blocks(S);
+        rrl_pack::Idx ix, fx;                   // block ranges of the score and of the fold kernel
+        ix.S = fx.S = S;
+        ix.first[0] = fx.first[0] = 0;
+        for (int s = 0; s < S; ++s) {
+            const QsArgs& a = blocks[s] = block_of(args + s, gates ? gates + s : nullptr);
+            ix.first[s + 1] = ix.first[s] + a.n * a.P;         // n x ceil(k / 128) workgroups, as in the solo kernel
+            fx.first[s + 1] = fx.first[s] + grid_for(a.n);     // one thread per env
+        }
+        for (int s = S; s < rrl_pack::kMaxSeeds; ++s) {
+            ix.first[s + 1] = ix.first[S];
+            fx.first[s + 1] = fx.first[S];
+        }
+        const int grid = rrl_pack::finish(ix), fold_grid = rrl_pack::finish(fx);
+        plan = rrl_pack::store(key, blocks.data(), sizeof(QsArgs) * S, st);
+        if (!plan) return rrl_pack::store_error();
+        plan->grid = grid;
+        plan->ix = ix;
+        plan->i0 = fold_grid;
+        plan->ix2 = fx;
+    }
+    static bool lds_set = false;
+    const int rc = grant_lds(qsample_score_pack_kernel, lds_set);
+    if (rc != RRL_OK) return rc;
+    hipLaunchKernelGGL(qsample_score_pack_kernel, dim3((unsigned)plan->grid), dim3(kThreads), kLdsBytes, st,
+                       (const QsArgs*)plan->dev, plan->ix);
     const int rs = check_launch();
     if (rs != RRL_OK) return rs;
-    hipLaunchKernelGGL(qsample_fold_kernel, dim3((unsigned)grid_for(a.n)), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(qsample_fold_pack_kernel, dim3((unsigned)plan->i0), dim3(kBlock), 0, st, (const QsArgs*)plan->dev,
+                       plan->ix2);
     return check_launch();
 }
 

@@ -174,6 +174,13 @@ __device__ __forceinline__ float row16_sum(float v) {
     return v;
 }
 
+// The recovery gate (experiment.py:568) from the two pre-sigmoid heads of Q_risk(s, a_task): max(sigmoid z0, sigmoid z1) >
+// eps_safe.  fmaxf drops a NaN head for the other one; both NaN: the comparison is false, no recovery.
+__device__ __forceinline__ bool recovery_gate(float z0, float z1, float eps_safe) {
+    const float q0 = 1.f / (1.f + expf(-z0)), q1 = 1.f / (1.f + expf(-z1));
+    return fmaxf(q0, q1) > eps_safe;
+}
+
 __device__ __forceinline__ uint64_t effective_counter(uint64_t counter, const uint64_t* dev) {
     return dev ? counter + *dev : counter;
 }

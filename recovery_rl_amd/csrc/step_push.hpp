@@ -321,8 +321,7 @@ __device__ __forceinline__ void step_push_body(const StepPushArgs& p, const unsi
                     z0 = np > k ? z0 + zu[k] : z0;
                     z1 = np > k ? z1 + zw[k] : z1;
                 }
-                const float q0 = 1.f / (1.f + expf(-z0)), q1 = 1.f / (1.f + expf(-z1));
-                rec = fmaxf(q0, q1) > p.sel_eps;
+                rec = rrl::recovery_gate(z0, z1, p.sel_eps);
                 float2 ra = ra_in;
                 if (!p.sel_rec_action) {
                     const rrl_policy_head_t& hd = p.sel_rec_head;

@@ -692,7 +692,7 @@ __global__ void recovery_select_kernel(int N, const float* z, float eps_safe, co
                                        uint8_t* recovery, float* task_out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= N) return;
-    const bool rec = fmaxf(sigmoidf(z[b]), sigmoidf(z[N + b])) > eps_safe;
+    const bool rec = rrl::recovery_gate(z[b], z[N + b], eps_safe);
     recovery[b] = uint8_t(rec);
     const float t0 = task_action[(long long)b * ld_task], t1 = task_action[(long long)b * ld_task + 1];
     real_action[2 * b] = rec ? rec_action[2 * b] : t0;

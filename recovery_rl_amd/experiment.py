@@ -82,6 +82,10 @@ class VectorLoop:
         from .fast_update import qsample_acting_path
         self.qsample_hip = bool(getattr(agent, "fast", None) is not None and qsample_acting_path(cfg) == "hip"
                                 and agent.fast.qrisk.w2p is not None)
+        # ... with the recovery gate evaluated inside the qsample call (RRL_PACK_QSAMPLE=1, read once, here: what the loop
+        # runs is what vector_rules records)
+        from .fast_update import pack_qsample_enabled
+        self.qsample_gated = bool(self.qsample_hip and pack_qsample_enabled())
         self._graph_ahead = False
         # vectorisation rule 5: at N > 1 an env's CEM warm start does not survive its episode (MPC.forget_plans)
         self.forget_plans = bool(recovery_policy is not None and self.n > 1 and hasattr(recovery_policy, "forget_plans")
@@ -165,8 +169,9 @@ class VectorLoop:
         fast = getattr(self.agent, "fast", None)
         if self.qsample_hip and train and not random_actions and obs.shape[0] == self.n:
             # task action and the Q_risk gate on the fused kernels, then the gated envs' 1000 uniform candidates scored and the
-            # argmin taken by one rrl_qsample_act call (qrisk.py:214-225); ungated envs cost nothing
-            return self.qsample_actor().act_qsample(obs, cfg.eps_safe)
+            # argmin taken by one rrl_qsample_act call (qrisk.py:214-225); ungated envs cost nothing.  RRL_PACK_QSAMPLE=1: the
+            # gate is evaluated inside that call (three launches, all of kinds the seed packer records)
+            return self.qsample_actor().act_qsample(obs, cfg.eps_safe, gated=self.qsample_gated)
         if self.sqrl_hip and train and not random_actions and obs.shape[0] == self.n:
             # SQRL's 100 candidates per env scored and picked by one kernel (sac.py:139-161; no recovery policy here)
             action = self.sqrl_actor().act_sqrl(obs, cfg.eps_safe)
@@ -208,7 +213,15 @@ class VectorLoop:
         if cfg.MF_recovery or cfg.Q_sampling_recovery:
             qr = self.agent.safety_critic
             eps = self._policy_eps(qr.policy, obs) if (cfg.MF_recovery and self.n > 1) else None
-            rec_action = qr.select_action(obs) if eps is None else qr.select_action(obs, eps=eps)
+            if random_actions and getattr(self, "qsample_gated", False):
+                # the random-action phase of the Q-sampling line under RRL_PACK_QSAMPLE=1: the 1000 candidates per env from the
+                # loop's OWN generator (select_action would draw them from torch's global one, which the seeds of a packed
+                # run share: a seed's trajectory must not depend on what else is in the process)
+                lo, hi = self.qsample_actor().qsample_box
+                cand = lo + (hi - lo) * torch.rand(obs.shape[0], 1000, lo.numel(), device=self.device, generator=self.action_rng)
+                rec_action = qr.select_action(obs, candidates=cand)
+            else:
+                rec_action = qr.select_action(obs) if eps is None else qr.select_action(obs, eps=eps)
         else:
             rec_action = self.recovery_policy.act(obs, 0, mask=recovery)
         real_action = torch.where(recovery.unsqueeze(1), rec_action, action)
@@ -657,6 +670,9 @@ class Experiment:
         if exp_cfg.use_recovery and exp_cfg.Q_sampling_recovery and not exp_cfg.MF_recovery:
             # which code draws and scores the 1000 candidates of Q-sampling recovery in the training loop (RRL_FAST_QSAMPLE=1: the kernels)
             self.vector_rules["qsample_acting"] = "hip" if self.loop.qsample_hip else "modules"
+            if self.loop.qsample_gated:
+                # where the recovery gate of that pass is evaluated (RRL_PACK_QSAMPLE=1: inside the qsample call)
+                self.vector_rules["qsample_gate"] = "in_launch"
 
     # -- setup -----------------------------------------------------------------------------------
     def experiment_setup(self):
@@ -712,7 +728,7 @@ class Experiment:
         self.vector_rules = {"demo_share": share if share > 0 else 0.0, "pinned_demonstrations": int(pinned),
                              **{k: self.vector_rules[k] for k in ("update_path", "replay_capacities", "cover_rows_limit",
                                                                    "buffers_cover_the_run", "plan_warm_start", "sqrl_acting",
-                                                                   "qsample_acting")
+                                                                   "qsample_acting", "qsample_gate")
                                 if k in self.vector_rules}}
         if cfg.num_envs > 1:
             print("Q_risk batch: %s (--demo_share; 0 = the reference's single uniform draw, replay_memory.py:54-72)"
@@ -1150,10 +1166,16 @@ def run_packed(exp_cfg, rank=0, world_size=1):
     acting pass one rrl_sqrl_act_packed launch -- so it needs that pass on the kernel (RRL_FAST_SQRL=1 with
     RRL_FAST_BASELINES=1, no recovery policy, --hidden_size 256: fast_update.sqrl_acting_path) and at most 8 seeds (the launch
     reads Q_risk's fragment-order W2 copy, which packed runs keep up to 8 seeds); every seed's run_stats.pkl then records
-    vector_rules["sqrl_acting"] == "hip".  Not packed: --use_constraint_sampling without that switch or outside those limits
-    (its acting pass is module code then), model-based recovery, --dp_mode env_shard, --resume / --checkpoint_every."""
+    vector_rules["sqrl_acting"] == "hip".  Q-sampling recovery (--use_recovery --Q_sampling_recovery) packs under
+    RRL_PACK_QSAMPLE=1 (opt-in): its acting pass is then a policy forward, a Q_risk forward and one rrl_qsample_act_packed stage
+    that evaluates the recovery gate itself -- so it needs that pass on the kernels (RRL_FAST_QSAMPLE=1, --hidden_size 256, no
+    --MF_recovery: fast_update.qsample_acting_path) and at most 8 seeds; run_stats.pkl records vector_rules["qsample_gate"] ==
+    "in_launch".  Not packed: --use_constraint_sampling and --Q_sampling_recovery without their switches or outside those
+    limits (their acting passes are module code then), model-based recovery, --dp_mode env_shard, --resume /
+    --checkpoint_every."""
     import copy
-    from .fast_update import (fast_baselines_enabled, fast_path_supported, fast_sqrl_enabled, pack_sqrl_enabled, sqrl_acting_path,
+    from .fast_update import (fast_baselines_enabled, fast_path_supported, fast_qsample_enabled, fast_sqrl_enabled,
+                              pack_qsample_enabled, pack_sqrl_enabled, qsample_acting_path, sqrl_acting_path,
                               uses_baseline_terms)
     from .packed import PackedLoop
     S = int(exp_cfg.seeds_per_gpu)
@@ -1182,7 +1204,28 @@ def run_packed(exp_cfg, rank=0, world_size=1):
                        "to that many seeds; got %d)" % (PackedLoop.FRAG_MAX_SEEDS, S))
         if missing:
             raise ValueError("--seeds_per_gpu with RRL_PACK_SQRL=1 packs --use_constraint_sampling only with " + missing)
-    if exp_cfg.use_recovery and not exp_cfg.MF_recovery:
+    qsample = bool(exp_cfg.use_recovery and exp_cfg.Q_sampling_recovery and pack_qsample_enabled())
+    if qsample:
+        # RRL_PACK_QSAMPLE=1: the acting pass has to be the kernels (one packed stage), within the limits of the packed form
+        missing = None
+        if not fast_qsample_enabled():
+            missing = "the acting pass on the rrl_qsample_act kernels: set RRL_FAST_QSAMPLE=1"
+        elif exp_cfg.MF_recovery:
+            missing = ("a run without --MF_recovery (the model-free recovery policy wins over --Q_sampling_recovery, and packs "
+                       "without this switch)")
+        elif exp_cfg.use_constraint_sampling:
+            missing = "a run without --use_constraint_sampling (SQRL's acting pass is another one)"
+        elif int(exp_cfg.hidden_size) != 256:
+            missing = "--hidden_size 256 (the kernels' Q_risk width; got %d)" % int(exp_cfg.hidden_size)
+        elif qsample_acting_path(exp_cfg) != "hip":
+            missing = ("the acting pass on the rrl_qsample_act kernels (Gaussian policy, fixed alpha, --target_update_interval "
+                       "1, no --no_fast_path, RRL_W2_FRAG not 0)")
+        elif S > PackedLoop.FRAG_MAX_SEEDS:
+            missing = ("at most %d seeds per GPU (its launch reads Q_risk's fragment-order W2 copy, which packed runs keep up "
+                       "to that many seeds; got %d)" % (PackedLoop.FRAG_MAX_SEEDS, S))
+        if missing:
+            raise ValueError("--seeds_per_gpu with RRL_PACK_QSAMPLE=1 packs --Q_sampling_recovery only with " + missing)
+    if exp_cfg.use_recovery and not exp_cfg.MF_recovery and not qsample:
         raise ValueError("--seeds_per_gpu packs the model-free recovery policy only (--use_recovery needs --MF_recovery; "
                          "model-based recovery and --Q_sampling_recovery run one seed at a time)")
     if getattr(exp_cfg, "dp_mode", "replicas") != "replicas":

@@ -1072,19 +1072,26 @@ class FastActor:
         _lib.check(f.lib.rrl_sqrl_act(C.byref(a), _lib.current_stream()), "rrl_sqrl_act")
         return self.task_action
 
-    def act_qsample(self, obs, eps_safe, k=1000, cand=None, diag=None):
+    def act_qsample(self, obs, eps_safe, k=1000, cand=None, diag=None, gated=False):
         """Q-sampling recovery (QRiskWrapper.select_action, qrisk.py:214-225) for the n envs on the fused kernels: the sequence of
         act_gate -- the task policy's forward and head, the Q_risk gate -- which leaves task_action, real_action = task_action
         and recovery, then ONE rrl_qsample_act call on the gated envs: k uniform candidates from the action box on the
         actor's own Philox stream and device tick, the twin Q_risk on each, the argmin into real_action.
         -> (task action, executed action, recovery u8[n]); persistent buffers.  `cand` [n, k, 2] f32 injects the candidates,
-        `diag` = {name: tensor} asks for the launch's diagnostic outputs (q, z, cand, pick) -- tests."""
+        `diag` = {name: tensor} asks for the launch's diagnostic outputs (q, z, cand, pick) -- tests.
+        gated (RRL_PACK_QSAMPLE=1, pack_qsample_enabled): the same pass as three calls the launch tape records -- the task
+        policy's forward, Q_risk on [s | a_task] left as partial last-layer sums with the task head evaluated by the stack,
+        and rrl_qsample_act_gated, which evaluates the gate from those sums itself.  Same noise, same Philox stream, same
+        tick, same bits in the three buffers."""
         f, n = self.f, self.n
         assert obs.shape == (n, 2) and obs.is_contiguous()
         w2p = f.qrisk.w2_packed()
         if w2p is None or f.qrisk.H != 256:
             raise _lib.RRLError("rrl_qsample_act needs Q_risk at hidden width 256 with its fragment-order W2 copy")
-        self.act_gate(obs, eps_safe)
+        if gated:
+            gate = self._qsample_gate(obs, eps_safe)
+        else:
+            self.act_gate(obs, eps_safe)
         floats = int(f.lib.rrl_qsample_scratch_floats(n, k))
         if floats < 0:
             _lib.check(floats, "rrl_qsample_scratch_floats")
@@ -1092,15 +1099,42 @@ class FastActor:
             self._qsample_scratch = torch.empty(max(floats, 1), dtype=torch.float32, device=f.dev)
         lo, hi = self.qsample_box
         p, P, d = _lib.ptr, f.qrisk.p, diag or {}
-        a = _lib.rrl_qsample_act_t(n=n, k=k, H=f.qrisk.H, d_obs=2, d_act=2, obs=p(obs), mask=p(self.recovery), lo=p(lo), hi=p(hi),
+        a = _lib.rrl_qsample_act_t(n=n, k=k, H=f.qrisk.H, d_obs=2, d_act=2, obs=p(obs), mask=None if gated else p(self.recovery),
+                                   lo=p(lo), hi=p(hi),
                                    W1=p(P["W1"]), b1=p(P["b1"]), W2p=p(w2p), b2=p(P["b2"]), W3=p(P["W3"]), b3=p(P["b3"]),
                                    seed=self.qsample_seed, counter=0, counter_dev=p(self.qsample_tick), counter_inc=1,
                                    cand_in=p(cand), scratch=p(self._qsample_scratch), action=p(self.real_action),
                                    **{name: p(t) for name, t in d.items()})
         self._qsample_args = a           # keeps the argument block alive until the launch has been issued (and for profiles/)
+        if gated:
+            self._qsample_gate_args = gate
+            record("qsample", a, gate)
+            _lib.check(f.lib.rrl_qsample_act_gated(C.byref(a), C.byref(gate), _lib.current_stream()), "rrl_qsample_act_gated")
+            return self.task_action, self.real_action, self.recovery
         record("qsample", a)
         _lib.check(f.lib.rrl_qsample_act(C.byref(a), _lib.current_stream()), "rrl_qsample_act")
         return self.task_action, self.real_action, self.recovery
+
+    def _qsample_gate(self, obs, eps_safe):
+        """The forwards of act_gate through the entry points the launch tape records, the gate itself left to the qsample
+        call: -> its rrl_qsample_gate_t, reading Q_risk(s, a_task) as this pass's forward leaves it (qr.parts)."""
+        f, n = self.f, self.n
+        noise = f.actor_noise(n)
+        self.pending_select = None
+        f._forwards([(self.pol, obs, dict(save=False))], f.grouped)
+        task_head = self._task_head(noise[0], obs)
+        self.qr.finalize = False                 # the qsample kernels add the partial last-layer sums themselves
+        if f.fuse_heads and self.qr.split:
+            # no head launch: the task action is evaluated by the Q_risk stack that consumes it (and stored in xa)
+            forward_multi([self.qr.forward_desc(self.xa, save=False, in_head=task_head)])
+        else:
+            heads_multi([task_head])
+            forward_multi([self.qr.forward_desc(self.xa, save=False)])
+        z, n_part, ps = self.qr.parts
+        p = _lib.ptr
+        return _lib.rrl_qsample_gate_t(z=p(z), n_part=n_part, part_stride=ps, eps_safe=float(eps_safe),
+                                       task_action=p(self.xa[:, 2:4]), ld_task=4, task_out=p(self.task_action),
+                                       recovery_out=p(self.recovery))
 
     def act_gate(self, obs, eps_safe, noise=None):
         """Task action + recovery gate for a controller that acts elsewhere (model-based recovery: MPC.act on the gated rows):
@@ -1159,6 +1193,13 @@ def sqrl_acting_path(cfg):
 def fast_qsample_enabled():
     """RRL_FAST_QSAMPLE=1: the acting pass of --Q_sampling_recovery on the rrl_qsample_act kernels (opt-in; qsample_acting_path)."""
     return os.environ.get("RRL_FAST_QSAMPLE", "0") == "1"
+
+
+def pack_qsample_enabled():
+    """RRL_PACK_QSAMPLE=1: the acting pass of --Q_sampling_recovery with the recovery gate evaluated inside the qsample call
+    (rrl_qsample_act_gated: three launches the tape records), and --seeds_per_gpu packs that line, its acting call as one
+    rrl_qsample_act_packed stage (opt-in; needs qsample_acting_path(cfg) == "hip" and at most 8 seeds: experiment.run_packed)."""
+    return os.environ.get("RRL_PACK_QSAMPLE", "0") == "1"
 
 
 def qsample_acting_path(cfg):

@@ -39,6 +39,11 @@ class PackedLoop:
             raise ValueError("SQRL's constraint-sampling acting pass (rrl_sqrl_act_packed) packs at most %d seeds per GPU: it "
                              "reads the fragment-order W2 copy of Q_risk, which packed runs keep up to that many seeds only "
                              "(got %d)" % (self.FRAG_MAX_SEEDS, self.S))
+        # ... and so does the Q-sampling recovery call (rrl_qsample_act_packed)
+        if self.S > self.FRAG_MAX_SEEDS and any(getattr(loop, "qsample_hip", False) for loop in self.loops):
+            raise ValueError("the Q-sampling recovery acting pass (rrl_qsample_act_packed) packs at most %d seeds per GPU: it "
+                             "reads the fragment-order W2 copy of Q_risk, which packed runs keep up to that many seeds only "
+                             "(got %d)" % (self.FRAG_MAX_SEEDS, self.S))
         self.online_qrisk = online_qrisk
         self.lib = _lib.load()
         self.graph = None
@@ -134,6 +139,14 @@ class PackedLoop:
                 # SQRL's constraint-sampling acting pass: every seed's stand-alone descriptor, one launch (one k for all seeds)
                 args = (_lib.rrl_sqrl_act_t * S)(*[op[1] for op in ops])
                 stages.append((self.lib.rrl_sqrl_act_packed, (S, args), ops))
+            elif kind == "qsample":
+                # the Q-sampling recovery call with the gate inside it: every seed's descriptor and gate, one stage (k may
+                # differ by seed).  Without a gate (the mask form) the pass before it has launches the tape cannot pack
+                if any(len(op) < 3 for op in ops):
+                    raise _lib.RRLError("launch kind 'qsample' packs with the gate in the launch only (RRL_PACK_QSAMPLE=1)")
+                args = (_lib.rrl_qsample_act_t * S)(*[op[1] for op in ops])
+                gates = (_lib.rrl_qsample_gate_t * S)(*[op[2] for op in ops])
+                stages.append((self.lib.rrl_qsample_act_packed, (S, args, gates), ops))
             elif kind == "step":
                 env_name, env_kind = ops[0][1], ops[0][2]
                 assert all(op[1] == env_name and op[2] == env_kind for op in ops), "one env per packed run"
@@ -155,7 +168,8 @@ class PackedLoop:
         """Kernel launches of one packed iteration: a head + hidden backward stage is ONE launch when its stacks share a loss
         class and there are at most PAIR_MAX_SEEDS seeds (rrl_mlp_backward_pair_multi_packed: tile form up to two seeds,
         block form beyond), two otherwise; per-seed calls count once per seed; every other kind (the comparison algorithms'
-        "adam_duals", "penalty" and "heads" and SQRL's acting launch "sqrl" included) is one launch."""
+        "adam_duals", "penalty" and "heads", SQRL's acting launch "sqrl" and the Q-sampling recovery call "qsample" included) counts
+        as one entry."""
         total = 0
         for fn, args, ops in self.stages:
             if ops[0][0] == "pair_bwd":
