@@ -818,6 +818,8 @@ static int build_stack_group(int n, const rrl_stack_t* st, StackGroup& sg, int& 
                 (h.kind == RRL_HEAD_GAUSS ? !h.eps : (h.kind != RRL_HEAD_STOCH || !h.log_std)) || (h.obs_out && !h.action))
                 return RRL_EINVAL;
             if (!(p.scratch && rrl_mlp3_is_split(p.M, p.H))) return RRL_EINVAL;   // the column-split kernels only
+            // the stochastic head as a launch of its own ignores obs_out (rrl_hip.h): so does the head inside the stack
+            if (h.kind == RRL_HEAD_STOCH) sg.a[k].in_head.obs_out = nullptr;
         }
         sg.partial[k] = p.scratch;
         sg.G[k] = p.G;

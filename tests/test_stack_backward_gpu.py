@@ -17,6 +17,10 @@ SHAPES = {
     "full_tiles_short_K": (1, 128, 64, 2, 4, False),     # full tiles, K = B = 64 is not a panel multiple
     "first_layer_own_launch": (2, 128, 128, 4, 1, False),    # what set_fuse_first(False) runs
     "first_layer_fused": (2, 128, 128, 4, 1, True),          # (dW1, db1) and dx as tile partials
+    # the production shapes the method still admits (the bound below: 2 * 256 * 2 * 256 * 4 * 4 = 2^22) ...
+    "critic_256": (2, 256, 256, 4, 1, True),
+    "policy_256": (1, 256, 256, 2, 4, True),
+    "ragged_batch_256": (2, 256, 200, 4, 1, False),          # ... and --batch_size 200 at that width
 }
 FLAGS = ((True, False), (True, True), (False, True))     # (weight_grads, input_grad)
 SENTINEL = 7.0
