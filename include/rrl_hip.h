@@ -889,8 +889,13 @@ int rrl_ens_train_epoch_big(const rrl_ens_t* m, int n_seg, const rrl_adam_seg_t*
  *                                          thread per env; the tick of seed s is advanced by the fold thread of ITS env 0; the
  *                                          chunk count is not a template parameter, so k may differ by seed, as may n, weights,
  *                                          eps_safe, seed, tick, injected candidates and the diagnostics that are asked for)
- * Every seed's arguments are checked before anything is stored or launched (the stand-alone entry's codes); S outside
- * 1 .. 16 or a NULL array: RRL_EINVAL.  S == 1 is the stand-alone launch.
+ * The evaluation rollout (declared with its descriptor below; outside the iteration, at the seeds' evaluation points):
+ *   rrl_eval_rollout_packed                rrl_eval_rollout            (args[s]; seed s gets its ceil(n[s] / 16) workgroups and
+ *                                          its tick is advanced by the last of them; n, T, env kind, weights, groups, seed, tick
+ *                                          and traces may differ by seed)
+ * Every seed's arguments are checked before anything is stored or launched (the stand-alone entry's codes); a NULL array:
+ * RRL_EINVAL; S outside 1 .. 16: RRL_EINVAL, except from rrl_eval_rollout_packed, which returns RRL_ERANGE for it.  S == 1 is
+ * the stand-alone launch.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
     const rrl_draw_t *first, *second;
@@ -1035,6 +1040,65 @@ int rrl_qsample_act_gated(const rrl_qsample_act_t* a, const rrl_qsample_gate_t* 
  * codes), all before anything is stored or launched; S outside 1 .. 16 or args == NULL: RRL_EINVAL; a seed with more than
  * INT32_MAX / 16 score workgroups: RRL_ERANGE; S == 1 is the stand-alone (or gated) call. */
 int rrl_qsample_act_packed(int S, const rrl_qsample_act_t* args, const rrl_qsample_gate_t* gates, void* stream);
+
+/* --------------------------------------------------------------------------------------------
+ * Policy evaluation as ONE launch.  Replaces Experiment.get_test_rollout (recovery_rl/experiment.py:493-538: one
+ * deterministic-policy episode per env) for n Navigation 1 / 2 envs: reset, then T x (task policy -> Q_risk gate -> recovery
+ * policy -> transition) with the per-env return and flags, no launch boundary inside.  A workgroup owns a tile of 16 envs for
+ * the whole rollout; the networks run on one row tile of the tile of rrl_qsample_act (activations in LDS, W2 in rrl_w2_pack
+ * order, exact-f32 MFMA, k ascending), the env state stays in registers.
+ *   start      reset != 0: pos_i = START + N(0, I), the normal pair of Philox (seed, i, RRL_STREAM_RESET, tick);
+ *              reset == 0: pos_i = pos[i] (read, never written).  tick = counter + counter_dev[0].
+ *   step j     (j = 0 .. T - 1, rows still alive) obs = float(pos);
+ *              task = tanh(mean(obs)) * scale + bias (the Gaussian policy's mean rows, W3 rows 0 .. 1);
+ *              with the Q_risk group: gate = max(sigmoid z0, sigmoid z1) > eps_safe on Q_risk(obs, task), the device helper
+ *              of rrl_recovery_select (same bits); with the recovery group as well: rec = tanh(mean_r(obs)) * rscale + rbias +
+ *              exp(max(rlog_std, min_log_std)) * eps, eps = float of the normal pair of Philox (seed, i, RRL_STREAM_EVAL,
+ *              tick + reset + j), and executed = gate ? rec : task; without it executed = task;
+ *              transition of rrl_nav_step on double(executed) with the noise of (seed, i, RRL_STREAM_STEP, tick + reset + j).
+ *   results    ret[i] = f32 sum in step order of the rewards of the steps taken while alive, success[i] / violation[i] = OR
+ *              over those steps, steps[i] = their number; a row dies after a step whose done (success | constraint) is set.
+ *   tick       counter_dev[0] += T + reset by the last workgroup (counter_dev = {tick, ticket}), what reset() and T step()
+ *              calls of the eager env advance it by.
+ * A workgroup without a live row leaves the step loop, the recovery policy's forward is skipped while no row of the tile is
+ * gated, rows >= n write nothing: none of this changes a bit of any output.  Trace buffers (each nullable) are written at
+ * step j for the rows alive before it and left untouched otherwise.
+ * Checks before any launch, without a device: NULL descriptor or required pointer (the task policy's eight, ret, success,
+ * violation, steps), H != 256, d_obs or d_act != 2, n <= 0, unknown env_kind, a Q_risk group or a recovery group given in
+ * part, a recovery group without the Q_risk group, a W2p not 16-byte aligned, reset == 0 without pos: RRL_EINVAL; T outside
+ * 1..4096 or n > 2^22: RRL_ERANGE (an invalid field wins).
+ * ------------------------------------------------------------------------------------------ */
+enum { RRL_STREAM_EVAL = 12 };      /* recovery-policy noise of the evaluation rollout */
+typedef struct {
+    int n, T;                       /* envs; steps, 1..4096 (the reference: horizon + 1) */
+    int H, d_obs, d_act;            /* 256, 2, 2 */
+    int env_kind;                   /* RRL_ENV_NAV1 or RRL_ENV_NAV2 */
+    int reset;                      /* != 0: start states drawn here; 0: taken from pos */
+    const double* pos;              /* [n, 2], required with reset == 0; never written */
+    const float *pW1, *pb1, *pW2p, *pb2, *pW3, *pb3;   /* task policy: [256,2], [256], fragment order, [256], [>= 2,256], [>= 2] */
+    const float *scale, *bias;      /* [2] action box of the task policy */
+    const float *qW1, *qb1, *qW2p, *qb2, *qW3, *qb3;   /* Q_risk group, all or none: as rrl_sqrl_act_t's W1 .. b3 */
+    float eps_safe;
+    const float *rW1, *rb1, *rW2p, *rb2, *rW3, *rb3;   /* recovery group, all or none (with rscale, rbias, rlog_std) */
+    const float *rscale, *rbias, *rlog_std;            /* [2] each */
+    float min_log_std;
+    uint64_t seed, counter;         /* the env's Philox seed; tick = counter + counter_dev[0] */
+    uint64_t* counter_dev;          /* nullable {tick, ticket}: += T + reset by the last workgroup */
+    float* ret;                     /* [n] */
+    uint8_t *success, *violation;   /* [n] */
+    int32_t* steps;                 /* [n] */
+    double* tr_pos;                 /* nullable trace [T, n, 2]: state before step j */
+    float *tr_task, *tr_real;       /* nullable traces [T, n, 2]: task and executed action before clipping */
+    float* tr_z;                    /* nullable trace [T, 2, n]: pre-sigmoid Q_risk (Q_risk group only) */
+    float* tr_eps;                  /* nullable trace [T, n, 2]: the recovery noise (recovery group only) */
+    float* tr_reward;               /* nullable trace [T, n] */
+    uint8_t* tr_flags;              /* nullable trace [T, n]: bit 0 alive before the step, 1 done, 2 constraint, 3 success, 4 recovery */
+} rrl_eval_rollout_t;
+int rrl_eval_rollout(const rrl_eval_rollout_t* a, void* stream);
+/* ... and for S seeds side by side (the packed-launch table above): each seed with its own n, T, weights, env seed and tick,
+ * its outputs the bits of its stand-alone launch.  Every seed is checked as the stand-alone entry checks it, all before
+ * anything is stored or launched; args == NULL: RRL_EINVAL; S outside 1 .. 16: RRL_ERANGE; S == 1 is rrl_eval_rollout(args). */
+int rrl_eval_rollout_packed(int S, const rrl_eval_rollout_t* args, void* stream);
 
 #ifdef __cplusplus
 }

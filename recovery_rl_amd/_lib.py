@@ -15,7 +15,7 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
 HIP_SOURCES = ["nav_kernels.hip", "replay_kernels.hip", "maze_kernels.hip", "cem_kernels.hip",
                "mlp_kernels.hip", "mlp_fwd_kernels.hip", "update_kernels.hip", "log_kernels.hip", "plan_kernels.hip", "ens_train_kernels.hip",
-               "ens_train_big_kernels.hip", "sqrl_kernels.hip", "qsample_kernels.hip"]
+               "ens_train_big_kernels.hip", "sqrl_kernels.hip", "qsample_kernels.hip", "eval_kernels.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-ffp-contract=off", "-Wall", "-Wno-unused-function",
                "-Wno-bitwise-instead-of-logical"]
@@ -53,6 +53,7 @@ EXPORTS = [
     "rrl_ens_train_big_supported", "rrl_ens_big_scratch_floats", "rrl_ens_train_grad_big", "rrl_ens_train_epoch_big",
     "rrl_sqrl_scratch_floats", "rrl_sqrl_act", "rrl_sqrl_act_packed",
     "rrl_qsample_scratch_floats", "rrl_qsample_act", "rrl_qsample_act_gated", "rrl_qsample_act_packed",
+    "rrl_eval_rollout", "rrl_eval_rollout_packed",
 ]
 
 class RRLError(RuntimeError):
@@ -313,6 +314,19 @@ class rrl_qsample_gate_t(C.Structure):
                 ("task_action", C.c_void_p), ("ld_task", C.c_int), ("task_out", C.c_void_p), ("recovery_out", C.c_void_p)]
 
 
+STREAM_EVAL = 12
+
+
+class rrl_eval_rollout_t(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n", "T", "H", "d_obs", "d_act", "env_kind", "reset")] + [
+        (n, C.c_void_p) for n in ("pos", "pW1", "pb1", "pW2p", "pb2", "pW3", "pb3", "scale", "bias",
+                                  "qW1", "qb1", "qW2p", "qb2", "qW3", "qb3")] + [("eps_safe", C.c_float)] + [
+        (n, C.c_void_p) for n in ("rW1", "rb1", "rW2p", "rb2", "rW3", "rb3", "rscale", "rbias", "rlog_std")] + [
+        ("min_log_std", C.c_float), ("seed", C.c_uint64), ("counter", C.c_uint64)] + [
+        (n, C.c_void_p) for n in ("counter_dev", "ret", "success", "violation", "steps", "tr_pos", "tr_task", "tr_real",
+                                  "tr_z", "tr_eps", "tr_reward", "tr_flags")]
+
+
 _lib = None
 
 
@@ -399,6 +413,8 @@ def _declare(lib):
         "rrl_qsample_act": (ci, [C.POINTER(rrl_qsample_act_t), vp]),
         "rrl_qsample_act_gated": (ci, [C.POINTER(rrl_qsample_act_t), C.POINTER(rrl_qsample_gate_t), vp]),
         "rrl_qsample_act_packed": (ci, [ci, C.POINTER(rrl_qsample_act_t), C.POINTER(rrl_qsample_gate_t), vp]),
+        "rrl_eval_rollout": (ci, [C.POINTER(rrl_eval_rollout_t), vp]),
+        "rrl_eval_rollout_packed": (ci, [ci, C.POINTER(rrl_eval_rollout_t), vp]),
         "rrl_episode_log_append": (ci, [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(rrl_episode_log_t), vp]),
     }
     for name, (res, args) in sig.items():

@@ -728,7 +728,7 @@ class Experiment:
         self.vector_rules = {"demo_share": share if share > 0 else 0.0, "pinned_demonstrations": int(pinned),
                              **{k: self.vector_rules[k] for k in ("update_path", "replay_capacities", "cover_rows_limit",
                                                                    "buffers_cover_the_run", "plan_warm_start", "sqrl_acting",
-                                                                   "qsample_acting", "qsample_gate")
+                                                                   "qsample_acting", "qsample_gate", "evaluation")
                                 if k in self.vector_rules}}
         if cfg.num_envs > 1:
             print("Q_risk batch: %s (--demo_share; 0 = the reference's single uniform draw, replay_memory.py:54-72)"
@@ -1075,6 +1075,12 @@ class Experiment:
         the mean episode return, success rate and violation rate."""
         cfg = self.exp_cfg
         env = self.eval_env()
+        rollout = self.eval_rollout()
+        if rollout is not None:
+            # RRL_FAST_EVAL=1: reset, the horizon + 1 steps and the per-env results in one launch (rrl_eval_rollout)
+            rollout.launch(env._max_episode_steps + 1)
+            return self._eval_result(rollout.stats(label))
+        self.vector_rules.pop("evaluation", None)          # the rule records the path the LAST evaluation took
         obs = env.reset()
         n = cfg.num_envs
         alive = torch.ones(n, dtype=torch.bool, device=self.device)
@@ -1091,11 +1097,26 @@ class Experiment:
             obs = obs.clone()
         out = {"label": label, "avg_reward": float(ret.mean().item()), "success_rate": float(succ.float().mean().item()),
                "violation_rate": float(viol.float().mean().item())}
+        return self._eval_result(out)
+
+    def _eval_result(self, out):
         if self.rank == 0:
             print("----------------------------------------")
             print("Avg. Reward: {}".format(round(out["avg_reward"], 2)))
             print("----------------------------------------")
         return out
+
+    def eval_rollout(self):
+        """The EvalRollout of this experiment's evaluation env when evaluation runs on the kernel
+        (fast_update.eval_rollout_path), else None: the module code below."""
+        from .fast_update import EvalRollout, eval_rollout_path
+        cfg = self.exp_cfg
+        if eval_rollout_path(cfg) != "hip" or getattr(self.agent, "fast", None) is None:
+            return None
+        if getattr(self, "_eval_rollout", None) is None:
+            self._eval_rollout = EvalRollout(self.agent.fast, self.eval_env(), cfg.eps_safe, cfg.use_recovery)
+        self.vector_rules["evaluation"] = "hip"
+        return self._eval_rollout
 
     def eval_env(self):
         if getattr(self, "_eval_env", None) is None:
@@ -1174,8 +1195,8 @@ def run_packed(exp_cfg, rank=0, world_size=1):
     limits (their acting passes are module code then), model-based recovery, --dp_mode env_shard, --resume /
     --checkpoint_every."""
     import copy
-    from .fast_update import (fast_baselines_enabled, fast_path_supported, fast_qsample_enabled, fast_sqrl_enabled,
-                              pack_qsample_enabled, pack_sqrl_enabled, qsample_acting_path, sqrl_acting_path,
+    from .fast_update import (eval_rollouts_packed, fast_baselines_enabled, fast_path_supported, fast_qsample_enabled,
+                              fast_sqrl_enabled, pack_qsample_enabled, pack_sqrl_enabled, qsample_acting_path, sqrl_acting_path,
                               uses_baseline_terms)
     from .packed import PackedLoop
     S = int(exp_cfg.seeds_per_gpu)
@@ -1265,6 +1286,11 @@ def run_packed(exp_cfg, rank=0, world_size=1):
         exps.append(exp)
     cfg = exp_cfg
     histories = [[] for _ in exps]
+    # RRL_FAST_EVAL=1 (fast_update.eval_rollout_path): every seed evaluates every 10 episodes per env, as its solo run, and the
+    # seeds due at a log point go out as ONE rrl_eval_rollout_packed launch; otherwise packed runs do not evaluate
+    rollouts = [e.eval_rollout() for e in exps] if cfg.eval else [None] * S
+    evals = [[] for _ in exps]
+    next_eval = [10 * n] * S
 
     def before():
         for e, info in zip(exps, infos):
@@ -1279,8 +1305,12 @@ def run_packed(exp_cfg, rank=0, world_size=1):
     def log_point(it):
         """Per-seed counters, table and info stream at the logging cadence; True when every seed has reached its budget."""
         done = True
+        all_stats = [e.loop.read_stats() for e in exps]
+        due = [k for k in range(S) if rollouts[k] is not None and all_stats[k]["episodes"] >= next_eval[k]]
+        if due:
+            eval_rollouts_packed([rollouts[k] for k in due], exps[0].eval_env()._max_episode_steps + 1)
         for k, (e, hist) in enumerate(zip(exps, histories)):
-            stats = e.loop.read_stats()
+            stats = all_stats[k]
             e._absorb(stats)
             hist.append(dict(stats, iteration=it))
             print("Seed: {}, Iter: {}, total numsteps: {}, episodes: {}, mean episode reward: {}".format(
@@ -1295,8 +1325,11 @@ def run_packed(exp_cfg, rank=0, world_size=1):
             if infos[k] is not None:
                 train_stats[k].extend(infos[k].drain())
             done = done and (stats["env_steps"] > cfg.num_steps or stats["episodes"] > cfg.num_eps)
+            if k in due:
+                evals[k].append(e._eval_result(rollouts[k].stats(stats["episodes"])))
+                next_eval[k] += 10 * n
             with open(osp.join(e.logdir, "run_stats.pkl"), "wb") as f:
-                pickle.dump({"vector_stats": hist, "eval_stats": [], "num_envs": n, "seeds_per_gpu": S,
+                pickle.dump({"vector_stats": hist, "eval_stats": evals[k], "num_envs": n, "seeds_per_gpu": S,
                              "vector_rules": e.vector_rules, "episode_stats": np.concatenate(tables[k]),
                              **({"train_stats": train_stats[k], "test_stats": [], "info_envs": info_k}
                                 if infos[k] is not None else {})}, f)

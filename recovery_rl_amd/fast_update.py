@@ -1213,6 +1213,84 @@ def qsample_acting_path(cfg):
     return "hip" if hip else "modules"
 
 
+def fast_eval_enabled():
+    """RRL_FAST_EVAL=1: policy evaluation as one rrl_eval_rollout launch (opt-in; eval_rollout_path)."""
+    return os.environ.get("RRL_FAST_EVAL", "0") == "1"
+
+
+def eval_rollout_path(cfg):
+    """Where Experiment.get_test_rollout_vectorized runs: "hip" (EvalRollout: one launch) under RRL_FAST_EVAL=1 on the fused
+    path at hidden width 256, Navigation 1 / 2, the lock-step loop, without a recovery policy or with the model-free one;
+    else "modules" (the loop's act() on the torch modules and the eager env), which Maze, Q-sampling, SQRL, model-based
+    recovery and every other configuration keep."""
+    hip = (fast_eval_enabled() and fast_path_supported(cfg) and not getattr(cfg, "no_fast_path", False)
+           and int(cfg.hidden_size) == 256 and cfg.env_name in ("navigation1", "navigation2")
+           and int(getattr(cfg, "num_envs", 1)) > 1 and not cfg.use_constraint_sampling
+           and (not cfg.use_recovery or bool(cfg.MF_recovery)))
+    return "hip" if hip else "modules"
+
+
+class EvalRollout:
+    """One evaluation (Experiment.get_test_rollout_vectorized) of `env`'s envs as one rrl_eval_rollout launch on the live flat
+    weights of `fast`.  Owns the per-env result buffers and its OWN fragment-order copies of the three W2 matrices, re-made
+    right before each launch: it depends neither on RRL_W2_FRAG nor on how many seeds a packed run keeps those copies for."""
+
+    def __init__(self, fast, env, eps_safe, use_recovery):
+        self.f, self.env, self.n = fast, env, env.num_envs
+        self.eps_safe, self.use_recovery = float(eps_safe), bool(use_recovery)
+        dev = fast.dev
+        self.ret = torch.zeros(self.n, dtype=torch.float32, device=dev)
+        self.success = torch.zeros(self.n, dtype=torch.uint8, device=dev)
+        self.violation = torch.zeros(self.n, dtype=torch.uint8, device=dev)
+        self.steps = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self.nets = [fast.policy] + ([fast.qrisk, fast.recpolicy] if self.use_recovery else [])
+        self.w2p = [torch.empty(net.p["W2"].numel(), dtype=torch.float32, device=dev) for net in self.nets]
+        self.args = None
+
+    def desc(self, T, reset=True, pos=None, trace=None):
+        """The launch's rrl_eval_rollout_t on the live flat buffers and the env's seed and device tick, the W2 copies made
+        current.  `pos` [n, 2] f64 with reset=False: the start states; `trace` = {name: tensor} asks for trace buffers."""
+        f, p = self.f, _lib.ptr
+        for net, w2p in zip(self.nets, self.w2p):
+            W2 = net.p["W2"]
+            _lib.check(f.lib.rrl_w2_pack(W2.shape[0], W2.shape[1], W2.data_ptr(), w2p.data_ptr(), _lib.current_stream()),
+                       "rrl_w2_pack")
+        P = f.policy.p
+        a = _lib.rrl_eval_rollout_t(n=self.n, T=int(T), H=f.policy.H, d_obs=2, d_act=2, env_kind=self.env.kind,
+                                    reset=int(bool(reset)), pos=p(pos), pW1=p(P["W1"]), pb1=p(P["b1"]), pW2p=p(self.w2p[0]),
+                                    pb2=p(P["b2"]), pW3=p(P["W3"]), pb3=p(P["b3"]), scale=p(f.scale), bias=p(f.bias),
+                                    seed=self.env.seed_value, counter=0, counter_dev=p(self.env.tick), ret=p(self.ret),
+                                    success=p(self.success), violation=p(self.violation), steps=p(self.steps),
+                                    **{name: p(t) for name, t in (trace or {}).items()})
+        if self.use_recovery:
+            Q, R = f.qrisk.p, f.recpolicy.p
+            a.qW1, a.qb1, a.qW2p, a.qb2, a.qW3, a.qb3 = (p(Q["W1"]), p(Q["b1"]), p(self.w2p[1]), p(Q["b2"]), p(Q["W3"]),
+                                                         p(Q["b3"]))
+            a.eps_safe = self.eps_safe
+            a.rW1, a.rb1, a.rW2p, a.rb2, a.rW3, a.rb3 = (p(R["W1"]), p(R["b1"]), p(self.w2p[2]), p(R["b2"]), p(R["W3"]),
+                                                         p(R["b3"]))
+            a.rscale, a.rbias, a.rlog_std = p(f.rscale), p(f.rbias), p(R["log_std"])
+            a.min_log_std = f.qr.policy.min_log_std
+        self.args = a              # keeps the argument block alive until the launch has been issued
+        return a
+
+    def launch(self, T, **kw):
+        a = self.desc(T, **kw)
+        _lib.check(self.f.lib.rrl_eval_rollout(C.byref(a), _lib.current_stream()), "rrl_eval_rollout")
+
+    def stats(self, label):
+        """The three means of the per-env arrays, as the module path takes them."""
+        return {"label": label, "avg_reward": float(self.ret.mean().item()),
+                "success_rate": float(self.success.bool().float().mean().item()),
+                "violation_rate": float(self.violation.bool().float().mean().item())}
+
+
+def eval_rollouts_packed(rollouts, T):
+    """The evaluations of several seeds (EvalRollout each) as ONE rrl_eval_rollout_packed launch."""
+    args = (_lib.rrl_eval_rollout_t * len(rollouts))(*[r.desc(T) for r in rollouts])
+    _lib.check(_lib.load().rrl_eval_rollout_packed(len(rollouts), args, _lib.current_stream()), "rrl_eval_rollout_packed")
+
+
 def uses_baseline_terms(cfg):
     return any(bool(getattr(cfg, f, False)) for f in BASELINE_FLAGS)
 
