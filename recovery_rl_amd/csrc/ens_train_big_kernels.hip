@@ -22,11 +22,15 @@
 // the batch-32 kernel.
 #include <hip/hip_runtime.h>
 
+#include "mfma_tile.hpp"
 #include "rrl_host.hpp"
 
 namespace {
 
 using rrl_host::check_launch;
+using rrl_tile::f32x4;
+using rrl_tile::mfma;
+using rrl_tile::opaque;
 
 constexpr int kH = 200, kDin = 4, kDout = 4;
 constexpr int kR = 64;               // rows per tile
@@ -41,17 +45,6 @@ constexpr int kOffW0 = 0, kOffW3 = 800, kOffB0 = 1600, kOffB1 = 1800, kOffB2 = 2
 constexpr int kThreadsB = 1024;      // 16 waves
 constexpr int kMaxP = 64, kMaxQ = 32;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-// Identity the optimiser cannot see through: address arithmetic derived from opaque(lane) is redone per phase instead of
-// being hoisted out of the tile loop and kept live (hoisted, the per-element addresses of the epilogues cost > 200 VGPRs)
-__device__ __forceinline__ int opaque(int x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ float softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }   // F.softplus
 __device__ __forceinline__ float softplus_grad(float x) { return x > 20.f ? 1.f : sigm(x); }

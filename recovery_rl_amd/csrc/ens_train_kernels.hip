@@ -13,11 +13,14 @@
 // logvar 2), batch 32.  Weight layout [net][in][out] (torch.baddbmm(b, x, w)).
 #include <hip/hip_runtime.h>
 
+#include "mfma_tile.hpp"
 #include "rrl_host.hpp"
 
 namespace {
 
 using rrl_host::check_launch;
+using rrl_tile::f32x4;
+using rrl_tile::mfma;
 
 constexpr int kH = 200;          // hidden width
 constexpr int kB = 32;           // batch rows per net
@@ -32,12 +35,6 @@ constexpr int kLdsBytes = kLdsFloats * 4;      // 71 KB
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ float softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }   // F.softplus
 __device__ __forceinline__ float softplus_grad(float x) { return x > 20.f ? 1.f : sigm(x); }
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 constexpr int kColTiles = (kH + 15) / 16;     // 13 (200 = 12.5 x 16: the last tile is half masked)
 

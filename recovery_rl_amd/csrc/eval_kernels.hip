@@ -17,8 +17,9 @@
 // The stand-alone and the packed kernel (rrl_eval_rollout_packed: S seeds side by side, pack.hpp) have ONE body
 // (rollout_tile); they differ only in where the argument block and the tile index come from.
 //
-// The matrix helpers are restated from qsample_kernels.hip, the transition from nav_kernels.hip's NavEnv, not shared: a shared
-// header would move those files' kernels.
+// The tile's primitives and layer-2 helpers come from mfma_tile.hpp (one row tile: MR = 1); run_stack is this file's own,
+// for its 16 rows, DIN < 4 inputs and NOUT outputs.  The transition is restated from nav_kernels.hip's NavEnv.
+#include "mfma_tile.hpp"
 #include "pack.hpp"
 #include "rrl_device.hpp"
 #include "rrl_host.hpp"
@@ -27,14 +28,19 @@ using namespace rrl_host;
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using rrl_tile::f32x4;
+using rrl_tile::kActStride;
+using rrl_tile::kH;
+using rrl_tile::kThreads;
+using rrl_tile::kWaves;
+using rrl_tile::layer_mma;
+using rrl_tile::mfma;
+using rrl_tile::opaque;
+using rrl_tile::reduce16;
+using rrl_tile::reluf;
 
 constexpr uint32_t kStreamEval = RRL_STREAM_EVAL;
-constexpr int kH = 256, kTiles = kH / 16;
 constexpr int kRows = 16;                 // rows per workgroup: one row tile, every wave owns 2 column tiles of it
-constexpr int kWaves = 8;
-constexpr int kThreads = kWaves * 64;
-constexpr int kActStride = kH + 4;        // +4 floats: row r starts at bank 4r, ds_read_b128 conflict-free
 constexpr int kMaxT = 4096, kMaxN = 1 << 22;
 
 // LDS carve-up (floats)
@@ -69,62 +75,6 @@ struct EvArgs {
     uint8_t* tr_flags;
 };
 
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-// Identity the optimiser cannot see through: address arithmetic derived from opaque(lane) is redone per phase instead of
-// being hoisted and kept live across the matrix loops.
-__device__ __forceinline__ int opaque(int x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
-__device__ __forceinline__ float reluf(float x) { return x < 0.f ? 0.f : x; }   // NaN stays NaN (F.relu)
-
-// B fragments of K chunk j for this wave's two column tiles: W2p is [ct][j][lane] float4 (rrl_w2_pack), one coalesced
-// 1 KB load per fragment
-__device__ __forceinline__ void load_b(f32x4 (&b)[2], const float* __restrict__ w2p, const int (&ct)[2], int j, int lane) {
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-        b[c] = *reinterpret_cast<const f32x4*>(w2p + ((size_t)(ct[c] * kTiles + j) * 64 + lane) * 4);
-}
-
-// acc[c] += act[:, 16 j .. 16 j + 15] * W2[column tile ct[c]]; chunk step t uses k = 16 j + 4 (lane / 16) + t
-__device__ __forceinline__ void mma_chunk(f32x4 (&acc)[2], const float* act, const f32x4 (&b)[2], int j, int lane) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(act + (lane & 15) * kActStride + 16 * j + (lane >> 4) * 4);
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) acc[c] = mfma(a[t], b[c][t], acc[c]);
-}
-
-// layer 2: the weight fragments of chunk j + 1 are requested before the MFMAs of chunk j (register double buffer)
-__device__ __forceinline__ void layer_mma(f32x4 (&acc)[2], const float* act, const float* __restrict__ w2p,
-                                          const int (&ct)[2], int lane) {
-    f32x4 b0[2], b1[2];
-    load_b(b0, w2p, ct, 0, lane);
-    int j = 0;
-#pragma unroll 1
-    for (; j + 2 < kTiles; j += 2) {
-        load_b(b1, w2p, ct, j + 1, lane);
-        __builtin_amdgcn_sched_barrier(0);      // keep the prefetch ahead of the MFMAs it hides behind
-        mma_chunk(acc, act, b0, j, lane);
-        load_b(b0, w2p, ct, j + 2, lane);
-        __builtin_amdgcn_sched_barrier(0);
-        mma_chunk(acc, act, b1, j + 1, lane);
-    }
-    load_b(b1, w2p, ct, kTiles - 1, lane);
-    mma_chunk(acc, act, b0, kTiles - 2, lane);
-    mma_chunk(acc, act, b1, kTiles - 1, lane);
-}
-
-__device__ __forceinline__ float reduce16(float v) {   // sum over the 16 lanes that share lane / 16
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    v += __shfl_xor(v, 8, 64);
-    return v;
-}
-
 // One 2-hidden-layer stack (head `head` of w) on the row tile in xs: inputs = the first DIN columns of xs, outputs = the
 // first NOUT rows of W3.  Leaves part[o][wave][row] (output o's pre-activation is b3[o] + the sum over the 8 waves, added by
 // the caller in wave order).  Ends with a barrier.
@@ -152,23 +102,23 @@ __device__ __forceinline__ void run_stack(float* lds, const Net& w, int head, fl
         const float wv = W1[col * DIN + (k1 < DIN ? k1 : 0)];  // B operand of layer 1: W1[col][k]
         w1v[c] = k1 < DIN ? wv : 0.f;
     }
-    f32x4 acc[2];
+    f32x4 acc[1][2];
     // layer 1: K = 4 inputs = ONE mfma per column tile
     const float xv = xs[(ln & 15) * 4 + k1];
     const float x = k1 < DIN ? xv : 0.f;
 #pragma unroll
-    for (int c = 0; c < 2; ++c) acc[c] = mfma(x, w1v[c], f32x4{0.f, 0.f, 0.f, 0.f});
+    for (int c = 0; c < 2; ++c) acc[0][c] = mfma(x, w1v[c], f32x4{0.f, 0.f, 0.f, 0.f});
     // act[row][col] = relu(acc + b1[col]); C layout: row = 4 (lane / 16) + i, col = 16 ct + lane % 16
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
         const int col = ct[c] * 16 + (opaque(lane) & 15);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) act[(4 * (opaque(lane) >> 4) + i) * kActStride + col] = reluf(acc[c][i] + b1v[c]);
+        for (int i = 0; i < 4; ++i) act[(4 * (opaque(lane) >> 4) + i) * kActStride + col] = reluf(acc[0][c][i] + b1v[c]);
     }
     __syncthreads();
 #pragma unroll
-    for (int c = 0; c < 2; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    layer_mma(acc, act, W2p, ct, opaque(lane));
+    for (int c = 0; c < 2; ++c) acc[0][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    layer_mma<1>(acc, act, W2p, ct, opaque(lane));
     // last layer folded in: out_o[row] = sum_col relu(h2 + b2) W3[o][col]
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -176,7 +126,7 @@ __device__ __forceinline__ void run_stack(float* lds, const Net& w, int head, fl
         for (int o = 0; o < NOUT; ++o) {
             float s = 0.f;
 #pragma unroll
-            for (int c = 0; c < 2; ++c) s += reluf(acc[c][i] + b2v[c]) * w3v[o][c];
+            for (int c = 0; c < 2; ++c) s += reluf(acc[0][c][i] + b2v[c]) * w3v[o][c];
             const float v = reduce16(s);
             if ((ln & 15) == 0) part[(o * kWaves + wave) * kRows + 4 * (ln >> 4) + i] = v;
         }
@@ -445,14 +395,13 @@ int rrl_eval_rollout_packed(int S, const rrl_eval_rollout_t* args, void* stream)
     rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
         std::vector<EvArgs> blocks(S);
-        rrl_pack::Idx ix;
-        ix.S = S;
-        ix.first[0] = 0;
+        int count[rrl_pack::kMaxSeeds];
         for (int s = 0; s < S; ++s) {
             blocks[s] = block_of(args + s);
-            ix.first[s + 1] = ix.first[s] + blocks[s].blocks;      // <= 2^18 workgroups per seed: any mapping's grid fits an int
+            count[s] = blocks[s].blocks;            // <= 2^18 workgroups per seed: any mapping's grid fits an int
         }
-        for (int s = S; s < rrl_pack::kMaxSeeds; ++s) ix.first[s + 1] = ix.first[S];
+        rrl_pack::Idx ix;
+        rrl_pack::ranges(ix, S, count);
         const int grid = rrl_pack::finish(ix);
         plan = rrl_pack::store(key, blocks.data(), sizeof(EvArgs) * S, st);
         if (!plan) return rrl_pack::store_error();

@@ -20,20 +20,7 @@ namespace loss {
 
 constexpr float kLogSigMax = 2.f, kLogSigMin = -20.f, kEps = 1e-6f;   // model.py:14-16
 
-// value of a stack output given as np <= 4 partial sums ps floats apart: ((p0 + p1) + p2) + p3, the order of the
-// stand-alone sum kernel.  All loads are issued together (a run-time loop over np chained one memory round trip per
-// part: twelve of them in a row set the 11 us of the critic-loss head backward).
-__device__ __forceinline__ float psum(const float* p, long long idx, int np, long long ps) {
-    const float v0 = p[idx];
-    const float v1 = p[(np > 1 ? ps : 0) + idx];
-    const float v2 = p[(np > 2 ? 2 * ps : 0) + idx];
-    const float v3 = p[(np > 3 ? 3 * ps : 0) + idx];
-    float v = v0;
-    v = np > 1 ? v + v1 : v;
-    v = np > 2 ? v + v2 : v;
-    v = np > 3 ? v + v3 : v;
-    return v;
-}
+using rrl::psum;
 
 }  // namespace loss
 
@@ -80,23 +67,21 @@ template <class Group, class Member, class Build>
 static int build_pack(int S, const int* n, const Member* const* members, std::vector<Group>& groups, rrl_pack::Idx& ix,
                       Build build) {
     groups.resize(S);
-    ix.S = S;
-    ix.first[0] = 0;
+    int count[rrl_pack::kMaxSeeds];
     for (int s = 0; s < S; ++s) {
         const int rc = build(n[s], members[s], groups[s]);
         if (rc != RRL_OK) return rc;
-        ix.first[s + 1] = ix.first[s] + groups[s].first[n[s]];
+        count[s] = groups[s].first[n[s]];
     }
-    for (int s = S; s < rrl_pack::kMaxSeeds; ++s) ix.first[s + 1] = ix.first[S];
+    rrl_pack::ranges(ix, S, count);
     return RRL_OK;
 }
 
 // 2-D packed launch (rrl_pack::locate_grid): seed s owns `most[s]` workgroups per member row; returns grid.x
 static int finish_members(rrl_pack::Idx& ix, int S, const int* most) {
-    ix.S = S;
-    ix.first[0] = 0;
-    for (int s = 0; s < S; ++s) ix.first[s + 1] = ix.first[s] + (most[s] > 0 ? most[s] : 1);
-    for (int s = S; s < rrl_pack::kMaxSeeds; ++s) ix.first[s + 1] = ix.first[S];
+    int count[rrl_pack::kMaxSeeds];
+    for (int s = 0; s < S; ++s) count[s] = most[s] > 0 ? most[s] : 1;
+    rrl_pack::ranges(ix, S, count);
     return rrl_pack::finish(ix);
 }
 // the placement's four scalars in one batch of kernel-argument loads, then (seed, index inside the seed's member row).
@@ -107,7 +92,8 @@ static int finish_members(rrl_pack::Idx& ix, int S, const int* most) {
     arrive_together((ix).sp, (ix).p, (ix).r, (ix).S);                                         \
     if (!rrl_pack::locate_grid((ix), blockIdx.x, s, local)) return
 
-// tiles of R >= 4 need more than the default 64 KB of LDS per workgroup (gfx950 has 160 KB per CU): opt in once
+// tiles of R >= 4 need more than the default 64 KB of LDS per workgroup (gfx950 has 160 KB per CU): opt in once.
+// Not rrl_host::grant_lds: a refusal here is final and reported as RRL_ERANGE, and a request of <= 64 KB asks for nothing.
 static bool grant_lds(const void* kernel, size_t bytes) {
     if (bytes <= 64 * 1024) return true;
     if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)) != hipSuccess) {

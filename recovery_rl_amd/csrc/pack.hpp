@@ -147,6 +147,14 @@ inline int seed_share(int S) {
     return pinned_mapping(S, sp, p, r) ? sp * r : 1;
 }
 
+// host: the ranges of `ix` from the workgroups every seed needs; the entries behind seed S - 1 repeat first[S], so that
+// first[s + 1] - first[s] is 0 workgroups for a seed nobody has
+inline void ranges(Idx& ix, int S, const int* count) {
+    ix.S = S;
+    ix.first[0] = 0;
+    for (int s = 0; s < kMaxSeeds; ++s) ix.first[s + 1] = ix.first[s] + (s < S ? count[s] : 0);
+}
+
 // host: choose the mapping for `ix` (first[] and S filled in) and return the grid size
 inline int finish(Idx& ix) {
     int most = 0;

@@ -19,6 +19,7 @@
 //
 // Row order inside a tile: 16 consecutive (m, c) groups x the 4 particles that are bound to ensemble member
 // e (TS-infinity: member = particle / (npart / nets), MPC.py:441-455); tile id = (group block, e).
+#include "mfma_tile.hpp"
 #include "rrl_device.hpp"
 #include "rrl_host.hpp"
 #include "plan_layout.hpp"
@@ -28,7 +29,13 @@ using namespace rrl_plan;
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// the tile's primitives; the matrix helpers below are this file's own (NCV / XR / f16x3 variants, other signatures)
+using rrl_tile::f32x4;
+using rrl_tile::mfma;
+using rrl_tile::opaque;
+using rrl_tile::reduce16;
+using rrl_tile::reluf;
+
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // waves per SIMD the register allocator targets: 2 = one workgroup per CU (<= 256 VGPRs), 4 = two (<= 128)
@@ -50,9 +57,6 @@ static_assert(kActFloats >= kRows * kActStride, "the f32 activation tile must fi
 constexpr int kLdsFloats = kActFloats + 3 * kRows * 4 + 2 * kWaves * kRows + 4 * kRows * 4;
 constexpr int kLdsBytes = kLdsFloats * 4;  // 78.5 KB: two workgroups per CU
 
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 // v = hi + lo with hi = f16(v) and lo = f16(v - hi): v - hi is exact in f32 (13 significant bits at most), so for
 // |v| >= 2^-3 hi + lo carries 22 bits of v and three products hi*hi + hi*lo + lo*hi carry ~2^-21 of the f32 product (the
 // lo*lo term, 2^-22 of it, is dropped).  lo is stored UNSCALED: for |v| below ~0.06 it falls into the f16 subnormal range
@@ -66,14 +70,6 @@ __device__ __forceinline__ void split16(float v, _Float16& hi, _Float16& lo) {
     lo = (_Float16)(v - (float)hi);
 }
 
-// Identity the optimiser cannot see through: address arithmetic derived from opaque(lane) is redone per phase
-// instead of being hoisted out of the rollout loop and kept live (that hoisting costs > 100 VGPRs here).
-__device__ __forceinline__ int opaque(int x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
-
-__device__ __forceinline__ float reluf(float x) { return x < 0.f ? 0.f : x; }   // NaN stays NaN (F.relu)
 // v_rcp_f32 (1 ulp) instead of the IEEE division sequence (~10 instructions): swish runs once per hidden activation of
 // the ensemble, 40 k times per workgroup and rollout step
 __device__ __forceinline__ float sigmoidf(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
@@ -253,14 +249,6 @@ __device__ __forceinline__ void store_act(const f32x4 (&acc)[MR][NC], float* act
                 }
             }
     }
-}
-
-__device__ __forceinline__ float reduce16(float v) {   // sum over the 16 lanes that share lane / 16
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    v += __shfl_xor(v, 8, 64);
-    return v;
 }
 
 // LDS carve-up shared by the two kernels

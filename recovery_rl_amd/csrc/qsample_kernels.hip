@@ -14,32 +14,24 @@
 // kernels have ONE body (score_chunk, fold_envs); the stand-alone and the packed kernels (rrl_qsample_act_packed: S seeds side
 // by side, pack.hpp) differ only in where the argument block and (env, chunk) come from.
 //
-// The matrix helpers are restated from sqrl_kernels.hip, not shared: a shared header would move that file's kernels.
+// The tile and the twin-head phase (q_phase) come from mfma_tile.hpp, shared with sqrl_kernels.hip.
+#include "mfma_tile.hpp"
 #include "pack.hpp"
 #include "rrl_device.hpp"
 #include "rrl_host.hpp"
 
 using namespace rrl_host;
+using namespace rrl_tile;
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr uint32_t kStreamQsample = RRL_STREAM_QSAMPLE;
-constexpr int kH = 256, kTiles = kH / 16;
 constexpr int kMaxK = 1024;               // candidates per env
 constexpr int kChunk = 128;               // candidates per workgroup
-constexpr int kRows = 64;                 // rows per pass: 4 row tiles, every wave owns 2 column tiles of all of them
-constexpr int kWaves = 8;
-constexpr int kThreads = kWaves * 64;
-constexpr int kActStride = kH + 4;        // +4 floats: row r starts at bank 4r, ds_read_b128 conflict-free
 constexpr int kPartial = 4;               // floats of a workgroup's partial: key, index (int bits), candidate x, y
 
-// LDS carve-up (floats)
-constexpr int kOffAct = 0;                                   // [64][260] activations of the current pass
-constexpr int kOffXs = kOffAct + kRows * kActStride;         // [64][4] (obs, candidate)
-constexpr int kOffQpart = kOffXs + kRows * 4;                // [2 heads][8 waves][64 rows] partial last-layer sums
-constexpr int kOffCand = kOffQpart + 2 * kWaves * kRows;     // [128][2] candidate actions of the chunk
+// LDS carve-up (floats), behind the tile's act / xs / qpart
+constexpr int kOffCand = kOffOwn;                            // [128][2] candidate actions of the chunk
 constexpr int kOffQ = kOffCand + kChunk * 2;                 // [128] max(sigmoid z0, sigmoid z1)
 constexpr int kLdsFloats = kOffQ + kChunk;
 constexpr int kLdsBytes = kLdsFloats * 4;                    // 73.2 KB: two workgroups per CU
@@ -91,134 +83,6 @@ __device__ __forceinline__ bool gate_fired(const QsArgs& a, long long e) {
     return rrl::recovery_gate(z0, z1, a.g_eps);
 }
 
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-// Identity the optimiser cannot see through: address arithmetic derived from opaque(lane) is redone per phase instead of
-// being hoisted and kept live across the matrix loops.
-__device__ __forceinline__ int opaque(int x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
-__device__ __forceinline__ float reluf(float x) { return x < 0.f ? 0.f : x; }   // NaN stays NaN (F.relu)
-__device__ __forceinline__ float sigmoidf(float z) { return 1.f / (1.f + expf(-z)); }
-
-// B fragments of K chunk j for this wave's two column tiles: W2p is [ct][j][lane] float4 (rrl_w2_pack), one coalesced
-// 1 KB load per fragment
-__device__ __forceinline__ void load_b(f32x4 (&b)[2], const float* __restrict__ w2p, const int (&ct)[2], int j, int lane) {
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-        b[c] = *reinterpret_cast<const f32x4*>(w2p + ((size_t)(ct[c] * kTiles + j) * 64 + lane) * 4);
-}
-
-// acc[r][c] += act[row tile r, 16 j .. 16 j + 15] * W2[column tile ct[c]]; chunk step t uses k = 16 j + 4 (lane / 16) + t
-template <int MR>
-__device__ __forceinline__ void mma_chunk(f32x4 (&acc)[MR][2], const float* act, const f32x4 (&b)[2], int j, int lane) {
-    f32x4 a[MR];
-#pragma unroll
-    for (int r = 0; r < MR; ++r)
-        a[r] = *reinterpret_cast<const f32x4*>(act + (r * 16 + (lane & 15)) * kActStride + 16 * j + (lane >> 4) * 4);
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < MR; ++r)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) acc[r][c] = mfma(a[r][t], b[c][t], acc[r][c]);
-}
-
-// layer 2: the weight fragments of chunk j + 1 are requested before the MFMAs of chunk j (register double buffer)
-template <int MR>
-__device__ __forceinline__ void layer_mma(f32x4 (&acc)[MR][2], const float* act, const float* __restrict__ w2p,
-                                          const int (&ct)[2], int lane) {
-    f32x4 b0[2], b1[2];
-    load_b(b0, w2p, ct, 0, lane);
-    int j = 0;
-#pragma unroll 1
-    for (; j + 2 < kTiles; j += 2) {
-        load_b(b1, w2p, ct, j + 1, lane);
-        __builtin_amdgcn_sched_barrier(0);      // keep the prefetch ahead of the MFMAs it hides behind
-        mma_chunk<MR>(acc, act, b0, j, lane);
-        load_b(b0, w2p, ct, j + 2, lane);
-        __builtin_amdgcn_sched_barrier(0);
-        mma_chunk<MR>(acc, act, b1, j + 1, lane);
-    }
-    load_b(b1, w2p, ct, kTiles - 1, lane);
-    mma_chunk<MR>(acc, act, b0, kTiles - 2, lane);
-    mma_chunk<MR>(acc, act, b1, kTiles - 1, lane);
-}
-
-__device__ __forceinline__ float reduce16(float v) {   // sum over the 16 lanes that share lane / 16
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    v += __shfl_xor(v, 8, 64);
-    return v;
-}
-
-// The twin heads on the first MR row tiles of xs; leaves qpart[h][wave][row] (the output's pre-activation is b3 + the sum
-// over the 8 waves, added by the caller in wave order).  Ends with a barrier.
-template <int MR>
-__device__ __forceinline__ void q_phase(float* lds, const QsArgs& a, int wave, int lane) {
-    const int ln = opaque(lane);
-    const int ct[2] = {2 * wave, 2 * wave + 1};
-    float* act = lds + kOffAct;
-    const float* xs = lds + kOffXs;
-    float* qpart = lds + kOffQpart;
-#pragma unroll 1
-    for (int h = 0; h < 2; ++h) {
-        // epilogue constants first: their latency hides behind the matrix work
-        float b1v[2], b2v[2], w3v[2], w1v[2];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int col = ct[c] * 16 + (ln & 15);
-            b1v[c] = a.b1[h * kH + col];
-            b2v[c] = a.b2[h * kH + col];
-            w3v[c] = a.W3[h * kH + col];
-            w1v[c] = a.W1[(h * kH + col) * 4 + (ln >> 4)];        // B operand of layer 1: W1[col][k = lane / 16]
-        }
-        f32x4 acc[MR][2];
-#pragma unroll
-        for (int r = 0; r < MR; ++r)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // layer 1: K = 4 inputs = ONE mfma per tile
-#pragma unroll
-        for (int r = 0; r < MR; ++r) {
-            const float x = xs[(r * 16 + (ln & 15)) * 4 + (ln >> 4)];
-#pragma unroll
-            for (int c = 0; c < 2; ++c) acc[r][c] = mfma(x, w1v[c], acc[r][c]);
-        }
-        // act[row][col] = relu(acc + b1[col]); C layout: row = 16 r + 4 (lane / 16) + i, col = 16 ct + lane % 16
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int col = ct[c] * 16 + (opaque(lane) & 15);
-#pragma unroll
-            for (int r = 0; r < MR; ++r)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    act[(r * 16 + 4 * (opaque(lane) >> 4) + i) * kActStride + col] = reluf(acc[r][c][i] + b1v[c]);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < MR; ++r)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-        layer_mma<MR>(acc, act, a.W2p + (size_t)h * kH * kH, ct, opaque(lane));
-        // last layer folded in: z[row] = sum_col relu(h2 + b2) w3[col]
-#pragma unroll
-        for (int r = 0; r < MR; ++r)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float s = 0.f;
-#pragma unroll
-                for (int c = 0; c < 2; ++c) s += reluf(acc[r][c][i] + b2v[c]) * w3v[c];
-                const float v = reduce16(s);
-                if ((ln & 15) == 0) qpart[(h * kWaves + wave) * kRows + r * 16 + 4 * (ln >> 4) + i] = v;
-            }
-        __syncthreads();       // act is free again; qpart[h] complete
-    }
-}
-
 // One pass: rows [base, base + 16 MR) of the chunk's `rows` candidates (candidate c0 + row of env) through the twin heads;
 // q (and z) of the live ones.
 template <int MR>
@@ -234,22 +98,13 @@ __device__ __forceinline__ void score_pass(float* lds, const QsArgs& a, long lon
     q_phase<MR>(lds, a, wave, lane);
     if (tid < kRows && base + tid < rows) {
         const int r = base + tid;
-        float zv[2], q[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            float v = a.b3[h];
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) v += lds[kOffQpart + (h * kWaves + w) * kRows + tid];
-            zv[h] = v;
-            q[h] = sigmoidf(v);
-        }
-        const float qm = (q[0] > q[1] || q[0] != q[0]) ? q[0] : q[1];      // torch.max: NaN propagates
-        lds[kOffQ + r] = qm;
+        const TwinQ t = twin_q(lds, a, tid);
+        lds[kOffQ + r] = t.q;
         const long long row = env * a.k + c0 + r;
-        if (a.q) a.q[row] = qm;
+        if (a.q) a.q[row] = t.q;
         if (a.z) {
-            a.z[row] = zv[0];
-            a.z[(long long)a.n * a.k + row] = zv[1];
+            a.z[row] = t.z[0];
+            a.z[(long long)a.n * a.k + row] = t.z[1];
         }
     }
     // xs and qpart are rewritten only behind the next pass's barriers
@@ -453,17 +308,6 @@ QsArgs block_of(const rrl_qsample_act_t* p, const rrl_qsample_gate_t* g) {
     return a;
 }
 
-template <class K>
-int grant_lds(K kernel, bool& done) {       // > 64 KB of LDS has to be granted explicitly, once per kernel
-    if (done) return RRL_OK;
-    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes) != hipSuccess) {
-        last_hip_error = int(hipGetLastError());
-        return RRL_ELAUNCH;
-    }
-    done = true;
-    return RRL_OK;
-}
-
 // rrl_qsample_act (g == nullptr) and rrl_qsample_act_gated: the two kernels on one argument block
 int launch_solo(const rrl_qsample_act_t* p, const rrl_qsample_gate_t* g, void* stream) {
     const int rc = check_both(p, g);
@@ -471,7 +315,7 @@ int launch_solo(const rrl_qsample_act_t* p, const rrl_qsample_gate_t* g, void* s
     const QsArgs a = block_of(p, g);
     hipStream_t st = (hipStream_t)stream;
     static bool lds_set = false;
-    const int rl = grant_lds(qsample_score_kernel, lds_set);
+    const int rl = grant_lds(qsample_score_kernel, kLdsBytes, lds_set);
     if (rl != RRL_OK) return rl;
     hipLaunchKernelGGL(qsample_score_kernel, dim3((unsigned)((long long)a.n * a.P)), dim3(kThreads), kLdsBytes, st, a);
     const int rs = check_launch();
@@ -517,18 +361,15 @@ int rrl_qsample_act_packed(int S, const rrl_qsample_act_t* args, const rrl_qsamp
     rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
         std::vector<QsArgs> blocks(S);
-        rrl_pack::Idx ix, fx;                   // block ranges of the score and of the fold kernel
-        ix.S = fx.S = S;
-        ix.first[0] = fx.first[0] = 0;
+        int score[rrl_pack::kMaxSeeds], fold[rrl_pack::kMaxSeeds];
         for (int s = 0; s < S; ++s) {
             const QsArgs& a = blocks[s] = block_of(args + s, gates ? gates + s : nullptr);
-            ix.first[s + 1] = ix.first[s] + a.n * a.P;         // n x ceil(k / 128) workgroups, as in the solo kernel
-            fx.first[s + 1] = fx.first[s] + grid_for(a.n);     // one thread per env
+            score[s] = a.n * a.P;                              // n x ceil(k / 128) workgroups, as in the solo kernel
+            fold[s] = grid_for(a.n);                           // one thread per env
         }
-        for (int s = S; s < rrl_pack::kMaxSeeds; ++s) {
-            ix.first[s + 1] = ix.first[S];
-            fx.first[s + 1] = fx.first[S];
-        }
+        rrl_pack::Idx ix, fx;                   // block ranges of the score and of the fold kernel
+        rrl_pack::ranges(ix, S, score);
+        rrl_pack::ranges(fx, S, fold);
         const int grid = rrl_pack::finish(ix), fold_grid = rrl_pack::finish(fx);
         plan = rrl_pack::store(key, blocks.data(), sizeof(QsArgs) * S, st);
         if (!plan) return rrl_pack::store_error();
@@ -538,7 +379,7 @@ int rrl_qsample_act_packed(int S, const rrl_qsample_act_t* args, const rrl_qsamp
         plan->ix2 = fx;
     }
     static bool lds_set = false;
-    const int rc = grant_lds(qsample_score_pack_kernel, lds_set);
+    const int rc = grant_lds(qsample_score_pack_kernel, kLdsBytes, lds_set);
     if (rc != RRL_OK) return rc;
     hipLaunchKernelGGL(qsample_score_pack_kernel, dim3((unsigned)plan->grid), dim3(kThreads), kLdsBytes, st,
                        (const QsArgs*)plan->dev, plan->ix);

@@ -283,14 +283,13 @@ int rrl_sample_multi_packed(int S, const rrl_sample_args_t* args, void* stream) 
             threads = t > threads ? t : threads;
             lds = l > lds ? l : lds;
         }
-        rrl_pack::Idx ix;
-        ix.S = S;
-        ix.first[0] = 0;
+        int count[rrl_pack::kMaxSeeds];
         for (int s = 0; s < S; ++s) {
             noise_blocks(packs[s].nz, threads);
-            ix.first[s + 1] = ix.first[s] + 2 + packs[s].nz.blocks;
+            count[s] = 2 + packs[s].nz.blocks;
         }
-        for (int s = S; s < rrl_pack::kMaxSeeds; ++s) ix.first[s + 1] = ix.first[S];
+        rrl_pack::Idx ix;
+        rrl_pack::ranges(ix, S, count);
         static size_t granted = 64 * 1024;
         if (!grant_sample_lds(sample_pack_kernel, lds, granted)) return RRL_ERANGE;
         plan = rrl_pack::store(key, packs.data(), sizeof(SamplePack) * S, st);

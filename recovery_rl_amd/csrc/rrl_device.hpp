@@ -174,6 +174,22 @@ __device__ __forceinline__ float row16_sum(float v) {
     return v;
 }
 
+// A stack output may arrive as np <= 4 partial sums ps floats apart (rrl_mlp3_forward with scratch and no final sum): element
+// idx = ((p0 + p1) + p2) + p3, the order of the stand-alone sum kernel.  All four loads are issued before the first add (a
+// run-time loop over np chained one memory round trip per part: twelve of them in a row set the 11 us of the critic-loss
+// head backward); partial 0 is read again in the place of an absent one.
+__device__ __forceinline__ float psum(const float* p, long long idx, int np, long long ps) {
+    const float v0 = p[idx];
+    const float v1 = p[(np > 1 ? ps : 0) + idx];
+    const float v2 = p[(np > 2 ? 2 * ps : 0) + idx];
+    const float v3 = p[(np > 3 ? 3 * ps : 0) + idx];
+    float v = v0;
+    v = np > 1 ? v + v1 : v;
+    v = np > 2 ? v + v2 : v;
+    v = np > 3 ? v + v3 : v;
+    return v;
+}
+
 // The recovery gate (experiment.py:568) from the two pre-sigmoid heads of Q_risk(s, a_task): max(sigmoid z0, sigmoid z1) >
 // eps_safe.  fmaxf drops a NaN head for the other one; both NaN: the comparison is false, no recovery.
 __device__ __forceinline__ bool recovery_gate(float z0, float z1, float eps_safe) {

@@ -27,4 +27,16 @@ inline int check_launch() {
     return RRL_OK;
 }
 
+// > 64 KB of dynamic LDS has to be granted explicitly, once per kernel (`done`: the call site's flag for that kernel)
+template <class K>
+int grant_lds(K kernel, int bytes, bool& done) {
+    if (done) return RRL_OK;
+    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+        last_hip_error = int(hipGetLastError());
+        return RRL_ELAUNCH;
+    }
+    done = true;
+    return RRL_OK;
+}
+
 }  // namespace rrl_host

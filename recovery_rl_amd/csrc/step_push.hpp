@@ -664,17 +664,16 @@ inline int launch_packed(rrl_pack::Key& key, int S, const rrl_step_push_t* a, hi
     rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
         std::vector<StepPushArgs> ps(S);
-        rrl_pack::Idx ix;
-        ix.S = S;
-        ix.first[0] = 0;
+        int count[rrl_pack::kMaxSeeds];
         const int regime = regime_of(a[0].n);
         for (int s = 0; s < S; ++s) {
             const int rc = fill_args(ps[s], &a[s]);
             if (rc != RRL_OK) return rc;
             if (a[s].n <= 0 || regime_of(a[s].n) != regime) return RRL_EINVAL;
-            ix.first[s + 1] = ix.first[s] + grid_cover(a[s].n);
+            count[s] = grid_cover(a[s].n);
         }
-        for (int s = S; s < rrl_pack::kMaxSeeds; ++s) ix.first[s + 1] = ix.first[S];
+        rrl_pack::Idx ix;
+        rrl_pack::ranges(ix, S, count);
         plan = rrl_pack::store(key, ps.data(), sizeof(StepPushArgs) * S, st);
         if (!plan) return rrl_pack::store_error();
         plan->grid = rrl_pack::finish(ix);

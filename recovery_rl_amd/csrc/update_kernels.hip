@@ -17,26 +17,12 @@ namespace {
 using rrl_host::check_launch;
 using rrl_host::grid_for;
 using rrl_host::kBlock;
+using rrl::psum;
 
 constexpr float kLogSigMax = 2.f, kLogSigMin = -20.f, kEps = 1e-6f;   // model.py:14-16
 constexpr float kHalfLog2Pi = 0.918938533204672742f;
 
 __device__ __forceinline__ float sigmoidf(float z) { return 1.f / (1.f + expf(-z)); }
-
-// A stack output may arrive as `np` partial sums (rrl_mlp3_forward with scratch and no final sum): element
-// idx = p[idx] + p[ps + idx] + ... in that fixed order (the order of the stand-alone sum kernel).
-__device__ __forceinline__ float psum(const float* p, long long idx, int np, long long ps) {
-    // np <= 4; every load issued before the first add, sum in the fixed order ((p0 + p1) + p2) + p3
-    const float v0 = p[idx];
-    const float v1 = p[(np > 1 ? ps : 0) + idx];
-    const float v2 = p[(np > 2 ? 2 * ps : 0) + idx];
-    const float v3 = p[(np > 3 ? 3 * ps : 0) + idx];
-    float v = v0;
-    v = np > 1 ? v + v1 : v;
-    v = np > 2 ? v + v2 : v;
-    v = np > 3 ? v + v3 : v;
-    return v;
-}
 
 // ---- tanh-Gaussian head (GaussianPolicy.sample, model.py:324-340) -------------------------------
 // head[b] = (mean0, mean1, log_std0, log_std1) raw outputs of the last linear layer
@@ -753,15 +739,14 @@ int rrl_policy_heads_fwd_multi_packed(int S, const int* n, const rrl_policy_head
     rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
         std::vector<HeadGroup> groups(S);
-        rrl_pack::Idx ix;
-        ix.S = S;
-        ix.first[0] = 0;
+        int count[rrl_pack::kMaxSeeds];
         for (int s = 0; s < S; ++s) {               // every seed's heads are validated before anything is stored or launched
             const int rc = build_head_group(n[s], heads[s], groups[s]);
             if (rc != RRL_OK) return rc;
-            ix.first[s + 1] = ix.first[s] + groups[s].first[n[s]];
+            count[s] = groups[s].first[n[s]];
         }
-        for (int s = S; s < rrl_pack::kMaxSeeds; ++s) ix.first[s + 1] = ix.first[S];
+        rrl_pack::Idx ix;
+        rrl_pack::ranges(ix, S, count);
         plan = rrl_pack::store(key, groups.data(), sizeof(HeadGroup) * S, st);
         if (!plan) return rrl_pack::store_error();
         plan->grid = rrl_pack::finish(ix);
@@ -957,9 +942,7 @@ int rrl_adam_step_multi_packed(int S, const int* n_seg, const rrl_adam_seg_t* co
     rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
         std::vector<AdamPack> packs(S);
-        rrl_pack::Idx ix;
-        ix.S = S;
-        ix.first[0] = 0;
+        int count[rrl_pack::kMaxSeeds];
         int segs_most = 1;
         for (int s = 0; s < S; ++s) {
             packs[s] = AdamPack{};
@@ -969,10 +952,11 @@ int rrl_adam_step_multi_packed(int S, const int* n_seg, const rrl_adam_seg_t* co
             packs[s].lr = lr[s]; packs[s].b1 = beta1; packs[s].b2 = beta2; packs[s].eps = eps;
             int most = 1;                 // 2-D grid: a seed owns as many workgroups per segment row as its largest segment has
             for (int k = 0; k < n_seg[s]; ++k) most = std::max(most, packs[s].a.first_block[k + 1] - packs[s].a.first_block[k]);
-            ix.first[s + 1] = ix.first[s] + most;
+            count[s] = most;
             segs_most = std::max(segs_most, n_seg[s]);
         }
-        for (int s = S; s < rrl_pack::kMaxSeeds; ++s) ix.first[s + 1] = ix.first[S];
+        rrl_pack::Idx ix;
+        rrl_pack::ranges(ix, S, count);
         plan = rrl_pack::store(key, packs.data(), sizeof(AdamPack) * S, st);
         if (!plan) return rrl_pack::store_error();
         plan->grid = rrl_pack::finish(ix);
@@ -1007,9 +991,7 @@ int rrl_adam_step_multi_duals_packed(int S, const int* n_seg, const rrl_adam_seg
     rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
         std::vector<AdamDualPack> packs(S);
-        rrl_pack::Idx ix;
-        ix.S = S;
-        ix.first[0] = 0;
+        int count[rrl_pack::kMaxSeeds];
         int segs_most = 0;
         for (int s = 0; s < S; ++s) {               // every seed's segments and duals are validated before anything is launched
             packs[s] = AdamDualPack{};
@@ -1020,10 +1002,11 @@ int rrl_adam_step_multi_duals_packed(int S, const int* n_seg, const rrl_adam_seg
             packs[s].pk.lr = lr[s]; packs[s].pk.b1 = beta1; packs[s].pk.b2 = beta2; packs[s].pk.eps = eps;
             int most = 1;                 // the dual row needs one workgroup of the seed, a segment row as many as its largest segment
             for (int k = 0; k < n_seg[s]; ++k) most = std::max(most, packs[s].pk.a.first_block[k + 1] - packs[s].pk.a.first_block[k]);
-            ix.first[s + 1] = ix.first[s] + most;
+            count[s] = most;
             segs_most = std::max(segs_most, n_seg[s]);
         }
-        for (int s = S; s < rrl_pack::kMaxSeeds; ++s) ix.first[s + 1] = ix.first[S];
+        rrl_pack::Idx ix;
+        rrl_pack::ranges(ix, S, count);
         plan = rrl_pack::store(key, packs.data(), sizeof(AdamDualPack) * S, st);
         if (!plan) return rrl_pack::store_error();
         plan->grid = rrl_pack::finish(ix);

@@ -163,3 +163,26 @@ def test_early_tickets_are_not_waited_for_on_the_spot(kernels):
                 if op.startswith("global_atomic_add"):
                     tail = ins[i + 1:i + 5]
                     assert not ("s_waitcnt" in tail and "v_readfirstlane_b32" in tail), (k, i, tail)
+
+
+# ---- one definition per shared device helper (csrc/mfma_tile.hpp, csrc/rrl_device.hpp) ------------------------------------
+SHARED_HELPERS = {"mfma": "f32x4 mfma(", "opaque": "int opaque(", "reluf": "float reluf(", "reduce16": "float reduce16(",
+                  "psum": "float psum("}
+
+
+def test_shared_device_helpers_are_defined_once():
+    """The MFMA tile's primitives and psum used to be restated per kernel file "so that no kernel moves"; shared from one
+    header they compile to the same instructions (profiles/shared_tile_fingerprint.txt).  A definition is recognised by its
+    signature line; a copy that grows back in another file shows up here."""
+    sources = sorted(glob.glob(os.path.join(_lib.CSRC, "*.hip")) + glob.glob(os.path.join(_lib.CSRC, "*.hpp")))
+    assert len(sources) > 15
+    where = {name: [] for name in SHARED_HELPERS}
+    for path in sources:
+        for line in open(path):
+            code = line.split("//")[0]
+            for name, signature in SHARED_HELPERS.items():
+                if signature in code:
+                    where[name].append(os.path.basename(path))
+    expected = {"mfma": ["mfma_tile.hpp"], "opaque": ["mfma_tile.hpp"], "reluf": ["mfma_tile.hpp"],
+                "reduce16": ["mfma_tile.hpp"], "psum": ["rrl_device.hpp"]}
+    assert where == expected
