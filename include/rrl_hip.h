@@ -893,9 +893,10 @@ int rrl_ens_train_epoch_big(const rrl_ens_t* m, int n_seg, const rrl_adam_seg_t*
  *   rrl_eval_rollout_packed                rrl_eval_rollout            (args[s]; seed s gets its ceil(n[s] / 16) workgroups and
  *                                          its tick is advanced by the last of them; n, T, env kind, weights, groups, seed, tick
  *                                          and traces may differ by seed)
+ *   rrl_eval_rollout_maze_packed           rrl_eval_rollout_maze       (args[s], horizon[s]; the same mapping on the Maze kernel)
  * Every seed's arguments are checked before anything is stored or launched (the stand-alone entry's codes); a NULL array:
- * RRL_EINVAL; S outside 1 .. 16: RRL_EINVAL, except from rrl_eval_rollout_packed, which returns RRL_ERANGE for it.  S == 1 is
- * the stand-alone launch.
+ * RRL_EINVAL; S outside 1 .. 16: RRL_EINVAL, except from rrl_eval_rollout[_maze]_packed, which return RRL_ERANGE for it.
+ * S == 1 is the stand-alone launch.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
     const rrl_draw_t *first, *second;
@@ -1099,6 +1100,25 @@ int rrl_eval_rollout(const rrl_eval_rollout_t* a, void* stream);
  * its outputs the bits of its stand-alone launch.  Every seed is checked as the stand-alone entry checks it, all before
  * anything is stored or launched; args == NULL: RRL_EINVAL; S outside 1 .. 16: RRL_ERANGE; S == 1 is rrl_eval_rollout(args). */
 int rrl_eval_rollout_packed(int S, const rrl_eval_rollout_t* args, void* stream);
+
+/* The same rollout for n Maze envs (MazeVecEnv(auto_reset = False)): the SAME descriptor on kernels of their own, so the
+ * Navigation kernels carry no Maze branch.  Networks, gate, recovery noise, results, traces and the tile are those above;
+ * the env part is rrl_maze_step / rrl_maze_reset's device code (maze_device.hpp), bit for bit:
+ *   start      reset != 0: pos_i = the draw of rrl_maze_reset(mode 0, check_constraint 1) at the tick, rejection loop
+ *              included; reset == 0: pos_i = pos[i].  The episode clock starts at 0 either way.
+ *   step j     obs, task, gate and recovery action as above (noise: RRL_STREAM_EVAL at tick + reset + j);
+ *              new = move(pos, double(executed)) -- the move clamps to +-0.1 itself, the traces hold the unclipped action;
+ *              d = goal distance of new, reward = float(-d), constraint = contact at new, success = -d > -0.03:
+ *              all judged at the NEW state (Navigation's cost is judged at the old one);
+ *              done = (j + 1 >= horizon) | constraint | (d < 0.03): a row that reaches the horizon is done with neither flag.
+ *   tick       counter_dev[0] += T + reset: the Maze step draws nothing, but the eager step() advances the tick by 1 as well.
+ * Checks: the descriptor's, except that env_kind must be RRL_ENV_MAZE (a Navigation kind is RRL_EINVAL here, as Maze is
+ * there); horizon outside 1 .. 2^30: RRL_ERANGE (an invalid field wins). */
+int rrl_eval_rollout_maze(const rrl_eval_rollout_t* a, int horizon, void* stream);
+/* ... and for S seeds side by side, horizon[s] seed s's (part of the plan key).  args or horizon NULL: RRL_EINVAL; S outside
+ * 1 .. 16: RRL_ERANGE; every seed is checked before anything is stored or launched; S == 1 is
+ * rrl_eval_rollout_maze(args, horizon[0]). */
+int rrl_eval_rollout_maze_packed(int S, const rrl_eval_rollout_t* args, const int* horizon, void* stream);
 
 #ifdef __cplusplus
 }

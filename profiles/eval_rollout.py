@@ -1,8 +1,10 @@
 """Policy evaluation at 4096 envs, Navigation 1, model-free recovery, hidden 256: the eager module path
 (Experiment.get_test_rollout_vectorized as the parent commit runs it: horizon + 1 x loop.act(train=False) + env.step) against
-the rrl_eval_rollout kernel path (RRL_FAST_EVAL=1), in one process.
+the rrl_eval_rollout kernel path (RRL_FAST_EVAL=1), in one process.  `--env maze`: the same for Maze with the flags of
+BASELINE config 3, the kernel path being rrl_eval_rollout_maze (RRL_FAST_EVAL=1 with RRL_FAST_EVAL_MAZE=1).
 
     python profiles/eval_rollout.py [--envs 4096] [--repeats 7] [--out profiles/eval_rollout.json]
+    python profiles/eval_rollout.py --env maze --out profiles/eval_rollout_maze.json
 
 Two measurements:
   * ONE evaluation, warm (one untimed call first), repeated: wall clock around the call with a device synchronisation on both
@@ -27,19 +29,22 @@ sys.path.insert(0, ROOT)
 import arg_utils  # noqa: E402
 from recovery_rl_amd.experiment import Experiment  # noqa: E402
 
-MF = ["--use_recovery", "--MF_recovery", "--gamma_safe", "0.8", "--eps_safe", "0.3"]
+MF = {"navigation1": ["--use_recovery", "--MF_recovery", "--gamma_safe", "0.8", "--eps_safe", "0.3"],
+      "maze": ["--use_recovery", "--MF_recovery", "--gamma_safe", "0.5", "--eps_safe", "0.15", "--pos_fraction", "0.3"]}
+ENV = "navigation1"
 
 
 def cfg(envs, logdir, extra=()):
-    return arg_utils.get_args(["--env-name", "navigation1", "--cuda", "--hidden_size", "256", "--num_envs", str(envs),
-                               "--seed", "1", "--num_unsafe_transitions", "4000", "--logdir", logdir] + MF + list(extra))
+    return arg_utils.get_args(["--env-name", ENV, "--cuda", "--hidden_size", "256", "--num_envs", str(envs),
+                               "--seed", "1", "--num_unsafe_transitions", "4000", "--logdir", logdir] + MF[ENV] + list(extra))
 
 
 def set_path(path):
-    if path == "hip":
-        os.environ["RRL_FAST_EVAL"] = "1"
-    else:
-        os.environ.pop("RRL_FAST_EVAL", None)
+    for switch in ("RRL_FAST_EVAL", "RRL_FAST_EVAL_MAZE"):
+        if path == "hip":
+            os.environ[switch] = "1"
+        else:
+            os.environ.pop(switch, None)
 
 
 def timed(fn):
@@ -93,10 +98,12 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--env", choices=sorted(MF), default=ENV)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "eval_rollout.json"))
     a = ap.parse_args()
+    ENV = a.env
     with tempfile.TemporaryDirectory() as tmp:
-        result = {"envs": a.envs, "device": torch.cuda.get_device_name(0), "one_evaluation": one_evaluation(a.envs, a.repeats, tmp),
+        result = {"env": a.env, "envs": a.envs, "device": torch.cuda.get_device_name(0), "one_evaluation": one_evaluation(a.envs, a.repeats, tmp),
                   "run_share": run_share(a.envs, tmp)}
     set_path("modules")
     with open(a.out, "w") as f:

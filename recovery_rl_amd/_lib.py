@@ -53,7 +53,7 @@ EXPORTS = [
     "rrl_ens_train_big_supported", "rrl_ens_big_scratch_floats", "rrl_ens_train_grad_big", "rrl_ens_train_epoch_big",
     "rrl_sqrl_scratch_floats", "rrl_sqrl_act", "rrl_sqrl_act_packed",
     "rrl_qsample_scratch_floats", "rrl_qsample_act", "rrl_qsample_act_gated", "rrl_qsample_act_packed",
-    "rrl_eval_rollout", "rrl_eval_rollout_packed",
+    "rrl_eval_rollout", "rrl_eval_rollout_packed", "rrl_eval_rollout_maze", "rrl_eval_rollout_maze_packed",
 ]
 
 class RRLError(RuntimeError):
@@ -315,6 +315,7 @@ class rrl_qsample_gate_t(C.Structure):
 
 
 STREAM_EVAL = 12
+ENV_NAV1, ENV_NAV2, ENV_MAZE = 0, 1, 2          # RRL_ENV_*: rrl_eval_rollout_t.env_kind
 
 
 class rrl_eval_rollout_t(C.Structure):
@@ -415,6 +416,8 @@ def _declare(lib):
         "rrl_qsample_act_packed": (ci, [ci, C.POINTER(rrl_qsample_act_t), C.POINTER(rrl_qsample_gate_t), vp]),
         "rrl_eval_rollout": (ci, [C.POINTER(rrl_eval_rollout_t), vp]),
         "rrl_eval_rollout_packed": (ci, [ci, C.POINTER(rrl_eval_rollout_t), vp]),
+        "rrl_eval_rollout_maze": (ci, [C.POINTER(rrl_eval_rollout_t), ci, vp]),
+        "rrl_eval_rollout_maze_packed": (ci, [ci, C.POINTER(rrl_eval_rollout_t), C.POINTER(ci), vp]),
         "rrl_episode_log_append": (ci, [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(rrl_episode_log_t), vp]),
     }
     for name, (res, args) in sig.items():

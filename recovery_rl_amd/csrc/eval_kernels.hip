@@ -1,6 +1,6 @@
 // eval_kernels.hip -- policy evaluation (Experiment.get_test_rollout, recovery_rl/experiment.py:493-538) for gfx950: one
-// deterministic-policy episode of n Navigation 1 / 2 envs -- reset, then T x (task policy -> Q_risk gate -> recovery policy ->
-// transition), per-env return and flags -- as ONE launch with no launch boundary inside.
+// deterministic-policy episode of n Navigation 1 / 2 or Maze envs -- reset, then T x (task policy -> Q_risk gate -> recovery
+// policy -> transition), per-env return and flags -- as ONE launch with no launch boundary inside.
 //
 // The module path runs horizon + 1 times three nn.Linear stacks, an eager env step and a handful of small torch ops: a few
 // thousand dependent launches.  Here a workgroup owns a tile of 16 envs for the whole rollout: the env state (double position,
@@ -18,7 +18,10 @@
 // (rollout_tile); they differ only in where the argument block and the tile index come from.
 //
 // The tile's primitives and layer-2 helpers come from mfma_tile.hpp (one row tile: MR = 1); run_stack is this file's own,
-// for its 16 rows, DIN < 4 inputs and NOUT outputs.  The transition is restated from nav_kernels.hip's NavEnv.
+// for its 16 rows, DIN < 4 inputs and NOUT outputs.  The body is generic over the env (a trait with reset and step, as
+// step_push.hpp's): NavRoll restates nav_kernels.hip's NavEnv, MazeRoll is maze_device.hpp's transition behind kernels of
+// its own (rrl_eval_rollout_maze[_packed]), so the Navigation kernels carry no Maze branch.
+#include "maze_device.hpp"
 #include "mfma_tile.hpp"
 #include "pack.hpp"
 #include "rrl_device.hpp"
@@ -152,9 +155,58 @@ __device__ __forceinline__ bool nav_step(int kind, double x, double y, float ax,
     return rrl::in_obstacle<1>(nx, ny);
 }
 
+// What one transition leaves: the next state, the reward and the three flags of the eager env's step()
+struct Outcome {
+    double nx, ny;
+    float rew;
+    bool cons, succ, done;
+};
+
+// Navigation 1 / 2: start at START + N(0, I); the cost is judged at the OLD state, done = success | constraint
+struct NavRoll {
+    __device__ __forceinline__ void reset(const EvArgs& a, long long row, uint64_t tick, double& x, double& y) const {
+        double z0, z1;                                       // NavEnv::reset: START_STATE + randn(2)
+        rrl::normal_at(a.seed, uint32_t(row), rrl::kStreamReset, tick, z0, z1);
+        x = -50.0 + z0;
+        y = 0.0 + z1;
+    }
+    __device__ __forceinline__ Outcome step(const EvArgs& a, long long row, uint64_t ctr, int, double x, double y, float ax,
+                                            float ay) const {
+        double ex, ey, nx, ny, cost;
+        rrl::normal_at(a.seed, uint32_t(row), rrl::kStreamStep, ctr, ex, ey);
+        const bool cons = nav_step(a.kind, x, y, ax, ay, ex, ey, nx, ny, cost);
+        const bool sc = cost > -4.0;
+        const bool dn = sc | cons;
+        return Outcome{nx, ny, float(cost), cons, sc, dn};
+    }
+};
+
+// Maze (MazeVecEnv(auto_reset=False), maze_kernels.hip's maze_step_kernel / MazeEnv): reset of mode 0 with the rejection
+// loop; the step draws nothing, the reward is judged at the NEW state, and the env's own horizon ends a row with neither flag
+struct MazeRoll {
+    int horizon;
+    __device__ __forceinline__ void reset(const EvArgs& a, long long row, uint64_t tick, double& x, double& y) const {
+        rrl_maze::reset_one(a.seed, uint32_t(row), tick, 0, true, x, y);
+    }
+    __device__ __forceinline__ Outcome step(const EvArgs&, long long, uint64_t, int j, double x, double y, float ax,
+                                            float ay) const {
+        Outcome o;
+        o.nx = x;
+        o.ny = y;
+        rrl_maze::move(o.nx, o.ny, double(ax), double(ay));  // clamps to +-0.1 itself
+        const double d = rrl_maze::goal_distance(o.nx, o.ny);
+        o.rew = float(-d);
+        o.cons = rrl_maze::in_contact(o.nx, o.ny);
+        o.succ = -d > -0.03;
+        o.done = (j + 1 >= horizon) | o.cons | (d < rrl_maze::kGoalThresh);
+        return o;
+    }
+};
+
 // Workgroup b of the argument block's own grid: envs [16 b, 16 (b + 1)) through the whole rollout.  Thread tid < 16
 // owns env 16 b + tid: state and results in its registers, written once at the end.
-__device__ __forceinline__ void rollout_tile(const EvArgs& a, unsigned b, float* lds) {
+template <class Env>
+__device__ __forceinline__ void rollout_tile(const EvArgs& a, const Env& env, unsigned b, float* lds) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int R = kRows;
@@ -167,11 +219,8 @@ __device__ __forceinline__ void rollout_tile(const EvArgs& a, unsigned b, float*
 
     double x = 0.0, y = 0.0;
     if (mine) {
-        if (a.reset) {                                       // NavEnv::reset: START_STATE + randn(2)
-            double z0, z1;
-            rrl::normal_at(a.seed, uint32_t(row), rrl::kStreamReset, tick, z0, z1);
-            x = -50.0 + z0;
-            y = 0.0 + z1;
+        if (a.reset) {
+            env.reset(a, row, tick, x, y);
         } else {
             x = a.pos[2 * row];
             y = a.pos[2 * row + 1];
@@ -228,12 +277,9 @@ __device__ __forceinline__ void rollout_tile(const EvArgs& a, unsigned b, float*
         // ---- transition ----
         if (alive) {
             const long long o = (long long)j * a.n + row;
-            double ex, ey, nx, ny, cost;
-            rrl::normal_at(a.seed, uint32_t(row), rrl::kStreamStep, ctr, ex, ey);
-            const bool cons = nav_step(a.kind, x, y, r0, r1, ex, ey, nx, ny, cost);
-            const bool sc = cost > -4.0;
-            const bool dn = sc | cons;
-            const float rew = float(cost);
+            const Outcome t = env.step(a, row, ctr, j, x, y, r0, r1);
+            const bool cons = t.cons, sc = t.succ, dn = t.done;
+            const float rew = t.rew;
             if (a.tr_pos) {
                 a.tr_pos[2 * o] = x;
                 a.tr_pos[2 * o + 1] = y;
@@ -260,8 +306,8 @@ __device__ __forceinline__ void rollout_tile(const EvArgs& a, unsigned b, float*
             succ |= sc;
             viol |= cons;
             ++steps;
-            x = nx;
-            y = ny;
+            x = t.nx;
+            y = t.ny;
             alive = !dn;
         }
     }
@@ -277,7 +323,7 @@ __device__ __forceinline__ void rollout_tile(const EvArgs& a, unsigned b, float*
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void eval_rollout_kernel(const EvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    rollout_tile(a, blockIdx.x, lds);
+    rollout_tile(a, NavRoll{}, blockIdx.x, lds);
 }
 
 // The copied argument block's pointers as global ones (pack.hpp: to_global)
@@ -299,7 +345,31 @@ void eval_rollout_pack_kernel(const EvArgs* __restrict__ blocks, rrl_pack::Idx i
     if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
     EvArgs a = blocks[s];
     globalize(a);
-    rollout_tile(a, unsigned(local), lds);
+    rollout_tile(a, NavRoll{}, unsigned(local), lds);
+}
+
+// The Maze kernels: the same body on MazeRoll.  The argument block is EvArgs unchanged; the horizon rides beside it (the
+// solo kernel's second argument, MazeBlock's tail in a packed plan), so the Navigation kernels' argument offsets stay put.
+struct MazeBlock {
+    EvArgs a;
+    int horizon;
+};
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void eval_rollout_maze_kernel(const EvArgs a, int horizon) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    rollout_tile(a, MazeRoll{horizon}, blockIdx.x, lds);
+}
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void eval_rollout_maze_pack_kernel(const MazeBlock* __restrict__ blocks, rrl_pack::Idx ix) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int s, local;
+    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
+    EvArgs a = blocks[s].a;
+    const int horizon = blocks[s].horizon;
+    globalize(a);
+    rollout_tile(a, MazeRoll{horizon}, unsigned(local), lds);
 }
 
 template <size_t N>
@@ -309,8 +379,10 @@ int given(const void* const (&p)[N]) {
     return k;
 }
 
-// the checks of a descriptor, before any launch (rrl_hip.h)
-int check_desc(const rrl_eval_rollout_t* p) {
+constexpr int kMaxHorizon = 1 << 30;
+
+// the checks of a descriptor, before any launch (rrl_hip.h); maze: the entry's env is Maze, else Navigation 1 / 2
+int check_desc(const rrl_eval_rollout_t* p, bool maze = false) {
     if (!p) return RRL_EINVAL;
     const void* const need[] = {p->pW1, p->pb1, p->pW2p, p->pb2, p->pW3, p->pb3, p->scale, p->bias,
                                 p->ret, p->success, p->violation, p->steps};
@@ -319,7 +391,8 @@ int check_desc(const rrl_eval_rollout_t* p) {
     const int nq = given(qg), nr = given(rg);
     const auto aligned = [](const void* w) { return (reinterpret_cast<uintptr_t>(w) & 15) == 0; };
     if (given(need) != 12 || (nq != 0 && nq != 6) || (nr != 0 && nr != 9) || (nr && !nq) || p->H != kH || p->d_obs != 2 ||
-        p->d_act != 2 || p->n <= 0 || (p->env_kind != RRL_ENV_NAV1 && p->env_kind != RRL_ENV_NAV2) || !aligned(p->pW2p) ||
+        p->d_act != 2 || p->n <= 0 || !(maze ? p->env_kind == RRL_ENV_MAZE : (p->env_kind == RRL_ENV_NAV1 || p->env_kind == RRL_ENV_NAV2)) ||
+        !aligned(p->pW2p) ||
         !aligned(p->qW2p) || !aligned(p->rW2p) || (!p->reset && !p->pos))
         return RRL_EINVAL;
     if (p->T < 1 || p->T > kMaxT || p->n > kMaxN) return RRL_ERANGE;
@@ -369,6 +442,21 @@ int launch_solo(const rrl_eval_rollout_t* p, void* stream) {
     return check_launch();
 }
 
+int check_maze(const rrl_eval_rollout_t* p, int horizon) {
+    const int rc = check_desc(p, true);
+    if (rc != RRL_OK) return rc;
+    return horizon < 1 || horizon > kMaxHorizon ? RRL_ERANGE : RRL_OK;
+}
+
+int launch_maze_solo(const rrl_eval_rollout_t* p, int horizon, void* stream) {
+    const int rc = check_maze(p, horizon);
+    if (rc != RRL_OK) return rc;
+    const EvArgs a = block_of(p);
+    hipLaunchKernelGGL(eval_rollout_maze_kernel, dim3((unsigned)a.blocks), dim3(kThreads), kLdsBytes, (hipStream_t)stream, a,
+                       horizon);
+    return check_launch();
+}
+
 }  // namespace
 
 extern "C" {
@@ -410,6 +498,48 @@ int rrl_eval_rollout_packed(int S, const rrl_eval_rollout_t* args, void* stream)
     }
     hipLaunchKernelGGL(eval_rollout_pack_kernel, dim3((unsigned)plan->grid), dim3(kThreads), kLdsBytes, st,
                        (const EvArgs*)plan->dev, plan->ix);
+    return check_launch();
+}
+
+int rrl_eval_rollout_maze(const rrl_eval_rollout_t* p, int horizon, void* stream) {
+    return launch_maze_solo(p, horizon, stream);
+}
+
+int rrl_eval_rollout_maze_packed(int S, const rrl_eval_rollout_t* args, const int* horizon, void* stream) {
+    if (!args || !horizon) return RRL_EINVAL;
+    if (S <= 0 || S > rrl_pack::kMaxSeeds) return RRL_ERANGE;
+    int worst = RRL_OK;
+    for (int s = 0; s < S; ++s) {               // every seed is checked before anything is stored or launched
+        const int rc = check_maze(args + s, horizon[s]);
+        if (rc == RRL_EINVAL) return rc;        // an invalid field wins over a size out of range, whichever seed has it
+        if (rc != RRL_OK) worst = rc;
+    }
+    if (worst != RRL_OK) return worst;
+    if (S == 1) return launch_maze_solo(args, horizon[0], stream);
+    rrl_pack::Key key;
+    key.pod(14);
+    key.pod(S);
+    key.add(args, sizeof(rrl_eval_rollout_t) * S);
+    key.add(horizon, sizeof(int) * S);
+    hipStream_t st = (hipStream_t)stream;
+    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    if (!plan) {
+        std::vector<MazeBlock> blocks(S);
+        int count[rrl_pack::kMaxSeeds];
+        for (int s = 0; s < S; ++s) {
+            blocks[s] = MazeBlock{block_of(args + s), horizon[s]};
+            count[s] = blocks[s].a.blocks;
+        }
+        rrl_pack::Idx ix;
+        rrl_pack::ranges(ix, S, count);
+        const int grid = rrl_pack::finish(ix);
+        plan = rrl_pack::store(key, blocks.data(), sizeof(MazeBlock) * S, st);
+        if (!plan) return rrl_pack::store_error();
+        plan->grid = grid;
+        plan->ix = ix;
+    }
+    hipLaunchKernelGGL(eval_rollout_maze_pack_kernel, dim3((unsigned)plan->grid), dim3(kThreads), kLdsBytes, st,
+                       (const MazeBlock*)plan->dev, plan->ix);
     return check_launch();
 }
 

@@ -28,6 +28,7 @@ class MazeVecEnv(StatusWordMixin):
     def __init__(self, env_name="maze", num_envs=1, device="cuda", seed=0, horizon=HORIZON,
                  auto_reset=True):
         self.env_name = "maze"
+        self.kind = _lib.ENV_MAZE
         self.device = _lib.require_gpu(device)
         self.lib = _lib.load()
         self.num_envs = int(num_envs)

@@ -1077,7 +1077,8 @@ class Experiment:
         env = self.eval_env()
         rollout = self.eval_rollout()
         if rollout is not None:
-            # RRL_FAST_EVAL=1: reset, the horizon + 1 steps and the per-env results in one launch (rrl_eval_rollout)
+            # RRL_FAST_EVAL=1: reset, the horizon + 1 steps and the per-env results in one launch (rrl_eval_rollout; Maze,
+            # with RRL_FAST_EVAL_MAZE=1 as well: rrl_eval_rollout_maze, whose rows the env's horizon ends one step earlier)
             rollout.launch(env._max_episode_steps + 1)
             return self._eval_result(rollout.stats(label))
         self.vector_rules.pop("evaluation", None)          # the rule records the path the LAST evaluation took

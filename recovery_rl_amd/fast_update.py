@@ -1218,13 +1218,19 @@ def fast_eval_enabled():
     return os.environ.get("RRL_FAST_EVAL", "0") == "1"
 
 
+def fast_eval_maze_enabled():
+    """RRL_FAST_EVAL_MAZE=1, on top of RRL_FAST_EVAL=1: Maze evaluates on rrl_eval_rollout_maze (opt-in; eval_rollout_path)."""
+    return os.environ.get("RRL_FAST_EVAL_MAZE", "0") == "1"
+
+
 def eval_rollout_path(cfg):
     """Where Experiment.get_test_rollout_vectorized runs: "hip" (EvalRollout: one launch) under RRL_FAST_EVAL=1 on the fused
-    path at hidden width 256, Navigation 1 / 2, the lock-step loop, without a recovery policy or with the model-free one;
-    else "modules" (the loop's act() on the torch modules and the eager env), which Maze, Q-sampling, SQRL, model-based
-    recovery and every other configuration keep."""
+    path at hidden width 256, Navigation 1 / 2 -- or Maze with RRL_FAST_EVAL_MAZE=1 as well --, the lock-step loop, without
+    a recovery policy or with the model-free one; else "modules" (the loop's act() on the torch modules and the eager env),
+    which Q-sampling, SQRL, model-based recovery and every other configuration keep."""
+    envs = ("navigation1", "navigation2") + (("maze",) if fast_eval_maze_enabled() else ())
     hip = (fast_eval_enabled() and fast_path_supported(cfg) and not getattr(cfg, "no_fast_path", False)
-           and int(cfg.hidden_size) == 256 and cfg.env_name in ("navigation1", "navigation2")
+           and int(cfg.hidden_size) == 256 and cfg.env_name in envs
            and int(getattr(cfg, "num_envs", 1)) > 1 and not cfg.use_constraint_sampling
            and (not cfg.use_recovery or bool(cfg.MF_recovery)))
     return "hip" if hip else "modules"
@@ -1274,8 +1280,16 @@ class EvalRollout:
         self.args = a              # keeps the argument block alive until the launch has been issued
         return a
 
+    @property
+    def maze(self):
+        return self.env.kind == _lib.ENV_MAZE
+
     def launch(self, T, **kw):
         a = self.desc(T, **kw)
+        if self.maze:      # the env's own horizon ends a row: a launch argument of the Maze entry (T stays horizon + 1)
+            _lib.check(self.f.lib.rrl_eval_rollout_maze(C.byref(a), int(self.env.horizon), _lib.current_stream()),
+                       "rrl_eval_rollout_maze")
+            return
         _lib.check(self.f.lib.rrl_eval_rollout(C.byref(a), _lib.current_stream()), "rrl_eval_rollout")
 
     def stats(self, label):
@@ -1286,8 +1300,14 @@ class EvalRollout:
 
 
 def eval_rollouts_packed(rollouts, T):
-    """The evaluations of several seeds (EvalRollout each) as ONE rrl_eval_rollout_packed launch."""
+    """The evaluations of several seeds (EvalRollout each) as ONE rrl_eval_rollout_packed launch (one env per packed run:
+    rrl_eval_rollout_maze_packed with every seed's env horizon when that env is Maze)."""
     args = (_lib.rrl_eval_rollout_t * len(rollouts))(*[r.desc(T) for r in rollouts])
+    if rollouts[0].maze:
+        horizon = (C.c_int * len(rollouts))(*[int(r.env.horizon) for r in rollouts])
+        _lib.check(_lib.load().rrl_eval_rollout_maze_packed(len(rollouts), args, horizon, _lib.current_stream()),
+                   "rrl_eval_rollout_maze_packed")
+        return
     _lib.check(_lib.load().rrl_eval_rollout_packed(len(rollouts), args, _lib.current_stream()), "rrl_eval_rollout_packed")
 
 
