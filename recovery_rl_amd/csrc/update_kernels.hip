@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
+#include <mutex>
 
 #include "rrl_device.hpp"
 #include "pack.hpp"
@@ -328,7 +330,31 @@ struct AdamSegs {
     rrl_adam_seg_t seg[RRL_ADAM_MAX_SEGS];
     int vec[RRL_ADAM_MAX_SEGS];                  // every pointer of the segment is 16-byte aligned
     int first_block[RRL_ADAM_MAX_SEGS + 1];      // workgroups [first_block[k], first_block[k+1]) serve segment k
+    int memo[RRL_ADAM_MAX_SEGS];                 // the segment's slot in adam_memo (solo launches; -1: none)
 };
+
+// The two bias corrections of step count t.  Each double pow() is a ~230-instruction dependent chain (~1 us) in front of
+// the arithmetic, yet (beta1, beta2, t) are known one launch ahead: a solo launch carries one more workgroup per segment
+// that works out the corrections of the NEXT step and leaves them here, and the next launch on that step counter picks
+// them up instead of calling pow().  An entry is a pure function of its tag (t, bits of beta1, bits of beta2), computed
+// by the device code below whoever wrote it: a reader that finds its whole tag uses the values, any other reader (first
+// launch, a step counter set from the host, other betas, no slot) takes the pow() path.  A slot belongs to one step_dev
+// address for the life of the process (adam_memo_slots) and holds the entries of even and odd t: a launch reads the one
+// of t = step + 1 while its own extra workgroup writes the one of step + 2, and the launch boundary hands it over.
+struct alignas(32) AdamMemoEntry {
+    uint64_t t;
+    uint32_t b1_bits, b2_bits;
+    float om_b1t, bc2_sqrt;                      // float(1 - b1^t), float(sqrt(1 - b2^t)), the powers in double
+    uint32_t pad[2];
+};
+constexpr int kAdamMemoSlots = 256;
+constexpr int kAdamShared = 8;                   // floats of LDS the prologue of adam_seg_body passes values through
+__device__ AdamMemoEntry adam_memo[kAdamMemoSlots][2];
+__device__ __forceinline__ float adam_om_b1t(float b1, uint64_t t) { return float(1.0 - pow(double(b1), double(t))); }
+__device__ __forceinline__ float adam_bc2_sqrt(float b2, uint64_t t) { return float(sqrt(1.0 - pow(double(b2), double(t)))); }
+__device__ __forceinline__ bool adam_memo_hit(const AdamMemoEntry& e, uint64_t t, float b1, float b2) {
+    return e.t == t && e.b1_bits == __float_as_uint(b1) && e.b2_bits == __float_as_uint(b2);
+}
 
 __device__ __forceinline__ float adam_elem(float& p, float g, float& m, float& v, float step_size, float bc2_sqrt,
                                            float b1, float b2, float eps, float wd) {
@@ -389,9 +415,9 @@ __device__ __forceinline__ void adam_slot_load(const AdamVec& a, long long i0, A
     const float4* p4 = reinterpret_cast<const float4*>(a.p);
     const float4* m4 = reinterpret_cast<const float4*>(a.m);
     const float4* v4 = reinterpret_cast<const float4*>(a.v);
-    const float4* t4 = reinterpret_cast<const float4*>(a.target);
+    const float4* t4 = reinterpret_cast<const float4*>(a.target ? a.target : a.p);
     const float4* g4 = reinterpret_cast<const float4*>(a.g);
-    const float4* h4 = reinterpret_cast<const float4*>(a.g2);
+    const float4* h4 = reinterpret_cast<const float4*>(a.g2 ? a.g2 : a.g);
     s.i0 = i0;
     s.i1 = i0 + a.stride;
     s.two = s.i1 < a.n4;
@@ -400,12 +426,22 @@ __device__ __forceinline__ void adam_slot_load(const AdamVec& a, long long i0, A
     s.G[0] = g4[i0]; s.G[1] = g4[j1];
     s.M[0] = m4[i0]; s.M[1] = m4[j1];
     s.V[0] = v4[i0]; s.V[1] = v4[j1];
-    if (4 * i0 < a.pe) s.G[0] = part_sum4(a.gp, a.np, a.ps, i0);          // pe % 4 == 0: a float4 is inside or outside
-    if (4 * j1 < a.pe) s.G[1] = part_sum4(a.gp, a.np, a.ps, j1);
-    s.T[0] = s.P[0]; s.T[1] = s.P[1];
-    s.Hh[0] = s.Hh[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a.target) { s.T[0] = t4[i0]; s.T[1] = t4[j1]; }
-    if (a.g2) { s.Hh[0] = h4[i0]; s.Hh[1] = h4[j1]; }
+    // an absent target / g2 is requested at p / g (lines this thread asks for anyway) and its value never used: a load under
+    // `if (a.target)` was merged with T = P at the end of the branch, behind a wait for P -- a second dependent round trip
+    s.T[0] = t4[i0]; s.T[1] = t4[j1];
+    s.Hh[0] = h4[i0]; s.Hh[1] = h4[j1];
+    // the partial sums under a WAVE-uniform branch (pe % 4 == 0: a float4 is inside or outside): the waves that touch the range
+    // ask for the partials right behind the operands above, with no wait in between, the others ask for nothing; a lane outside
+    // the range reads float4 0 of it and keeps its g.  (Per-lane branches waited for g before the first partial was requested.)
+    const bool in0 = 4 * i0 < a.pe, in1 = 4 * j1 < a.pe;
+    if (__builtin_amdgcn_ballot_w64(in0) != 0) {
+        const float4 acc = part_sum4(a.gp, a.np, a.ps, in0 ? i0 : 0);
+        if (in0) s.G[0] = acc;
+    }
+    if (__builtin_amdgcn_ballot_w64(in1) != 0) {
+        const float4 acc = part_sum4(a.gp, a.np, a.ps, in1 ? j1 : 0);
+        if (in1) s.G[1] = acc;
+    }
 }
 __device__ __forceinline__ void adam_slot_finish(const AdamVec& a, AdamSlot& s, float step_size, float bc2_sqrt, float b1,
                                                  float b2, float eps, float tau, float wd) {
@@ -539,19 +575,110 @@ __device__ __forceinline__ void adam_seg_body(const rrl_adam_seg_t& sg, bool vec
     }
 }
 
+// adam_seg_body for a segment of a solo launch that has a memo slot (`memo` >= 0).  The segment has one workgroup
+// more (block == blocks, the WRITER): it touches no parameter, takes the same prologue for t = step + 2 and stores the
+// result in the slot's entry of that parity.  It joins the ticket, so its read of the step count is ordered before the
+// store of step + 1 like everybody's.
+// sh[]: 0 step size, 1 bc2_sqrt of the memo, 2 / 3 the step count as thread 0 / thread 64 read it, 4 thread 0 found the memo,
+// 5 bc2_sqrt by pow(), 6 thread 64 called no pow(), 7 1 - b1^t
+__device__ __forceinline__ void adam_seg_body_memo(const rrl_adam_seg_t& sg, bool vec, float lr, float b1, float b2, float eps,
+                                                   int block, int blocks, float* sh, int memo) {
+    // the step count and both entries of the memo slot are requested first (64 bytes, every thread the same: which entry
+    // counts depends on the step count, no request does), then the thread's first two float4 slots of every operand --
+    // before anything waits for the step count
+    // (the index 0 out of a vector register: values the compiler knows to be wave-uniform -- the parity select below makes it
+    // look -- are moved into scalar registers right behind their loads, with a wait in front of every operand request)
+    int zero = 0;
+    asm volatile("" : "+v"(zero));
+    const uint64_t step = sg.step_dev[zero];     // every thread (thread 0 uses it): a load under a branch is waited for at its end
+    const bool writer = block == blocks;
+    const int arrivals = blocks + 1;
+    const AdamMemoEntry* slot = &adam_memo[memo][zero];
+    const AdamMemoEntry e0 = slot[0], e1 = slot[1];
+    AdamSlot first;
+    const bool pre = vec && !writer && (long long)block * kBlock + threadIdx.x < (sg.n >> 2);
+    if (pre) {
+        const AdamVec av{sg.p, sg.g, sg.m, sg.v, sg.target, sg.g2, sg.g_part, sg.n_part, sg.part_stride,
+                         sg.g_part ? sg.part_elems : 0, sg.n >> 2, (long long)blocks * kBlock, nullptr, nullptr, 0, 0};
+        adam_slot_load(av, (long long)block * kBlock + threadIdx.x, first);
+    }
+    const uint64_t t = step + (writer ? 2 : 1);
+    // the entry of t's parity, used iff its whole tag is t's (never by the writer: it is there to call pow())
+    const AdamMemoEntry& e = (t & 1) ? e1 : e0;
+    const bool may_hit = !writer;
+    unsigned long long ticket = ~0ULL;
+    if (threadIdx.x == 0) {
+        // plain load (above), then the ticket once it has returned ("memory" clobber: the compiler keeps the order): the read
+        // of the step count cannot slip behind the ticket
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        // the ticket is taken as soon as this workgroup has READ the step count: the last of the segment's workgroups
+        // to do so knows every other one has read it too and may store t + 1 -- the returning atomic's round trip
+        // (~0.7 us) runs under the parameter loads: its value is looked at after them
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // the step count has returned (no agent-scope release: that
+        ticket = __hip_atomic_fetch_add((unsigned long long*)&sg.step_dev[1], 1ULL, __ATOMIC_RELAXED,   // is an L2 write-back)
+                                        __HIP_MEMORY_SCOPE_AGENT);
+        const bool hit = may_hit && adam_memo_hit(e, t, b1, b2);
+        const float om_b1t = hit ? e.om_b1t : adam_om_b1t(b1, t);
+        sh[0] = lr / om_b1t;
+        sh[7] = om_b1t;
+        sh[1] = e.bc2_sqrt;
+        sh[2] = __uint_as_float(uint32_t(step));
+        sh[4] = __uint_as_float(hit ? 1u : 0u);
+    } else if (threadIdx.x == 64) {
+        // the second bias correction on another wave: each double pow is a ~230-instruction dependent chain (~1 us) that the
+        // whole workgroup waits for at the barrier below -- side by side instead of one behind the other
+        const bool hit = may_hit && adam_memo_hit(e, t, b1, b2);
+        if (!hit) sh[5] = adam_bc2_sqrt(b2, t);
+        sh[3] = __uint_as_float(uint32_t(step));
+        sh[6] = __uint_as_float(hit ? 1u : 0u);
+    }
+    __syncthreads();
+    // only wave 0's read of the step count is ordered before this workgroup's ticket: a slow wave 1 may have read the count
+    // AFTER the segment's last workgroup stored t + 1 (and then looked at the memo entry this launch's writer fills).  Wave 0's
+    // view is the step's: its memo values where it found them; else wave 1's pow() if wave 1 called it on the same step count;
+    // else thread 0 redoes that correction (workgroup-uniform branch, never taken in practice)
+    float bc2_sqrt = sh[1];
+    if (__float_as_uint(sh[4]) == 0u) {
+        if (__float_as_uint(sh[6]) != 0u || __float_as_uint(sh[2]) != __float_as_uint(sh[3])) {
+            if (threadIdx.x == 0) sh[5] = adam_bc2_sqrt(b2, t);
+            __syncthreads();
+        }
+        bc2_sqrt = sh[5];
+    }
+    if (writer) {
+        if (threadIdx.x == 0) {
+            // plain vector stores; nothing of this launch reads them
+            uint4* dst = reinterpret_cast<uint4*>(&adam_memo[memo][t & 1]);
+            dst[0] = make_uint4(uint32_t(t), uint32_t(t >> 32), __float_as_uint(b1), __float_as_uint(b2));
+            dst[1] = make_uint4(__float_as_uint(sh[7]), __float_as_uint(bc2_sqrt), 0u, 0u);
+        }
+    } else {
+        adam_range(sg.n, sg.p, sg.g, sg.m, sg.v, sh[0], bc2_sqrt, b1, b2, eps, sg.target, sg.tau, sg.weight_decay, sg.g2,
+                   block, blocks, vec, sg.g_part, sg.n_part, sg.part_stride, sg.part_elems, first, vec, sg.w2p, sg.target_w2p,
+                   sg.w2_off, sg.w2_heads);
+    }
+    if (threadIdx.x == 0 && ticket == (unsigned long long)arrivals - 1) {
+        sg.step_dev[0] = step + 1;
+        sg.step_dev[1] = 0;
+    }
+}
+
 // solo launch: grid (workgroups of the largest segment, segments) -- blockIdx.y IS the segment, its block arrives in one batch
-// of scalar loads (the flat grid of the packed form walks first_block[] first: one more dependent round trip)
+// of scalar loads (the flat grid of the packed form walks first_block[] first: one more dependent round trip).  Workgroup
+// `blocks` of a segment with a memo slot is its writer (adam_seg_body_memo)
 __global__ __launch_bounds__(kBlock) void adam_multi_kernel(AdamSegs a, int n_seg, float lr, float b1, float b2,
                                                             float eps) {
-    __shared__ float sh[4];
+    __shared__ float sh[kAdamShared];
     const int k = blockIdx.y;
     rrl_adam_seg_t sg = a.seg[k];
-    const int vec = a.vec[k], blocks = a.first_block[k + 1] - a.first_block[k];
+    const int vec = a.vec[k], blocks = a.first_block[k + 1] - a.first_block[k], memo = a.memo[k];
+    asm volatile("" ::"s"(memo));                // ahead of the pointers' pins: the slot arrives in their batch, not in one behind it
     rrl_pack::to_global_all(sg.p, sg.g, sg.m, sg.v, sg.step_dev, sg.target, sg.g2, sg.g_part, sg.w2p, sg.target_w2p);
     asm volatile("" ::"s"(sg.n), "s"(sg.tau), "s"(sg.weight_decay), "s"(sg.n_part), "s"(sg.part_stride), "s"(sg.part_elems),
                  "s"(vec), "s"(blocks), "s"(sg.w2_off), "s"(sg.w2_heads));
-    if ((int)blockIdx.x >= blocks) return;
-    adam_seg_body(sg, vec != 0, lr, b1, b2, eps, blockIdx.x, blocks, sh);
+    if ((int)blockIdx.x >= blocks + (memo >= 0 ? 1 : 0)) return;
+    if (memo < 0) adam_seg_body(sg, vec != 0, lr, b1, b2, eps, blockIdx.x, blocks, sh);
+    else adam_seg_body_memo(sg, vec != 0, lr, b1, b2, eps, blockIdx.x, blocks, sh, memo);
 }
 
 // the dual variables of the comparison algorithms (rrl_dual_t): one thread per member, torch.optim.Adam's capturable step on
@@ -580,7 +707,7 @@ __device__ __forceinline__ void dual_body(rrl_dual_t d, float b1, float b2, floa
 // after the other (a handful of scalars)
 __global__ __launch_bounds__(kBlock) void adam_multi_dual_kernel(AdamSegs a, int n_seg, DualSet ds, float lr, float b1,
                                                                  float b2, float eps) {
-    __shared__ float sh[4];
+    __shared__ float sh[kAdamShared];
     const int k = blockIdx.y;
     if (k == n_seg) {
         if (blockIdx.x != 0 || threadIdx.x != 0) return;
@@ -590,12 +717,14 @@ __global__ __launch_bounds__(kBlock) void adam_multi_dual_kernel(AdamSegs a, int
         return;
     }
     rrl_adam_seg_t sg = a.seg[k];
-    const int vec = a.vec[k], blocks = a.first_block[k + 1] - a.first_block[k];
+    const int vec = a.vec[k], blocks = a.first_block[k + 1] - a.first_block[k], memo = a.memo[k];
+    asm volatile("" ::"s"(memo));                // ahead of the pointers' pins: the slot arrives in their batch, not in one behind it
     rrl_pack::to_global_all(sg.p, sg.g, sg.m, sg.v, sg.step_dev, sg.target, sg.g2, sg.g_part, sg.w2p, sg.target_w2p);
     asm volatile("" ::"s"(sg.n), "s"(sg.tau), "s"(sg.weight_decay), "s"(sg.n_part), "s"(sg.part_stride), "s"(sg.part_elems),
                  "s"(vec), "s"(blocks), "s"(sg.w2_off), "s"(sg.w2_heads));
-    if ((int)blockIdx.x >= blocks) return;
-    adam_seg_body(sg, vec != 0, lr, b1, b2, eps, blockIdx.x, blocks, sh);
+    if ((int)blockIdx.x >= blocks + (memo >= 0 ? 1 : 0)) return;
+    if (memo < 0) adam_seg_body(sg, vec != 0, lr, b1, b2, eps, blockIdx.x, blocks, sh);
+    else adam_seg_body_memo(sg, vec != 0, lr, b1, b2, eps, blockIdx.x, blocks, sh, memo);
 }
 
 // the same launch for S seeds (pack.hpp): grid (workgroups of the seeds' largest segments under the XCD-aware placement,
@@ -607,7 +736,7 @@ struct AdamPack {
     float lr, b1, b2, eps;
 };
 __global__ __launch_bounds__(kBlock) void adam_pack_kernel(const AdamPack* __restrict__ packs, rrl_pack::Idx ix) {
-    __shared__ float sh[4];
+    __shared__ float sh[kAdamShared];
     int s, local;
     asm volatile("" ::"s"(ix.sp), "s"(ix.p), "s"(ix.r), "s"(ix.S));
     if (!rrl_pack::locate_grid(ix, blockIdx.x, s, local)) return;
@@ -631,7 +760,7 @@ struct AdamDualPack {
     DualSet ds;
 };
 __global__ __launch_bounds__(kBlock) void adam_pack_dual_kernel(const AdamDualPack* __restrict__ packs, rrl_pack::Idx ix) {
-    __shared__ float sh[4];
+    __shared__ float sh[kAdamShared];
     int s, local;
     asm volatile("" ::"s"(ix.sp), "s"(ix.p), "s"(ix.r), "s"(ix.S));
     if (!rrl_pack::locate_grid(ix, blockIdx.x, s, local)) return;
@@ -856,7 +985,36 @@ static int build_adam_segs(int n_seg, const rrl_adam_seg_t* segs, AdamSegs& a) {
         a.first_block[k + 1] = a.first_block[k] + (grid_for(sg.n) < cap ? grid_for(sg.n) : cap);
     }
     for (int k = n_seg; k < RRL_ADAM_MAX_SEGS; ++k) a.first_block[k + 1] = a.first_block[n_seg];
+    for (int k = 0; k < RRL_ADAM_MAX_SEGS; ++k) a.memo[k] = -1;
     return RRL_OK;
+}
+
+// The solo launches' memo slots (adam_memo): the first kAdamMemoSlots distinct step_dev addresses of the process get one each,
+// for good -- no eviction, no reassignment, so whatever a captured launch carries stays that address's slot; later addresses
+// get none (-1: pow() as ever).  Two segments of one launch on one step counter get none either: their writers would fill
+// one entry.  RRL_ADAM_MEMO=0 (read at every call) switches the memo off.  Returns whether any segment got a slot.
+static bool adam_memo_slots(int n_seg, AdamSegs& a) {
+    static std::mutex mu;
+    static const void* owner[kAdamMemoSlots];
+    static int used = 0;
+    const char* env = std::getenv("RRL_ADAM_MEMO");
+    if (env && env[0] == '0' && env[1] == 0) return false;
+    bool any = false;
+    std::lock_guard<std::mutex> lock(mu);
+    for (int k = 0; k < n_seg; ++k) {
+        const void* key = a.seg[k].step_dev;
+        bool twice = false;
+        for (int j = 0; j < n_seg; ++j) twice |= j != k && a.seg[j].step_dev == key;
+        if (twice) continue;
+        int slot = int(std::find(owner, owner + used, key) - owner);
+        if (slot == used) {
+            if (used == kAdamMemoSlots) continue;
+            owner[used++] = key;
+        }
+        a.memo[k] = slot;
+        any = true;
+    }
+    return any;
 }
 
 // ---- W2 in MFMA fragment order (rrl_stack_t.W2p): pure permutation, one float4 per thread ----
@@ -886,6 +1044,7 @@ int rrl_adam_step_multi(int n_seg, const rrl_adam_seg_t* segs, float lr, float b
     if (rc != RRL_OK) return rc;
     int most = 1;
     for (int k = 0; k < n_seg; ++k) most = a.first_block[k + 1] - a.first_block[k] > most ? a.first_block[k + 1] - a.first_block[k] : most;
+    if (adam_memo_slots(n_seg, a)) ++most;       // room for the memo writer of the largest segment
     hipLaunchKernelGGL(adam_multi_kernel, dim3(most, n_seg), dim3(kBlock), 0, (hipStream_t)stream, a, n_seg,
                        lr, beta1, beta2, eps);
     return check_launch();
@@ -917,6 +1076,7 @@ int rrl_adam_step_multi_duals(int n_seg, const rrl_adam_seg_t* segs, int n_dual,
         const int rc = build_adam_segs(n_seg, segs, a);
         if (rc != RRL_OK) return rc;
         for (int k = 0; k < n_seg; ++k) most = std::max(most, a.first_block[k + 1] - a.first_block[k]);
+        if (adam_memo_slots(n_seg, a)) ++most;
     }
     hipLaunchKernelGGL(adam_multi_dual_kernel, dim3(most, n_seg + 1), dim3(kBlock), 0, (hipStream_t)stream, a, n_seg, ds,
                        lr, beta1, beta2, eps);
