@@ -894,8 +894,12 @@ int rrl_ens_train_epoch_big(const rrl_ens_t* m, int n_seg, const rrl_adam_seg_t*
  *                                          its tick is advanced by the last of them; n, T, env kind, weights, groups, seed, tick
  *                                          and traces may differ by seed)
  *   rrl_eval_rollout_maze_packed           rrl_eval_rollout_maze       (args[s], horizon[s]; the same mapping on the Maze kernel)
+ *   rrl_eval_rollout_qs_packed             rrl_eval_rollout_qs         (args[s]; the same mapping on the Q-sampling kernels; n, T,
+ *                                          k, env seed, tick, weights, box and traces may differ by seed, and the kind within
+ *                                          Navigation or the horizon within Maze; Navigation and Maze seeds in one call:
+ *                                          RRL_EINVAL)
  * Every seed's arguments are checked before anything is stored or launched (the stand-alone entry's codes); a NULL array:
- * RRL_EINVAL; S outside 1 .. 16: RRL_EINVAL, except from rrl_eval_rollout[_maze]_packed, which return RRL_ERANGE for it.
+ * RRL_EINVAL; S outside 1 .. 16: RRL_EINVAL, except from rrl_eval_rollout[_maze|_qs]_packed, which return RRL_ERANGE for it.
  * S == 1 is the stand-alone launch.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
@@ -1119,6 +1123,45 @@ int rrl_eval_rollout_maze(const rrl_eval_rollout_t* a, int horizon, void* stream
  * 1 .. 16: RRL_ERANGE; every seed is checked before anything is stored or launched; S == 1 is
  * rrl_eval_rollout_maze(args, horizon[0]). */
 int rrl_eval_rollout_maze_packed(int S, const rrl_eval_rollout_t* args, const int* horizon, void* stream);
+
+/* The same rollout for Q-sampling recovery (--use_recovery --Q_sampling_recovery: QRiskWrapper.select_action,
+ * recovery_rl/qrisk.py:214-225, inside get_test_rollout): in the place of a recovery policy, a row whose gate fired while
+ * alive executes the best of k uniform candidates -- rrl_qsample_act's three steps inside the rollout launch, on kernels of
+ * their own (Navigation 1 / 2 and Maze, by base.env_kind), so the kernels above keep their code.  Start, task policy, gate,
+ * transition, results, tick and the base's traces are those above; for a gated live row i at step j:
+ *   candidate  b = Philox (seed, row i k + c, RRL_STREAM_EVAL_QSAMPLE, tick + reset + j), c = 0 .. k - 1; u_0, u_1 = the
+ *              open-unit doubles of its low and high 64 bits; a_j = float(double(lo_j) + (double(hi_j) - double(lo_j)) u_j):
+ *              double arithmetic without contraction, rounded once (rrl_qsample_act's).  The draws are keyed by (env row,
+ *              step) alone: they do not depend on which other rows are gated or alive, nor on n.
+ *   score      z_h = head h of Q_risk on [float(pos_i) | a_c], q = max(sigmoid z_0, sigmoid z_1), NaN propagates: the 64-row
+ *              tile of rrl_qsample_act in passes of up to four row tiles -- the bits rrl_qsample_act gives for the same
+ *              obs and candidate
+ *   pick       argmin_c q: the lowest index wins ties and NaN counts as the smallest (torch.argmin); executed = a_pick
+ * A workgroup serves the gated live rows of its 16 one after another in ascending row order, so k up to 1024 fits its LDS
+ * (82.4 KB: one workgroup per CU).  Rows that are not gated, dead rows and rows >= n draw and score nothing, a tile with no
+ * gated live row in a step skips the phase, a workgroup without a live row leaves the step loop: none of this changes a bit
+ * of any output.  tr_real of a gated row holds the picked candidate; tr_eps is never written; tr_pick / tr_q are written for
+ * gated live rows only.  The time follows the gated share: with every row gated on every step at k = 1000 and T = 101 a
+ * workgroup runs 16 rows x 16 passes x 2 heads per step, about 110 TFLOP for 4096 envs -- on the order of a second, the
+ * FLOPs the module path spends on every evaluation whatever the gate says.
+ * Checks before any launch, without a device: everything rrl_eval_rollout (rrl_eval_rollout_maze for RRL_ENV_MAZE) checks
+ * on base, with the same codes; NULL lo or hi, no Q_risk group, any pointer of the recovery group given: RRL_EINVAL; k outside
+ * 1..1024, n k >= 2^32, a Maze horizon outside 1 .. 2^30: RRL_ERANGE (an invalid field wins). */
+enum { RRL_STREAM_EVAL_QSAMPLE = 13 };   /* Q-sampling candidates of the evaluation rollout */
+typedef struct {
+    rrl_eval_rollout_t base;   /* recovery group (rW1 ..) must be all NULL; Q_risk group required */
+    int k;                     /* candidates per gated row, 1..1024 (the reference: 1000) */
+    int horizon;               /* Maze only (1 .. 2^30); ignored for Navigation */
+    const float *lo, *hi;      /* [2] action box on the device */
+    int32_t* tr_pick;          /* nullable trace [T, n]: the pick of a gated live row, else untouched */
+    float*   tr_q;             /* nullable trace [T, n]: its q, else untouched */
+} rrl_eval_rollout_qs_t;
+int rrl_eval_rollout_qs(const rrl_eval_rollout_qs_t* a, void* stream);
+/* ... and for S seeds side by side (the packed-launch table above): all Navigation (either kind) or all Maze (any horizons),
+ * a mix is RRL_EINVAL; each seed's outputs, traces and tick are the bits of its stand-alone launch.  Every seed is checked as
+ * the stand-alone entry checks it, all before anything is stored or launched (RRL_EINVAL of any seed wins); args == NULL:
+ * RRL_EINVAL; S outside 1 .. 16: RRL_ERANGE; S == 1 is rrl_eval_rollout_qs(args). */
+int rrl_eval_rollout_qs_packed(int S, const rrl_eval_rollout_qs_t* args, void* stream);
 
 #ifdef __cplusplus
 }

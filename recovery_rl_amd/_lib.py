@@ -54,6 +54,7 @@ EXPORTS = [
     "rrl_sqrl_scratch_floats", "rrl_sqrl_act", "rrl_sqrl_act_packed",
     "rrl_qsample_scratch_floats", "rrl_qsample_act", "rrl_qsample_act_gated", "rrl_qsample_act_packed",
     "rrl_eval_rollout", "rrl_eval_rollout_packed", "rrl_eval_rollout_maze", "rrl_eval_rollout_maze_packed",
+    "rrl_eval_rollout_qs", "rrl_eval_rollout_qs_packed",
 ]
 
 class RRLError(RuntimeError):
@@ -328,6 +329,14 @@ class rrl_eval_rollout_t(C.Structure):
                                   "tr_z", "tr_eps", "tr_reward", "tr_flags")]
 
 
+STREAM_EVAL_QSAMPLE = 13
+
+
+class rrl_eval_rollout_qs_t(C.Structure):
+    _fields_ = [("base", rrl_eval_rollout_t), ("k", C.c_int), ("horizon", C.c_int)] + [
+        (n, C.c_void_p) for n in ("lo", "hi", "tr_pick", "tr_q")]
+
+
 _lib = None
 
 
@@ -418,6 +427,8 @@ def _declare(lib):
         "rrl_eval_rollout_packed": (ci, [ci, C.POINTER(rrl_eval_rollout_t), vp]),
         "rrl_eval_rollout_maze": (ci, [C.POINTER(rrl_eval_rollout_t), ci, vp]),
         "rrl_eval_rollout_maze_packed": (ci, [ci, C.POINTER(rrl_eval_rollout_t), C.POINTER(ci), vp]),
+        "rrl_eval_rollout_qs": (ci, [C.POINTER(rrl_eval_rollout_qs_t), vp]),
+        "rrl_eval_rollout_qs_packed": (ci, [ci, C.POINTER(rrl_eval_rollout_qs_t), vp]),
         "rrl_episode_log_append": (ci, [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(rrl_episode_log_t), vp]),
     }
     for name, (res, args) in sig.items():

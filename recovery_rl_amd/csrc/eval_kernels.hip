@@ -21,6 +21,17 @@
 // for its 16 rows, DIN < 4 inputs and NOUT outputs.  The body is generic over the env (a trait with reset and step, as
 // step_push.hpp's): NavRoll restates nav_kernels.hip's NavEnv, MazeRoll is maze_device.hpp's transition behind kernels of
 // its own (rrl_eval_rollout_maze[_packed]), so the Navigation kernels carry no Maze branch.
+//
+// Q-sampling recovery (rrl_eval_rollout_qs[_packed], four more kernels: Navigation / Maze x solo / packed) is the same body
+// with the QsOn trait: a row whose gate fired while alive draws k uniform candidates (stream RRL_STREAM_EVAL_QSAMPLE, keyed
+// by (env row, step) alone), scores them on the 64-row twin-head tile of mfma_tile.hpp (q_phase / twin_q: the bits of
+// rrl_qsample_act) in passes of up to four row tiles, and executes the argmin.  The gated rows of a tile are served one
+// after another in ascending row order (a workgroup-uniform loop over the gate's ballot), so k up to 1024 stays within one
+// workgroup's LDS: the 64-row tile prefix (70.0 KB; the 16-row rollout regions lie inside its activation region, every
+// hand-over behind a barrier) + candidates and their q (12 KB) + obs / results / mask (0.4 KB) = 82.4 KB, one workgroup per
+// CU of the 160 KB -- the launch's shape anyway (4096 envs = 256 workgroups).  A tile with no gated live row skips the
+// phase; rows that are not gated, dead or >= n draw and score nothing.  The NoQs instantiations are the four kernels above,
+// instruction for instruction (profiles/eval_rollout_qsample_fingerprint.txt).
 #include "maze_device.hpp"
 #include "mfma_tile.hpp"
 #include "pack.hpp"
@@ -53,6 +64,19 @@ constexpr int kOffPart = kOffXs + kRows * 4;                 // [2 outputs][8 wa
 constexpr int kLdsFloats = kOffPart + 2 * kWaves * kRows;
 constexpr int kLdsBytes = kLdsFloats * 4;                    // 17.5 KB
 
+// Q-sampling form: the 64-row tile's prefix (act / xs / qpart of mfma_tile.hpp) overlays the regions above -- they are dead
+// between the gate's fold and the next step's xs, which is where the candidate phase runs -- and its own regions follow
+constexpr uint32_t kStreamEvalQs = RRL_STREAM_EVAL_QSAMPLE;
+constexpr int kMaxK = 1024;                                  // candidates per gated row
+constexpr int kOffQsCand = rrl_tile::kOffOwn;                // [1024][2] candidates of the row being served
+constexpr int kOffQsQ = kOffQsCand + kMaxK * 2;              // [1024] max(sigmoid z0, sigmoid z1)
+constexpr int kOffQsObs = kOffQsQ + kMaxK;                   // [16][2] float(pos) of the tile's rows
+constexpr int kOffQsRes = kOffQsObs + kRows * 2;             // [16][4] pick (int bits), its q, that candidate
+constexpr int kOffQsMask = kOffQsRes + kRows * 4;            // [1] the gate of the tile's rows, one bit each (int bits)
+constexpr int kQsLdsFloats = kOffQsMask + 4;
+constexpr int kQsLdsBytes = kQsLdsFloats * 4;                // 82.4 KB: one workgroup per CU
+static_assert(kLdsFloats <= rrl_tile::kOffXs, "the rollout's regions lie inside the 64-row tile's activation region");
+
 struct Net {
     const float *W1, *b1, *W2p, *b2, *W3, *b3;
 };
@@ -76,6 +100,21 @@ struct EvArgs {
     double* tr_pos;
     float *tr_task, *tr_real, *tr_z, *tr_eps, *tr_reward;
     uint8_t* tr_flags;
+};
+
+// The Q-sampling group of a launch (rrl_eval_rollout_qs_t's own fields), beside EvArgs so that the kernels without it keep
+// their argument block
+struct QsArgs {
+    int k;
+    const float *lo, *hi;
+    int32_t* tr_pick;
+    float* tr_q;
+};
+struct NoQs {
+    static constexpr bool on = false;
+};
+struct QsOn : QsArgs {
+    static constexpr bool on = true;
 };
 
 // One 2-hidden-layer stack (head `head` of w) on the row tile in xs: inputs = the first DIN columns of xs, outputs = the
@@ -203,10 +242,98 @@ struct MazeRoll {
     }
 };
 
+// One pass of the candidate phase: candidates [base, base + 16 MR) of the k in LDS through the twin heads on [obs | candidate];
+// q of the live ones into LDS (score_pass of qsample_kernels.hip on this file's carve-up)
+template <int MR>
+__device__ __forceinline__ void qs_pass(float* lds, const Net& q, int k, int base, float ox, float oy, int tid, int wave,
+                                        int lane) {
+    if (tid < rrl_tile::kRows) {
+        const int r = base + tid;
+        f32x4 x = {0.f, 0.f, 0.f, 0.f};           // rows past k: finite inputs, results never read
+        if (r < k) x = f32x4{ox, oy, lds[kOffQsCand + 2 * r], lds[kOffQsCand + 2 * r + 1]};
+        *reinterpret_cast<f32x4*>(lds + rrl_tile::kOffXs + tid * 4) = x;
+    }
+    __syncthreads();
+    rrl_tile::q_phase<MR>(lds, q, wave, lane);
+    if (tid < rrl_tile::kRows && base + tid < k) lds[kOffQsQ + base + tid] = rrl_tile::twin_q(lds, q, tid).q;
+    // xs and qpart are rewritten only behind the next pass's barriers
+}
+
+// The candidate phase of tile row g (env `grow`) at step counter ctr: k draws, their scores, the argmin -> res[g] in LDS.
+// Every thread of the workgroup takes part; starts behind a barrier and ends with one.
+__device__ __forceinline__ void qs_row(float* lds, const EvArgs& a, const QsArgs& s, int g, long long grow, uint64_t ctr,
+                                       int tid, int wave, int lane) {
+    const int k = s.k;
+    // ---- candidates: a_j = float(lo_j + (hi_j - lo_j) u_j) in double, u = the open-unit pair of the row's 128 bits ----
+#pragma unroll 1
+    for (int c = tid; c < k; c += kThreads) {
+        const rrl::Bits128 bits = rrl::philox_at(a.seed, uint32_t(grow * k + c), kStreamEvalQs, ctr);
+        const double u[2] = {rrl::unit_open(bits.lo), rrl::unit_open(bits.hi)};
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const double l = double(s.lo[j]), h = double(s.hi[j]);
+            lds[kOffQsCand + 2 * c + j] = float(l + (h - l) * u[j]);
+        }
+    }
+    const float ox = lds[kOffQsObs + 2 * g], oy = lds[kOffQsObs + 2 * g + 1];
+    __syncthreads();
+
+    // ---- scores: row tiles of 16, at most four per pass ----
+    const int nt = (k + 15) >> 4;
+#pragma unroll 1
+    for (int base = 0; base < k; base += rrl_tile::kRows) {
+        const int mr = nt - (base >> 4);
+        switch (mr) {
+            case 1: qs_pass<1>(lds, a.q, k, base, ox, oy, tid, wave, lane); break;
+            case 2: qs_pass<2>(lds, a.q, k, base, ox, oy, tid, wave, lane); break;
+            case 3: qs_pass<3>(lds, a.q, k, base, ox, oy, tid, wave, lane); break;
+            default: qs_pass<4>(lds, a.q, k, base, ox, oy, tid, wave, lane); break;
+        }
+    }
+    __syncthreads();                              // q of every candidate is in LDS
+
+    // ---- argmin, lowest index on ties; NaN counts as the smallest (torch.argmin) ----
+    if (wave == 0) {
+        float best = __builtin_inff();
+        int bidx = kMaxK;
+#pragma unroll 1
+        for (int r = lane; r < k; r += 64) {      // ascending r: strict < keeps the lower index
+            const float qv = lds[kOffQsQ + r];
+            const float key = qv != qv ? -__builtin_inff() : qv;
+            if (key < best) {
+                best = key;
+                bidx = r;
+            }
+        }
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const float ob = __shfl_xor(best, off, 64);
+            const int oi = __shfl_xor(bidx, off, 64);
+            if (ob < best || (ob == best && oi < bidx)) {
+                best = ob;
+                bidx = oi;
+            }
+        }
+        if (lane == 0) {
+            bidx = bidx < k ? bidx : 0;           // every q = +inf cannot happen (q <= 1); keeps the reads below in range
+            float* res = lds + kOffQsRes + 4 * g;
+            res[0] = __int_as_float(bidx);
+            res[1] = lds[kOffQsQ + bidx];
+            res[2] = lds[kOffQsCand + 2 * bidx];
+            res[3] = lds[kOffQsCand + 2 * bidx + 1];
+        }
+    }
+    __syncthreads();                              // res[g] is out; candidates and q are free for the next gated row
+}
+
 // Workgroup b of the argument block's own grid: envs [16 b, 16 (b + 1)) through the whole rollout.  Thread tid < 16
-// owns env 16 b + tid: state and results in its registers, written once at the end.
-template <class Env>
-__device__ __forceinline__ void rollout_tile(const EvArgs& a, const Env& env, unsigned b, float* lds) {
+// owns env 16 b + tid: state and results in its registers, written once at the end.  Qs = QsOn: a gated live row executes
+// the argmin of its k candidates (qs_row) in the place of a recovery policy's action.  The body declares no local for that
+// form (the pick is read back from LDS where it is traced): with two more locals the NoQs instantiations kept their
+// instruction counts but not their register numbering.
+template <class Env, class Qs = NoQs>
+__device__ __forceinline__ void rollout_tile(const EvArgs& a, const Env& env, unsigned b, float* lds,
+                                             const QsArgs* qsp = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int R = kRows;
@@ -272,6 +399,27 @@ __device__ __forceinline__ void rollout_tile(const EvArgs& a, const Env& env, un
                 r1 = tanhf(fold_part(part, 1, tid, a.r.b3[1])) * a.rscale[1] + a.rbias[1] +
                      expf(fmaxf(a.rlog_std[1], a.min_log_std)) * e1;
             }
+            if constexpr (Qs::on) {
+                // ---- Q-sampling: the gated live rows of the tile, one after another in ascending row order ----
+                if (tid < R) {
+                    lds[kOffQsObs + 2 * tid] = float(x);
+                    lds[kOffQsObs + 2 * tid + 1] = float(y);
+                }
+                const unsigned long long fired = __ballot(rec);      // wave 0: bit t = row t; rec is false elsewhere
+                if (tid == 0) lds[kOffQsMask] = __int_as_float(int(fired));
+                __syncthreads();                              // the gate's fold is behind this barrier: act / xs / part are free
+                unsigned m = __builtin_amdgcn_readfirstlane(__float_as_int(lds[kOffQsMask]));
+#pragma unroll 1
+                while (m) {                                   // workgroup-uniform; no gated row: the phase is skipped
+                    const int g = __builtin_ctz(m);
+                    m &= m - 1;
+                    qs_row(lds, a, *qsp, g, (long long)b * R + g, ctr, tid, wave, lane);
+                }
+                if (rec) {
+                    r0 = lds[kOffQsRes + 4 * tid + 2];
+                    r1 = lds[kOffQsRes + 4 * tid + 3];
+                }
+            }
         }
 
         // ---- transition ----
@@ -299,6 +447,11 @@ __device__ __forceinline__ void rollout_tile(const EvArgs& a, const Env& env, un
             if (a.tr_eps && has_r) {
                 a.tr_eps[2 * o] = e0;
                 a.tr_eps[2 * o + 1] = e1;
+            }
+            if constexpr (Qs::on) {
+                // res[tid] of this step stands until the next step's candidate phase, behind that step's barriers
+                if (rec && qsp->tr_pick) qsp->tr_pick[o] = __float_as_int(lds[kOffQsRes + 4 * tid]);
+                if (rec && qsp->tr_q) qsp->tr_q[o] = lds[kOffQsRes + 4 * tid + 1];
             }
             if (a.tr_reward) a.tr_reward[o] = rew;
             if (a.tr_flags) a.tr_flags[o] = uint8_t(1 | (int(dn) << 1) | (int(cons) << 2) | (int(sc) << 3) | (int(rec) << 4));
@@ -370,6 +523,52 @@ void eval_rollout_maze_pack_kernel(const MazeBlock* __restrict__ blocks, rrl_pac
     const int horizon = blocks[s].horizon;
     globalize(a);
     rollout_tile(a, MazeRoll{horizon}, unsigned(local), lds);
+}
+
+// The Q-sampling kernels: the same body with QsOn, on the larger LDS carve-up.  One argument block for both env kinds (the
+// Maze horizon is its tail, unused by Navigation); a packed plan holds S of them.  82.4 KB of LDS put one workgroup = two
+// waves per SIMD on a CU, so the kernels ask for that occupancy and its registers (at four waves' budget the rollout state
+// beside the four-row-tile accumulators spilled).
+struct QsBlock {
+    EvArgs a;
+    QsOn q;
+    int horizon;
+};
+
+__device__ __forceinline__ void globalize(QsOn& q) { rrl_pack::to_global_all(q.lo, q.hi, q.tr_pick, q.tr_q); }
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void eval_rollout_qs_kernel(const QsBlock k) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    rollout_tile<NavRoll, QsOn>(k.a, NavRoll{}, blockIdx.x, lds, &k.q);
+}
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void eval_rollout_qs_maze_kernel(const QsBlock k) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    rollout_tile<MazeRoll, QsOn>(k.a, MazeRoll{k.horizon}, blockIdx.x, lds, &k.q);
+}
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void eval_rollout_qs_pack_kernel(const QsBlock* __restrict__ blocks, rrl_pack::Idx ix) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int s, local;
+    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
+    QsBlock k = blocks[s];
+    globalize(k.a);
+    globalize(k.q);
+    rollout_tile<NavRoll, QsOn>(k.a, NavRoll{}, unsigned(local), lds, &k.q);
+}
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void eval_rollout_qs_maze_pack_kernel(const QsBlock* __restrict__ blocks, rrl_pack::Idx ix) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int s, local;
+    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
+    QsBlock k = blocks[s];
+    globalize(k.a);
+    globalize(k.q);
+    rollout_tile<MazeRoll, QsOn>(k.a, MazeRoll{k.horizon}, unsigned(local), lds, &k.q);
 }
 
 template <size_t N>
@@ -457,9 +656,109 @@ int launch_maze_solo(const rrl_eval_rollout_t* p, int horizon, void* stream) {
     return check_launch();
 }
 
+bool is_maze(const rrl_eval_rollout_qs_t* p) { return p && p->base.env_kind == RRL_ENV_MAZE; }
+
+// the checks of a Q-sampling descriptor, before any launch (rrl_hip.h): the base's for its env kind, then its own fields;
+// an invalid field wins over a size out of range
+int check_qs(const rrl_eval_rollout_qs_t* p) {
+    if (!p) return RRL_EINVAL;
+    const rrl_eval_rollout_t* e = &p->base;
+    const int rc = check_desc(e, is_maze(p));
+    if (rc == RRL_EINVAL) return rc;
+    const void* const rg[] = {e->rW1, e->rb1, e->rW2p, e->rb2, e->rW3, e->rb3, e->rscale, e->rbias, e->rlog_std};
+    if (!p->lo || !p->hi || !e->qW1 || given(rg) != 0) return RRL_EINVAL;   // (a Q_risk group given in part: check_desc)
+    if (rc != RRL_OK) return rc;
+    if (p->k < 1 || p->k > kMaxK || (long long)e->n * p->k >= (1LL << 32)) return RRL_ERANGE;
+    if (is_maze(p) && (p->horizon < 1 || p->horizon > kMaxHorizon)) return RRL_ERANGE;
+    return RRL_OK;
+}
+
+QsBlock qs_block_of(const rrl_eval_rollout_qs_t* p) {
+    QsBlock b{};
+    b.a = block_of(&p->base);
+    b.q.k = p->k;
+    b.q.lo = p->lo;
+    b.q.hi = p->hi;
+    b.q.tr_pick = p->tr_pick;
+    b.q.tr_q = p->tr_q;
+    b.horizon = is_maze(p) ? p->horizon : 0;
+    return b;
+}
+
+int launch_qs_solo(const rrl_eval_rollout_qs_t* p, void* stream) {
+    const int rc = check_qs(p);
+    if (rc != RRL_OK) return rc;
+    const QsBlock b = qs_block_of(p);
+    static bool nav_set = false, maze_set = false;
+    if (is_maze(p)) {
+        const int rl = grant_lds(eval_rollout_qs_maze_kernel, kQsLdsBytes, maze_set);
+        if (rl != RRL_OK) return rl;
+        hipLaunchKernelGGL(eval_rollout_qs_maze_kernel, dim3((unsigned)b.a.blocks), dim3(kThreads), kQsLdsBytes,
+                           (hipStream_t)stream, b);
+    } else {
+        const int rl = grant_lds(eval_rollout_qs_kernel, kQsLdsBytes, nav_set);
+        if (rl != RRL_OK) return rl;
+        hipLaunchKernelGGL(eval_rollout_qs_kernel, dim3((unsigned)b.a.blocks), dim3(kThreads), kQsLdsBytes, (hipStream_t)stream,
+                           b);
+    }
+    return check_launch();
+}
+
 }  // namespace
 
 extern "C" {
+
+int rrl_eval_rollout_qs(const rrl_eval_rollout_qs_t* p, void* stream) { return launch_qs_solo(p, stream); }
+
+int rrl_eval_rollout_qs_packed(int S, const rrl_eval_rollout_qs_t* args, void* stream) {
+    if (!args) return RRL_EINVAL;
+    if (S <= 0 || S > rrl_pack::kMaxSeeds) return RRL_ERANGE;
+    int worst = RRL_OK;
+    for (int s = 0; s < S; ++s) {               // every seed is checked before anything is stored or launched
+        const int rc = check_qs(args + s);
+        if (rc == RRL_EINVAL) return rc;        // an invalid field wins over a size out of range, whichever seed has it
+        if (rc != RRL_OK) worst = rc;
+    }
+    const bool maze = is_maze(args);
+    for (int s = 1; s < S; ++s)
+        if (is_maze(args + s) != maze) return RRL_EINVAL;       // one env family per launch: the kernels differ
+    if (worst != RRL_OK) return worst;
+    if (S == 1) return launch_qs_solo(args, stream);
+    rrl_pack::Key key;
+    key.pod(15);
+    key.pod(S);
+    key.add(args, sizeof(rrl_eval_rollout_qs_t) * S);
+    hipStream_t st = (hipStream_t)stream;
+    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    if (!plan) {
+        std::vector<QsBlock> blocks(S);
+        int count[rrl_pack::kMaxSeeds];
+        for (int s = 0; s < S; ++s) {
+            blocks[s] = qs_block_of(args + s);
+            count[s] = blocks[s].a.blocks;
+        }
+        rrl_pack::Idx ix;
+        rrl_pack::ranges(ix, S, count);
+        const int grid = rrl_pack::finish(ix);
+        plan = rrl_pack::store(key, blocks.data(), sizeof(QsBlock) * S, st);
+        if (!plan) return rrl_pack::store_error();
+        plan->grid = grid;
+        plan->ix = ix;
+    }
+    static bool nav_set = false, maze_set = false;
+    if (maze) {
+        const int rl = grant_lds(eval_rollout_qs_maze_pack_kernel, kQsLdsBytes, maze_set);
+        if (rl != RRL_OK) return rl;
+        hipLaunchKernelGGL(eval_rollout_qs_maze_pack_kernel, dim3((unsigned)plan->grid), dim3(kThreads), kQsLdsBytes, st,
+                           (const QsBlock*)plan->dev, plan->ix);
+    } else {
+        const int rl = grant_lds(eval_rollout_qs_pack_kernel, kQsLdsBytes, nav_set);
+        if (rl != RRL_OK) return rl;
+        hipLaunchKernelGGL(eval_rollout_qs_pack_kernel, dim3((unsigned)plan->grid), dim3(kThreads), kQsLdsBytes, st,
+                           (const QsBlock*)plan->dev, plan->ix);
+    }
+    return check_launch();
+}
 
 int rrl_eval_rollout(const rrl_eval_rollout_t* p, void* stream) { return launch_solo(p, stream); }
 

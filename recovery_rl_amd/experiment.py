@@ -1078,7 +1078,8 @@ class Experiment:
         rollout = self.eval_rollout()
         if rollout is not None:
             # RRL_FAST_EVAL=1: reset, the horizon + 1 steps and the per-env results in one launch (rrl_eval_rollout; Maze,
-            # with RRL_FAST_EVAL_MAZE=1 as well: rrl_eval_rollout_maze, whose rows the env's horizon ends one step earlier)
+            # with RRL_FAST_EVAL_MAZE=1 as well: rrl_eval_rollout_maze, whose rows the env's horizon ends one step earlier;
+            # Q-sampling recovery, with RRL_FAST_EVAL_QSAMPLE=1 as well: rrl_eval_rollout_qs, candidates drawn in the launch)
             rollout.launch(env._max_episode_steps + 1)
             return self._eval_result(rollout.stats(label))
         self.vector_rules.pop("evaluation", None)          # the rule records the path the LAST evaluation took
@@ -1110,12 +1111,14 @@ class Experiment:
     def eval_rollout(self):
         """The EvalRollout of this experiment's evaluation env when evaluation runs on the kernel
         (fast_update.eval_rollout_path), else None: the module code below."""
-        from .fast_update import EvalRollout, eval_rollout_path
+        from .fast_update import EvalRollout, eval_qsample_line, eval_rollout_path
         cfg = self.exp_cfg
         if eval_rollout_path(cfg) != "hip" or getattr(self.agent, "fast", None) is None:
             return None
         if getattr(self, "_eval_rollout", None) is None:
-            self._eval_rollout = EvalRollout(self.agent.fast, self.eval_env(), cfg.eps_safe, cfg.use_recovery)
+            # (eval_rollout_path said "hip" for the Q-sampling line: RRL_FAST_EVAL_QSAMPLE=1 -> rrl_eval_rollout_qs)
+            self._eval_rollout = EvalRollout(self.agent.fast, self.eval_env(), cfg.eps_safe, cfg.use_recovery,
+                                             qsample=eval_qsample_line(cfg))
         self.vector_rules["evaluation"] = "hip"
         return self._eval_rollout
 

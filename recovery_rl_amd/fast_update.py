@@ -1223,39 +1223,63 @@ def fast_eval_maze_enabled():
     return os.environ.get("RRL_FAST_EVAL_MAZE", "0") == "1"
 
 
+def fast_eval_qsample_enabled():
+    """RRL_FAST_EVAL_QSAMPLE=1, on top of RRL_FAST_EVAL=1: --Q_sampling_recovery evaluates on rrl_eval_rollout_qs (opt-in;
+    eval_rollout_path)."""
+    return os.environ.get("RRL_FAST_EVAL_QSAMPLE", "0") == "1"
+
+
+def eval_qsample_line(cfg):
+    """The configuration whose evaluation draws Q-sampling candidates: --use_recovery --Q_sampling_recovery without
+    --MF_recovery (model-free wins in the module code) and without --use_constraint_sampling."""
+    return (bool(cfg.use_recovery) and bool(getattr(cfg, "Q_sampling_recovery", False)) and not cfg.MF_recovery
+            and not cfg.use_constraint_sampling)
+
+
 def eval_rollout_path(cfg):
     """Where Experiment.get_test_rollout_vectorized runs: "hip" (EvalRollout: one launch) under RRL_FAST_EVAL=1 on the fused
     path at hidden width 256, Navigation 1 / 2 -- or Maze with RRL_FAST_EVAL_MAZE=1 as well --, the lock-step loop, without
-    a recovery policy or with the model-free one; else "modules" (the loop's act() on the torch modules and the eager env),
-    which Q-sampling, SQRL, model-based recovery and every other configuration keep."""
+    a recovery policy, with the model-free one, or -- with RRL_FAST_EVAL_QSAMPLE=1 as well, whatever RRL_FAST_QSAMPLE says --
+    with Q-sampling recovery; else "modules" (the loop's act() on the torch modules and the eager env), which SQRL, model-based
+    recovery and every other configuration keep."""
     envs = ("navigation1", "navigation2") + (("maze",) if fast_eval_maze_enabled() else ())
     hip = (fast_eval_enabled() and fast_path_supported(cfg) and not getattr(cfg, "no_fast_path", False)
            and int(cfg.hidden_size) == 256 and cfg.env_name in envs
            and int(getattr(cfg, "num_envs", 1)) > 1 and not cfg.use_constraint_sampling
-           and (not cfg.use_recovery or bool(cfg.MF_recovery)))
+           and (not cfg.use_recovery or bool(cfg.MF_recovery) or (fast_eval_qsample_enabled() and eval_qsample_line(cfg))))
     return "hip" if hip else "modules"
 
 
 class EvalRollout:
     """One evaluation (Experiment.get_test_rollout_vectorized) of `env`'s envs as one rrl_eval_rollout launch on the live flat
     weights of `fast`.  Owns the per-env result buffers and its OWN fragment-order copies of the three W2 matrices, re-made
-    right before each launch: it depends neither on RRL_W2_FRAG nor on how many seeds a packed run keeps those copies for."""
+    right before each launch: it depends neither on RRL_W2_FRAG nor on how many seeds a packed run keeps those copies for.
+    qsample=True: the Q-sampling form (rrl_eval_rollout_qs) -- no recovery policy; a gated row executes the best of QSAMPLE_K
+    uniform candidates from the action box FastActor.qsample_box takes, drawn inside the launch."""
 
-    def __init__(self, fast, env, eps_safe, use_recovery):
+    QSAMPLE_K = 1000                   # QRiskWrapper.select_action's candidate count
+
+    def __init__(self, fast, env, eps_safe, use_recovery, qsample=False):
         self.f, self.env, self.n = fast, env, env.num_envs
-        self.eps_safe, self.use_recovery = float(eps_safe), bool(use_recovery)
+        self.eps_safe, self.use_recovery, self.qsample = float(eps_safe), bool(use_recovery), bool(qsample)
         dev = fast.dev
         self.ret = torch.zeros(self.n, dtype=torch.float32, device=dev)
         self.success = torch.zeros(self.n, dtype=torch.uint8, device=dev)
         self.violation = torch.zeros(self.n, dtype=torch.uint8, device=dev)
         self.steps = torch.zeros(self.n, dtype=torch.int32, device=dev)
-        self.nets = [fast.policy] + ([fast.qrisk, fast.recpolicy] if self.use_recovery else [])
+        self.nets = [fast.policy] + ([fast.qrisk] + ([] if self.qsample else [fast.recpolicy]) if self.use_recovery else [])
+        if self.qsample:
+            ac = fast.qr.ac_space
+            self.box = tuple(torch.as_tensor(b, dtype=torch.float32, device=dev).contiguous() for b in (ac.low, ac.high))
         self.w2p = [torch.empty(net.p["W2"].numel(), dtype=torch.float32, device=dev) for net in self.nets]
         self.args = None
 
     def desc(self, T, reset=True, pos=None, trace=None):
-        """The launch's rrl_eval_rollout_t on the live flat buffers and the env's seed and device tick, the W2 copies made
-        current.  `pos` [n, 2] f64 with reset=False: the start states; `trace` = {name: tensor} asks for trace buffers."""
+        """The launch's rrl_eval_rollout_t (the Q-sampling form: rrl_eval_rollout_qs_t around it) on the live flat buffers and
+        the env's seed and device tick, the W2 copies made current.  `pos` [n, 2] f64 with reset=False: the start states;
+        `trace` = {name: tensor} asks for trace buffers."""
+        trace = dict(trace or {})
+        own = {name: trace.pop(name) for name in ("tr_pick", "tr_q") if name in trace}
         f, p = self.f, _lib.ptr
         for net, w2p in zip(self.nets, self.w2p):
             W2 = net.p["W2"]
@@ -1269,10 +1293,15 @@ class EvalRollout:
                                     success=p(self.success), violation=p(self.violation), steps=p(self.steps),
                                     **{name: p(t) for name, t in (trace or {}).items()})
         if self.use_recovery:
-            Q, R = f.qrisk.p, f.recpolicy.p
+            Q = f.qrisk.p
             a.qW1, a.qb1, a.qW2p, a.qb2, a.qW3, a.qb3 = (p(Q["W1"]), p(Q["b1"]), p(self.w2p[1]), p(Q["b2"]), p(Q["W3"]),
                                                          p(Q["b3"]))
             a.eps_safe = self.eps_safe
+        if self.qsample:
+            a = _lib.rrl_eval_rollout_qs_t(base=a, k=self.QSAMPLE_K, horizon=int(self.env.horizon) if self.maze else 0,
+                                           lo=p(self.box[0]), hi=p(self.box[1]), **{name: p(t) for name, t in own.items()})
+        elif self.use_recovery:
+            R = f.recpolicy.p
             a.rW1, a.rb1, a.rW2p, a.rb2, a.rW3, a.rb3 = (p(R["W1"]), p(R["b1"]), p(self.w2p[2]), p(R["b2"]), p(R["W3"]),
                                                          p(R["b3"]))
             a.rscale, a.rbias, a.rlog_std = p(f.rscale), p(f.rbias), p(R["log_std"])
@@ -1286,6 +1315,9 @@ class EvalRollout:
 
     def launch(self, T, **kw):
         a = self.desc(T, **kw)
+        if self.qsample:   # one entry for both env families (the Maze horizon rides in the descriptor)
+            _lib.check(self.f.lib.rrl_eval_rollout_qs(C.byref(a), _lib.current_stream()), "rrl_eval_rollout_qs")
+            return
         if self.maze:      # the env's own horizon ends a row: a launch argument of the Maze entry (T stays horizon + 1)
             _lib.check(self.f.lib.rrl_eval_rollout_maze(C.byref(a), int(self.env.horizon), _lib.current_stream()),
                        "rrl_eval_rollout_maze")
@@ -1301,7 +1333,13 @@ class EvalRollout:
 
 def eval_rollouts_packed(rollouts, T):
     """The evaluations of several seeds (EvalRollout each) as ONE rrl_eval_rollout_packed launch (one env per packed run:
-    rrl_eval_rollout_maze_packed with every seed's env horizon when that env is Maze)."""
+    rrl_eval_rollout_maze_packed with every seed's env horizon when that env is Maze; rrl_eval_rollout_qs_packed for the
+    Q-sampling form)."""
+    if rollouts[0].qsample:
+        args = (_lib.rrl_eval_rollout_qs_t * len(rollouts))(*[r.desc(T) for r in rollouts])
+        _lib.check(_lib.load().rrl_eval_rollout_qs_packed(len(rollouts), args, _lib.current_stream()),
+                   "rrl_eval_rollout_qs_packed")
+        return
     args = (_lib.rrl_eval_rollout_t * len(rollouts))(*[r.desc(T) for r in rollouts])
     if rollouts[0].maze:
         horizon = (C.c_int * len(rollouts))(*[int(r.env.horizon) for r in rollouts])
