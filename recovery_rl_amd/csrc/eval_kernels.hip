@@ -685,22 +685,66 @@ QsBlock qs_block_of(const rrl_eval_rollout_qs_t* p) {
     return b;
 }
 
+// the Q-sampling kernel of an env family, solo and packed, with the flag of its LDS grant (> 64 KB: once per kernel)
+struct QsSolo {
+    void (*kernel)(const QsBlock);
+    bool* granted;
+};
+QsSolo qs_solo(bool maze) {
+    static bool nav_set = false, maze_set = false;
+    return maze ? QsSolo{eval_rollout_qs_maze_kernel, &maze_set} : QsSolo{eval_rollout_qs_kernel, &nav_set};
+}
+struct QsPack {
+    void (*kernel)(const QsBlock*, rrl_pack::Idx);
+    bool* granted;
+};
+QsPack qs_pack(bool maze) {
+    static bool nav_set = false, maze_set = false;
+    return maze ? QsPack{eval_rollout_qs_maze_pack_kernel, &maze_set} : QsPack{eval_rollout_qs_pack_kernel, &nav_set};
+}
+
 int launch_qs_solo(const rrl_eval_rollout_qs_t* p, void* stream) {
     const int rc = check_qs(p);
     if (rc != RRL_OK) return rc;
     const QsBlock b = qs_block_of(p);
-    static bool nav_set = false, maze_set = false;
-    if (is_maze(p)) {
-        const int rl = grant_lds(eval_rollout_qs_maze_kernel, kQsLdsBytes, maze_set);
-        if (rl != RRL_OK) return rl;
-        hipLaunchKernelGGL(eval_rollout_qs_maze_kernel, dim3((unsigned)b.a.blocks), dim3(kThreads), kQsLdsBytes,
-                           (hipStream_t)stream, b);
-    } else {
-        const int rl = grant_lds(eval_rollout_qs_kernel, kQsLdsBytes, nav_set);
-        if (rl != RRL_OK) return rl;
-        hipLaunchKernelGGL(eval_rollout_qs_kernel, dim3((unsigned)b.a.blocks), dim3(kThreads), kQsLdsBytes, (hipStream_t)stream,
-                           b);
+    const QsSolo k = qs_solo(is_maze(p));
+    const int rl = grant_lds(k.kernel, kQsLdsBytes, *k.granted);
+    if (rl != RRL_OK) return rl;
+    hipLaunchKernelGGL(k.kernel, dim3((unsigned)b.a.blocks), dim3(kThreads), kQsLdsBytes, (hipStream_t)stream, b);
+    return check_launch();
+}
+
+// The packed entries check every seed before anything is stored or launched, and an invalid field (RRL_EINVAL) wins over
+// a size out of range (RRL_ERANGE), whichever seed has it: RRL_EINVAL at once, else the last seed's failure, else RRL_OK
+template <class Check>
+int check_seeds(int S, Check check) {
+    int worst = RRL_OK;
+    for (int s = 0; s < S; ++s) {
+        const int rc = check(s);
+        if (rc == RRL_EINVAL) return rc;
+        if (rc != RRL_OK) worst = rc;
     }
+    return worst;
+}
+
+// ... and launch alike (pack.hpp): `key` holds the entry's input, build(s, block) fills seed s's argument block and returns
+// its tiles (<= 2^18 workgroups per seed: any mapping's grid fits an int); granted: the kernel's LDS grant, if it needs one
+template <class Block, class Build, class Kernel>
+int launch_pack(const rrl_pack::Key& key, int S, Build build, Kernel kernel, int lds, bool* granted, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    if (!plan) {
+        std::vector<Block> blocks(S);
+        int count[rrl_pack::kMaxSeeds];
+        for (int s = 0; s < S; ++s) count[s] = build(s, blocks[s]);
+        plan = rrl_pack::publish(key, blocks, rrl_pack::place(S, count), st);
+        if (!plan) return rrl_pack::store_error();
+    }
+    if (granted) {
+        const int rl = grant_lds(kernel, lds, *granted);
+        if (rl != RRL_OK) return rl;
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)plan->grid), dim3(kThreads), lds, st, (const Block*)plan->dev, plan->ix);
     return check_launch();
 }
 
@@ -713,51 +757,18 @@ int rrl_eval_rollout_qs(const rrl_eval_rollout_qs_t* p, void* stream) { return l
 int rrl_eval_rollout_qs_packed(int S, const rrl_eval_rollout_qs_t* args, void* stream) {
     if (!args) return RRL_EINVAL;
     if (S <= 0 || S > rrl_pack::kMaxSeeds) return RRL_ERANGE;
-    int worst = RRL_OK;
-    for (int s = 0; s < S; ++s) {               // every seed is checked before anything is stored or launched
-        const int rc = check_qs(args + s);
-        if (rc == RRL_EINVAL) return rc;        // an invalid field wins over a size out of range, whichever seed has it
-        if (rc != RRL_OK) worst = rc;
-    }
+    const int worst = check_seeds(S, [&](int s) { return check_qs(args + s); });
+    if (worst == RRL_EINVAL) return worst;
     const bool maze = is_maze(args);
     for (int s = 1; s < S; ++s)
         if (is_maze(args + s) != maze) return RRL_EINVAL;       // one env family per launch: the kernels differ
     if (worst != RRL_OK) return worst;
     if (S == 1) return launch_qs_solo(args, stream);
-    rrl_pack::Key key;
-    key.pod(15);
-    key.pod(S);
+    rrl_pack::Key key(rrl_pack::Site::EvalRolloutQs, S);
     key.add(args, sizeof(rrl_eval_rollout_qs_t) * S);
-    hipStream_t st = (hipStream_t)stream;
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
-    if (!plan) {
-        std::vector<QsBlock> blocks(S);
-        int count[rrl_pack::kMaxSeeds];
-        for (int s = 0; s < S; ++s) {
-            blocks[s] = qs_block_of(args + s);
-            count[s] = blocks[s].a.blocks;
-        }
-        rrl_pack::Idx ix;
-        rrl_pack::ranges(ix, S, count);
-        const int grid = rrl_pack::finish(ix);
-        plan = rrl_pack::store(key, blocks.data(), sizeof(QsBlock) * S, st);
-        if (!plan) return rrl_pack::store_error();
-        plan->grid = grid;
-        plan->ix = ix;
-    }
-    static bool nav_set = false, maze_set = false;
-    if (maze) {
-        const int rl = grant_lds(eval_rollout_qs_maze_pack_kernel, kQsLdsBytes, maze_set);
-        if (rl != RRL_OK) return rl;
-        hipLaunchKernelGGL(eval_rollout_qs_maze_pack_kernel, dim3((unsigned)plan->grid), dim3(kThreads), kQsLdsBytes, st,
-                           (const QsBlock*)plan->dev, plan->ix);
-    } else {
-        const int rl = grant_lds(eval_rollout_qs_pack_kernel, kQsLdsBytes, nav_set);
-        if (rl != RRL_OK) return rl;
-        hipLaunchKernelGGL(eval_rollout_qs_pack_kernel, dim3((unsigned)plan->grid), dim3(kThreads), kQsLdsBytes, st,
-                           (const QsBlock*)plan->dev, plan->ix);
-    }
-    return check_launch();
+    const QsPack k = qs_pack(maze);
+    return launch_pack<QsBlock>(key, S, [&](int s, QsBlock& b) { return (b = qs_block_of(args + s)).a.blocks; }, k.kernel,
+                                kQsLdsBytes, k.granted, stream);
 }
 
 int rrl_eval_rollout(const rrl_eval_rollout_t* p, void* stream) { return launch_solo(p, stream); }
@@ -765,39 +776,14 @@ int rrl_eval_rollout(const rrl_eval_rollout_t* p, void* stream) { return launch_
 int rrl_eval_rollout_packed(int S, const rrl_eval_rollout_t* args, void* stream) {
     if (!args) return RRL_EINVAL;
     if (S <= 0 || S > rrl_pack::kMaxSeeds) return RRL_ERANGE;
-    int worst = RRL_OK;
-    for (int s = 0; s < S; ++s) {               // every seed is checked before anything is stored or launched
-        const int rc = check_desc(args + s);
-        if (rc == RRL_EINVAL) return rc;        // an invalid field wins over a size out of range, whichever seed has it
-        if (rc != RRL_OK) worst = rc;
-    }
-    if (worst != RRL_OK) return worst;
+    const int rc = check_seeds(S, [&](int s) { return check_desc(args + s); });
+    if (rc != RRL_OK) return rc;
     // one seed: the packed launch IS the solo launch (argument block in the kernel arguments, no plan)
     if (S == 1) return launch_solo(args, stream);
-    rrl_pack::Key key;
-    key.pod(13);
-    key.pod(S);
+    rrl_pack::Key key(rrl_pack::Site::EvalRollout, S);
     key.add(args, sizeof(rrl_eval_rollout_t) * S);
-    hipStream_t st = (hipStream_t)stream;
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
-    if (!plan) {
-        std::vector<EvArgs> blocks(S);
-        int count[rrl_pack::kMaxSeeds];
-        for (int s = 0; s < S; ++s) {
-            blocks[s] = block_of(args + s);
-            count[s] = blocks[s].blocks;            // <= 2^18 workgroups per seed: any mapping's grid fits an int
-        }
-        rrl_pack::Idx ix;
-        rrl_pack::ranges(ix, S, count);
-        const int grid = rrl_pack::finish(ix);
-        plan = rrl_pack::store(key, blocks.data(), sizeof(EvArgs) * S, st);
-        if (!plan) return rrl_pack::store_error();
-        plan->grid = grid;
-        plan->ix = ix;
-    }
-    hipLaunchKernelGGL(eval_rollout_pack_kernel, dim3((unsigned)plan->grid), dim3(kThreads), kLdsBytes, st,
-                       (const EvArgs*)plan->dev, plan->ix);
-    return check_launch();
+    return launch_pack<EvArgs>(key, S, [&](int s, EvArgs& b) { return (b = block_of(args + s)).blocks; },
+                               eval_rollout_pack_kernel, kLdsBytes, nullptr, stream);
 }
 
 int rrl_eval_rollout_maze(const rrl_eval_rollout_t* p, int horizon, void* stream) {
@@ -807,39 +793,14 @@ int rrl_eval_rollout_maze(const rrl_eval_rollout_t* p, int horizon, void* stream
 int rrl_eval_rollout_maze_packed(int S, const rrl_eval_rollout_t* args, const int* horizon, void* stream) {
     if (!args || !horizon) return RRL_EINVAL;
     if (S <= 0 || S > rrl_pack::kMaxSeeds) return RRL_ERANGE;
-    int worst = RRL_OK;
-    for (int s = 0; s < S; ++s) {               // every seed is checked before anything is stored or launched
-        const int rc = check_maze(args + s, horizon[s]);
-        if (rc == RRL_EINVAL) return rc;        // an invalid field wins over a size out of range, whichever seed has it
-        if (rc != RRL_OK) worst = rc;
-    }
-    if (worst != RRL_OK) return worst;
+    const int rc = check_seeds(S, [&](int s) { return check_maze(args + s, horizon[s]); });
+    if (rc != RRL_OK) return rc;
     if (S == 1) return launch_maze_solo(args, horizon[0], stream);
-    rrl_pack::Key key;
-    key.pod(14);
-    key.pod(S);
+    rrl_pack::Key key(rrl_pack::Site::EvalRolloutMaze, S);
     key.add(args, sizeof(rrl_eval_rollout_t) * S);
     key.add(horizon, sizeof(int) * S);
-    hipStream_t st = (hipStream_t)stream;
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
-    if (!plan) {
-        std::vector<MazeBlock> blocks(S);
-        int count[rrl_pack::kMaxSeeds];
-        for (int s = 0; s < S; ++s) {
-            blocks[s] = MazeBlock{block_of(args + s), horizon[s]};
-            count[s] = blocks[s].a.blocks;
-        }
-        rrl_pack::Idx ix;
-        rrl_pack::ranges(ix, S, count);
-        const int grid = rrl_pack::finish(ix);
-        plan = rrl_pack::store(key, blocks.data(), sizeof(MazeBlock) * S, st);
-        if (!plan) return rrl_pack::store_error();
-        plan->grid = grid;
-        plan->ix = ix;
-    }
-    hipLaunchKernelGGL(eval_rollout_maze_pack_kernel, dim3((unsigned)plan->grid), dim3(kThreads), kLdsBytes, st,
-                       (const MazeBlock*)plan->dev, plan->ix);
-    return check_launch();
+    const auto build = [&](int s, MazeBlock& b) { return (b = MazeBlock{block_of(args + s), horizon[s]}).a.blocks; };
+    return launch_pack<MazeBlock>(key, S, build, eval_rollout_maze_pack_kernel, kLdsBytes, nullptr, stream);
 }
 
 }  // extern "C"

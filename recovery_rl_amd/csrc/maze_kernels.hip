@@ -212,10 +212,7 @@ int rrl_maze_step_push_packed(int S, const rrl_step_push_t* a, void* stream) {
     if (S <= 0 || S > rrl_pack::kMaxSeeds || !a) return RRL_EINVAL;
     // one seed: the packed launch IS the solo launch (argument block in the kernel arguments, no plan)
     if (S == 1) return rrl_maze_step_push_x(&a[0], stream);
-    rrl_pack::Key key;
-    key.pod(7);
-    key.pod(S);
-    return rrl_step::launch_packed<MazeEnv>(key, S, a, (hipStream_t)stream);
+    return rrl_step::launch_packed<MazeEnv>(rrl_pack::Key(rrl_pack::Site::MazeStep, S), S, a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -50,40 +50,6 @@ static int largest_member(const Group& g, int n) {
 }
 
 // ---- packed launches: the same group launch for S seeds side by side (pack.hpp) ----
-template <class Member>
-static bool pack_key(int site, int S, const int* n, const Member* const* members, rrl_pack::Key& key) {
-    if (S <= 0 || S > rrl_pack::kMaxSeeds || !n || !members) return false;
-    key.pod(site);
-    key.pod(S);
-    for (int s = 0; s < S; ++s) {
-        if (n[s] <= 0 || n[s] > kMaxGroup || !members[s]) return false;
-        key.pod(n[s]);
-        key.add(members[s], sizeof(Member) * n[s]);
-    }
-    return true;
-}
-
-template <class Group, class Member, class Build>
-static int build_pack(int S, const int* n, const Member* const* members, std::vector<Group>& groups, rrl_pack::Idx& ix,
-                      Build build) {
-    groups.resize(S);
-    int count[rrl_pack::kMaxSeeds];
-    for (int s = 0; s < S; ++s) {
-        const int rc = build(n[s], members[s], groups[s]);
-        if (rc != RRL_OK) return rc;
-        count[s] = groups[s].first[n[s]];
-    }
-    rrl_pack::ranges(ix, S, count);
-    return RRL_OK;
-}
-
-// 2-D packed launch (rrl_pack::locate_grid): seed s owns `most[s]` workgroups per member row; returns grid.x
-static int finish_members(rrl_pack::Idx& ix, int S, const int* most) {
-    int count[rrl_pack::kMaxSeeds];
-    for (int s = 0; s < S; ++s) count[s] = most[s] > 0 ? most[s] : 1;
-    rrl_pack::ranges(ix, S, count);
-    return rrl_pack::finish(ix);
-}
 // the placement's four scalars in one batch of kernel-argument loads, then (seed, index inside the seed's member row).
 // (`plan` is named for the reader; pinning the pointer as well -- "s"(address) -- makes the compiler copy it out of a vector
 // register in some kernels and fails: "illegal VGPR to SGPR copy")

@@ -936,8 +936,8 @@ int rrl_mlp3_forward_riders(const rrl_stack_t* stack, const rrl_fwd_riders_t* ri
 
 // the column-split kernels only (what the steady-state iteration launches at H = 256); every seed on the same path
 int rrl_mlp3_forward_multi_packed(int S, const int* n, const rrl_stack_t* const* members, void* stream) {
-    rrl_pack::Key key;
-    if (!pack_key(2, S, n, members, key)) return RRL_EINVAL;
+    rrl_pack::Key key(rrl_pack::Site::StackForward, S);
+    if (!key.groups(S, n, members, kMaxGroup)) return RRL_EINVAL;
     // one seed: the packed launch IS the solo launch (argument block in the kernel arguments, no plan)
     if (S == 1) {
         StackGroup sg;
@@ -948,10 +948,9 @@ int rrl_mlp3_forward_multi_packed(int S, const int* n, const rrl_stack_t* const*
         return rrl_mlp3_forward_multi(n[0], members[0], stream);
     }
     hipStream_t st = (hipStream_t)stream;
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    const rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
-        std::vector<StackGroup> groups;
-        rrl_pack::Idx ix;
+        std::vector<StackGroup> groups(S);
         int path = -1;
         const int big_r = kBigR;      // (4 row tiles per workgroup measured at S = 4, 8: not faster, profiles/patches/README.md)
         // small batches (the updates' B = 256 forwards): kBigR row tiles per workgroup from kPackSmallR2MinSeeds seeds
@@ -963,15 +962,15 @@ int rrl_mlp3_forward_multi_packed(int S, const int* n, const rrl_stack_t* const*
         int loop_nb = 1;
         const auto build_all = [&]() {
             path = -1;
-            return build_pack<StackGroup>(S, n, members, groups, ix, [&](int nk, const rrl_stack_t* m, StackGroup& g) {
+            for (int s = 0; s < S; ++s) {
                 int my;
-                const int r = build_stack_group(nk, m, g, my, big_r, small_r, loop_nb, false);
+                const int r = build_stack_group(n[s], members[s], groups[s], my, big_r, small_r, loop_nb, false);
                 if (r != RRL_OK) return r;
                 if (my == 5) my = 3;          // mixed members: multi-row tiles for all of them (the placement is the pack's)
                 if ((my != 0 && my != 3) || (path >= 0 && my != path)) return int(RRL_EINVAL);
                 path = my;
-                return int(RRL_OK);
-            });
+            }
+            return int(RRL_OK);
         };
         int rc = build_all();
         if (rc != RRL_OK) return rc;
@@ -1015,12 +1014,11 @@ int rrl_mlp3_forward_multi_packed(int S, const int* n, const rrl_stack_t* const*
             most[s] = largest_member(groups[s], n[s]);
             members_most = n[s] > members_most ? n[s] : members_most;
         }
-        plan = rrl_pack::store(key, groups.data(), sizeof(StackGroup) * S, st);
+        rrl_pack::Launch l = rrl_pack::place_members(S, most);
+        l.i0 = path;
+        l.i1 = members_most;
+        plan = rrl_pack::publish(key, groups, l, st);
         if (!plan) return rrl_pack::store_error();
-        plan->grid = finish_members(ix, S, most);
-        plan->ix = ix;
-        plan->i0 = path;
-        plan->i1 = members_most;
     }
     if (plan->i0 == 0)
         hipLaunchKernelGGL(mlp3_fwd_split_pack_kernel<1>, dim3(plan->grid, plan->i1), dim3(256), split_lds_floats(1) * 4, st,

@@ -1709,7 +1709,7 @@ static bool hidden_blocks(int n, const rrl_hidden_bwd_t* ps, HiddenGroup& hg, in
 // plan of a packed hidden-layer backward: per seed the jobs (tile form, or block form from pack_block(S) seeds on), the 2-D
 // placement; i1 = kernel shape (-12: 32 x 64 blocks; 128 / 64 / 32: K-panel width of the tile form), i0 = members
 static int hidden_pack_plan(const rrl_pack::Key& key, int S, const int* n, const rrl_hidden_bwd_t* const* members, hipStream_t st,
-                            rrl_pack::Plan*& plan) {
+                            const rrl_pack::Plan*& plan) {
     std::vector<HiddenJobs> jobs(S);
     int most[rrl_pack::kMaxSeeds], members_most = 1;
     int shape = pack_block(S);
@@ -1729,14 +1729,11 @@ static int hidden_pack_plan(const rrl_pack::Key& key, int S, const int* n, const
     if (shape != 12)                               // the tile form, one tile per workgroup, cannot fold dx partials
         for (int s = 0; s < S; ++s)
             if (wants_fold(n[s], members[s])) return RRL_ERANGE;
-    plan = rrl_pack::store(key, jobs.data(), sizeof(HiddenJobs) * S, st);
-    if (!plan) return rrl_pack::store_error();
-    rrl_pack::Idx ix;
-    plan->grid = finish_members(ix, S, most);
-    plan->ix = ix;
-    plan->i0 = members_most;
-    plan->i1 = shape ? -shape : pack_panel(S);
-    return RRL_OK;
+    rrl_pack::Launch l = rrl_pack::place_members(S, most);
+    l.i0 = members_most;
+    l.i1 = shape ? -shape : pack_panel(S);
+    plan = rrl_pack::publish(key, jobs, l, st);
+    return plan ? RRL_OK : rrl_pack::store_error();
 }
 static void launch_hidden_pack(const rrl_pack::Plan* plan, hipStream_t st) {
     const dim3 grid(plan->grid, plan->i0, 2);
@@ -1748,12 +1745,12 @@ static void launch_hidden_pack(const rrl_pack::Plan* plan, hipStream_t st) {
 }
 
 int rrl_mlp_hidden_backward_multi_packed(int S, const int* n, const rrl_hidden_bwd_t* const* members, void* stream) {
-    rrl_pack::Key key;
-    if (!pack_key(1, S, n, members, key)) return RRL_EINVAL;
+    rrl_pack::Key key(rrl_pack::Site::HiddenBackward, S);
+    if (!key.groups(S, n, members, kMaxGroup)) return RRL_EINVAL;
     // one seed: the packed launch IS the solo launch (argument block in the kernel arguments, no plan)
     if (S == 1) return rrl_mlp_hidden_backward_multi(n[0], members[0], stream);
     hipStream_t st = (hipStream_t)stream;
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    const rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
         const int rc = hidden_pack_plan(key, S, n, members, st, plan);
         if (rc != RRL_OK) return rc;
@@ -1908,7 +1905,7 @@ int rrl_mlp_backward_pair_multi(int n, const rrl_head_bwd_t* heads, const rrl_hi
 }
 
 static int head_pack_plan(const rrl_pack::Key& key, int S, const int* n, const rrl_head_bwd_t* const* members, hipStream_t st,
-                          rrl_pack::Plan*& plan) {
+                          const rrl_pack::Plan*& plan) {
     std::vector<HeadBwdGroup> groups(S);
     int most[rrl_pack::kMaxSeeds], members_most = 1;
     for (int s = 0; s < S; ++s) {
@@ -1917,22 +1914,19 @@ static int head_pack_plan(const rrl_pack::Key& key, int S, const int* n, const r
         most[s] = largest_member(groups[s], n[s]);
         members_most = std::max(members_most, n[s]);
     }
-    plan = rrl_pack::store(key, groups.data(), sizeof(HeadBwdGroup) * S, st);
-    if (!plan) return rrl_pack::store_error();
-    rrl_pack::Idx ix;
-    plan->grid = finish_members(ix, S, most);
-    plan->ix = ix;
-    plan->i0 = members_most;
-    return RRL_OK;
+    rrl_pack::Launch l = rrl_pack::place_members(S, most);
+    l.i0 = members_most;
+    plan = rrl_pack::publish(key, groups, l, st);
+    return plan ? RRL_OK : rrl_pack::store_error();
 }
 
 int rrl_mlp_head_backward_multi_packed(int S, const int* n, const rrl_head_bwd_t* const* members, void* stream) {
-    rrl_pack::Key key;
-    if (!pack_key(3, S, n, members, key)) return RRL_EINVAL;
+    rrl_pack::Key key(rrl_pack::Site::HeadBackward, S);
+    if (!key.groups(S, n, members, kMaxGroup)) return RRL_EINVAL;
     // one seed: the packed launch IS the solo launch (argument block in the kernel arguments, no plan)
     if (S == 1) return rrl_mlp_head_backward_multi(n[0], members[0], stream);
     hipStream_t st = (hipStream_t)stream;
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    const rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
         const int rc = head_pack_plan(key, S, n, members, st, plan);
         if (rc != RRL_OK) return rc;
@@ -1945,15 +1939,15 @@ int rrl_mlp_head_backward_multi_packed(int S, const int* n, const rrl_head_bwd_t
 // for the paired form, the two packed launches otherwise -- the same decision, per seed the same results as the solo entry.
 int rrl_mlp_backward_pair_multi_packed(int S, const int* n, const rrl_head_bwd_t* const* heads,
                                        const rrl_hidden_bwd_t* const* hidden, void* stream) {
-    rrl_pack::Key key, key_head, key_hidden;
-    if (!pack_key(3, S, n, heads, key_head) || !pack_key(1, S, n, hidden, key_hidden)) return RRL_EINVAL;
+    rrl_pack::Key key(rrl_pack::Site::BackwardPair, S), key_head(rrl_pack::Site::HeadBackward, S),
+        key_hidden(rrl_pack::Site::HiddenBackward, S);
+    if (!key_head.groups(S, n, heads, kMaxGroup) || !key_hidden.groups(S, n, hidden, kMaxGroup)) return RRL_EINVAL;
     // one seed: the packed launch IS the solo launch (argument block in the kernel arguments, no plan)
     if (S == 1) return rrl_mlp_backward_pair_multi(n[0], heads[0], hidden[0], stream);
-    key.pod(7);
     key.add(key_head.bytes.data(), key_head.bytes.size());
     key.add(key_hidden.bytes.data(), key_hidden.bytes.size());
     hipStream_t st = (hipStream_t)stream;
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    const rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
         std::vector<PairJobs> jobs(S);
         int most[rrl_pack::kMaxSeeds], members_most = 1;
@@ -1972,21 +1966,17 @@ int rrl_mlp_backward_pair_multi_packed(int S, const int* n, const rrl_head_bwd_t
             most[s] = m;
             members_most = std::max(members_most, n[s]);
         }
+        // not pairable (i1 == 0): remember that in a plan without blocks, i.e. without device memory
+        rrl_pack::Launch l;
         if (pair) {
-            plan = rrl_pack::store(key, jobs.data(), sizeof(PairJobs) * S, st);
-            if (!plan) return rrl_pack::store_error();
-            rrl_pack::Idx ix;
-            plan->grid = finish_members(ix, S, most);
-            plan->ix = ix;
-            plan->i0 = members_most;
-            plan->i1 = dout + (blocks ? 16 : 0);
+            l = rrl_pack::place_members(S, most);
+            l.i0 = members_most;
+            l.i1 = dout + (blocks ? 16 : 0);
         } else {
-            // not pairable: remember that (an empty plan: no device copy needed) and issue the two packed launches
-            PairJobs none{};
-            plan = rrl_pack::store(key, &none, sizeof none, st);
-            if (!plan) return rrl_pack::store_error();
-            plan->i1 = 0;
+            jobs.clear();
         }
+        plan = rrl_pack::publish(key, jobs, l, st);
+        if (!plan) return rrl_pack::store_error();
     }
     if (plan->i1 == 0) {
         const int rc = rrl_mlp_head_backward_multi_packed(S, n, heads, stream);

@@ -9,6 +9,12 @@
 // input (the inputs of the steady-state iteration never change: after the first iteration every launch is a hit and nothing
 // is built, allocated or copied -- in particular nothing inside a captured hipGraph); the kernel gets one pointer plus the
 // per-seed block ranges (Idx, by value).
+//
+// Host protocol of a packed entry point, the same at every site: check S and the seeds; S == 1 forwards to the solo launch;
+// Key(Site, S) + the input's bytes; lookup(); on a miss build the S blocks, place() / place_members() them into a Launch and
+// publish(); launch from the plan.  A plan is COMPLETE before it is visible: store() fills every field before it inserts the
+// plan under the lock, lookup() and store() hand out `const Plan*`, and nobody writes a plan afterwards -- entry points
+// may be called from several threads, and a second thread finds either no plan or a whole one.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -39,7 +45,7 @@ struct Idx {
     int sp, p, r;
 };
 
-__device__ __forceinline__ int seed_of(const Idx& ix, int block) {
+__host__ __device__ __forceinline__ int seed_of(const Idx& ix, int block) {
     int s = 0;
     while (s + 1 < ix.S && block >= ix.first[s + 1]) ++s;
     return s;
@@ -47,7 +53,7 @@ __device__ __forceinline__ int seed_of(const Idx& ix, int block) {
 
 // (seed, workgroup index inside the seed's own grid) of physical workgroup b; false: b serves nobody (XCD-aware grids are
 // padded to whole rounds of eight)
-__device__ __forceinline__ bool locate(const Idx& ix, int b, int& s, int& local) {
+__host__ __device__ __forceinline__ bool locate(const Idx& ix, int b, int& s, int& local) {
     if (ix.sp == 0) {
         s = seed_of(ix, b);
         local = b - ix.first[s];
@@ -71,7 +77,7 @@ __device__ __forceinline__ bool locate(const Idx& ix, int b, int& s, int& local)
 // arithmetic alone.  Nothing is read before the member's argument block -- whose address is then known at wave start, so
 // that ONE batch of scalar loads fetches it from the plan's device copy -- and the block's own workgroup count bounds `local`
 // (a surplus workgroup exits behind that batch).  The linear placement (S > 8 with an uneven last round) keeps the walk.
-__device__ __forceinline__ bool locate_grid(const Idx& ix, int b, int& s, int& local) {
+__host__ __device__ __forceinline__ bool locate_grid(const Idx& ix, int b, int& s, int& local) {
     if (ix.sp == 0) return locate(ix, b, s, local);
     const int x = b & 7;
     if (ix.r > 1) {
@@ -164,17 +170,61 @@ inline int finish(Idx& ix) {
     return 8 * ((most + ix.p - 1) / ix.p);
 }
 
+// Launch parameters of a plan: the placement(s) and what the entry point's kernel choice needs
+struct Launch {
+    Idx ix{};
+    Idx ix2{};                    // block ranges of a call's second kernel (rrl_qsample_act_packed: the fold kernel)
+    int grid = 0;                 // workgroups of the launch (finish(ix))
+    int i0 = 0, i1 = 0;           // kernel-specific launch parameters (path, threads, ...)
+    size_t z0 = 0;                // ... dynamic LDS bytes
+};
+
+// 1-D placement: seed s owns count[s] consecutive workgroup indices of its own (0: a seed with nothing to do)
+inline Launch place(int S, const int* count) {
+    Launch l;
+    ranges(l.ix, S, count);
+    l.grid = finish(l.ix);
+    return l;
+}
+// 2-D placement (locate_grid): seed s owns most[s] workgroups (at least one) per member row; grid.x = Launch::grid
+inline Launch place_members(int S, const int* most) {
+    int count[kMaxSeeds];
+    for (int s = 0; s < S; ++s) count[s] = most[s] > 0 ? most[s] : 1;
+    return place(S, count);
+}
+
+// Every packed entry point, once: the first bytes of its keys (process-local values, free to renumber)
+enum class Site : int {
+    HiddenBackward = 1, StackForward, HeadBackward, BackwardPair, Adam, AdamDuals, PolicyHeads, RcpoPenalty, ReplayDraw,
+    NavStep, MazeStep, SqrlAct, QsampleAct, EvalRollout, EvalRolloutMaze, EvalRolloutQs
+};
+
 // A packed launch = (device copy of the S argument blocks, block ranges, launch parameters), built once per distinct
 // INPUT and looked up by the bytes of that input (the caller's descriptor arrays, which the Python side builds in zeroed
 // ctypes memory: deterministic, unlike the padding bytes of structs assembled here).  A hit costs one hash of a few KB.
 struct Key {
     std::vector<char> bytes;
+    Key(Site site, int S) {
+        pod(site);
+        pod(S);
+    }
     void add(const void* p, size_t n) {
         const char* c = static_cast<const char*>(p);
         bytes.insert(bytes.end(), c, c + n);
     }
     template <class T>
     void pod(const T& v) { add(&v, sizeof v); }
+    // a grouped launch's input: per seed n[s] in [1, max_members] members; false: invalid (nothing of `n` / `members` is trusted)
+    template <class Member>
+    bool groups(int S, const int* n, const Member* const* members, int max_members) {
+        if (S <= 0 || S > kMaxSeeds || !n || !members) return false;
+        for (int s = 0; s < S; ++s) {
+            if (n[s] <= 0 || n[s] > max_members || !members[s]) return false;
+            pod(n[s]);
+            add(members[s], sizeof(Member) * n[s]);
+        }
+        return true;
+    }
     uint64_t hash() const {
         uint64_t h = 1469598103934665603ULL;                    // FNV-1a
         for (char c : bytes) h = (h ^ (unsigned char)c) * 1099511628211ULL;
@@ -182,13 +232,8 @@ struct Key {
     }
 };
 
-struct Plan {
-    void* dev = nullptr;          // S argument blocks in device memory
-    Idx ix{};
-    Idx ix2{};                    // block ranges of a call's second kernel (rrl_qsample_act_packed: the fold kernel)
-    int grid = 0;                 // workgroups of the launch (finish(ix))
-    int i0 = 0, i1 = 0;           // kernel-specific launch parameters (path, threads, ...)
-    size_t z0 = 0;                // ... dynamic LDS bytes
+struct Plan : Launch {
+    void* dev = nullptr;          // S argument blocks in device memory (nullptr: a plan of launch parameters only)
     std::vector<char> key, host;  // the input it was built from; staging copy of the blocks (outlives the async transfer)
 };
 
@@ -207,7 +252,7 @@ inline int& store_error() {
     return e;
 }
 
-inline Plan* lookup(const Key& k) {
+inline const Plan* lookup(const Key& k) {
     std::lock_guard<std::mutex> lock(plan_mutex());
     auto it = plans().find(k.hash());
     if (it == plans().end()) return nullptr;
@@ -216,14 +261,15 @@ inline Plan* lookup(const Key& k) {
     return nullptr;
 }
 
-// new plan for `k`: `blocks` (bytes) copied to device memory, stream-ordered.  nullptr: allocation failed, or more distinct
-// inputs than this mechanism is meant for (argument blocks that change on every call)
 inline size_t& plan_count() {
     static size_t n = 0;
     return n;
 }
 
-inline Plan* store(const Key& k, const void* blocks, size_t bytes, hipStream_t st) {
+// new plan for `k`, whole before anybody can find it: `blocks` (bytes; 0: none, no device memory) copied to device memory,
+// stream-ordered, and `l`.  nullptr: allocation failed, or more distinct inputs than this mechanism is meant for (argument
+// blocks that change on every call)
+inline const Plan* store(const Key& k, const void* blocks, size_t bytes, const Launch& l, hipStream_t st) {
     std::lock_guard<std::mutex> lock(plan_mutex());
     store_error() = RRL_ELAUNCH;
     // a miss while the stream is CAPTURING would put a hipMalloc + a pageable copy into the graph and invalidate it with an
@@ -238,10 +284,11 @@ inline Plan* store(const Key& k, const void* blocks, size_t bytes, hipStream_t s
         return nullptr;
     }
     Plan* p = new Plan();
+    static_cast<Launch&>(*p) = l;
     p->key = k.bytes;
-    p->host.assign(static_cast<const char*>(blocks), static_cast<const char*>(blocks) + bytes);
-    if (hipMalloc(&p->dev, bytes) != hipSuccess ||
-        hipMemcpyAsync(p->dev, p->host.data(), bytes, hipMemcpyHostToDevice, st) != hipSuccess) {
+    if (bytes) p->host.assign(static_cast<const char*>(blocks), static_cast<const char*>(blocks) + bytes);
+    if (bytes && (hipMalloc(&p->dev, bytes) != hipSuccess ||
+                  hipMemcpyAsync(p->dev, p->host.data(), bytes, hipMemcpyHostToDevice, st) != hipSuccess)) {
         (void)hipGetLastError();
         delete p;
         return nullptr;
@@ -249,6 +296,11 @@ inline Plan* store(const Key& k, const void* blocks, size_t bytes, hipStream_t s
     plans()[k.hash()].push_back(p);
     ++plan_count();
     return p;
+}
+// ... of S typed argument blocks (none: a plan that only remembers a decision)
+template <class Block>
+inline const Plan* publish(const Key& k, const std::vector<Block>& blocks, const Launch& l, hipStream_t st) {
+    return store(k, blocks.data(), sizeof(Block) * blocks.size(), l, st);
 }
 
 // free every plan (device copies included).  Only when no captured graph that launches a packed kernel is alive: the graphs
@@ -258,7 +310,7 @@ inline int clear() {
     int n = 0;
     for (auto& kv : plans())
         for (Plan* p : kv.second) {
-            (void)hipFree(p->dev);
+            if (p->dev) (void)hipFree(p->dev);
             delete p;
             ++n;
         }

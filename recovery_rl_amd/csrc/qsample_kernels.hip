@@ -351,14 +351,12 @@ int rrl_qsample_act_packed(int S, const rrl_qsample_act_t* args, const rrl_qsamp
     if (S == 1) return launch_solo(args, gates, stream);
     for (int s = 0; s < S; ++s)                 // the grid of any mapping fits an int
         if ((long long)args[s].n * chunks_of(args[s].k) > INT32_MAX / rrl_pack::kMaxSeeds) return RRL_ERANGE;
-    rrl_pack::Key key;
-    key.pod(12);
-    key.pod(S);
+    rrl_pack::Key key(rrl_pack::Site::QsampleAct, S);
     key.pod(int(gates != nullptr));
     key.add(args, sizeof(rrl_qsample_act_t) * S);
     if (gates) key.add(gates, sizeof(rrl_qsample_gate_t) * S);
     hipStream_t st = (hipStream_t)stream;
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    const rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
         std::vector<QsArgs> blocks(S);
         int score[rrl_pack::kMaxSeeds], fold[rrl_pack::kMaxSeeds];
@@ -367,16 +365,12 @@ int rrl_qsample_act_packed(int S, const rrl_qsample_act_t* args, const rrl_qsamp
             score[s] = a.n * a.P;                              // n x ceil(k / 128) workgroups, as in the solo kernel
             fold[s] = grid_for(a.n);                           // one thread per env
         }
-        rrl_pack::Idx ix, fx;                   // block ranges of the score and of the fold kernel
-        rrl_pack::ranges(ix, S, score);
-        rrl_pack::ranges(fx, S, fold);
-        const int grid = rrl_pack::finish(ix), fold_grid = rrl_pack::finish(fx);
-        plan = rrl_pack::store(key, blocks.data(), sizeof(QsArgs) * S, st);
+        rrl_pack::Launch l = rrl_pack::place(S, score);     // the score kernel's placement, and in ix2 / i0 the fold kernel's
+        const rrl_pack::Launch f = rrl_pack::place(S, fold);
+        l.ix2 = f.ix;
+        l.i0 = f.grid;
+        plan = rrl_pack::publish(key, blocks, l, st);
         if (!plan) return rrl_pack::store_error();
-        plan->grid = grid;
-        plan->ix = ix;
-        plan->i0 = fold_grid;
-        plan->ix2 = fx;
     }
     static bool lds_set = false;
     const int rc = grant_lds(qsample_score_pack_kernel, kLdsBytes, lds_set);

@@ -258,9 +258,7 @@ int rrl_sample_multi_packed(int S, const rrl_sample_args_t* args, void* stream) 
     if (S == 1)
         return rrl_sample_multi(args[0].first, args[0].second, args[0].noise_pairs, args[0].noise_seed, args[0].noise_counter,
                                 args[0].noise_counter_dev, args[0].noise_counter_inc, args[0].noise_out, stream);
-    rrl_pack::Key key;
-    key.pod(5);
-    key.pod(S);
+    rrl_pack::Key key(rrl_pack::Site::ReplayDraw, S);
     for (int s = 0; s < S; ++s) {
         key_draw(key, args[s].first);
         key_draw(key, args[s].second);
@@ -268,7 +266,7 @@ int rrl_sample_multi_packed(int S, const rrl_sample_args_t* args, void* stream) 
         key.pod(args[s].noise_counter_dev); key.pod(args[s].noise_counter_inc); key.pod(args[s].noise_out);
     }
     hipStream_t st = (hipStream_t)stream;
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    const rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
         std::vector<SamplePack> packs(S);
         int threads = 0;
@@ -288,16 +286,13 @@ int rrl_sample_multi_packed(int S, const rrl_sample_args_t* args, void* stream) 
             noise_blocks(packs[s].nz, threads);
             count[s] = 2 + packs[s].nz.blocks;
         }
-        rrl_pack::Idx ix;
-        rrl_pack::ranges(ix, S, count);
         static size_t granted = 64 * 1024;
         if (!grant_sample_lds(sample_pack_kernel, lds, granted)) return RRL_ERANGE;
-        plan = rrl_pack::store(key, packs.data(), sizeof(SamplePack) * S, st);
+        rrl_pack::Launch l = rrl_pack::place(S, count);
+        l.i0 = threads;
+        l.z0 = lds;
+        plan = rrl_pack::publish(key, packs, l, st);
         if (!plan) return rrl_pack::store_error();
-        plan->grid = rrl_pack::finish(ix);
-        plan->ix = ix;
-        plan->i0 = threads;
-        plan->z0 = lds;
     }
     hipLaunchKernelGGL(sample_pack_kernel, dim3(plan->grid), dim3(plan->i0), plan->z0, st,
                        (const SamplePack*)plan->dev, plan->ix);

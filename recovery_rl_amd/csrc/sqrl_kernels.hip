@@ -315,12 +315,10 @@ int rrl_sqrl_act_packed(int S, const rrl_sqrl_act_t* args, void* stream) {
         if (args[s].k != args[0].k) return RRL_EINVAL;
     // one seed: the packed launch IS the solo launch (argument block in the kernel arguments, no plan)
     if (S == 1) return rrl_sqrl_act(args, stream);
-    rrl_pack::Key key;
-    key.pod(11);
-    key.pod(S);
+    rrl_pack::Key key(rrl_pack::Site::SqrlAct, S);
     key.add(args, sizeof(rrl_sqrl_act_t) * S);
     hipStream_t st = (hipStream_t)stream;
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    const rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
         std::vector<SqrlArgs> blocks(S);
         int count[rrl_pack::kMaxSeeds];
@@ -329,13 +327,10 @@ int rrl_sqrl_act_packed(int S, const rrl_sqrl_act_t* args, void* stream) {
             blocks[s] = block_of(args + s);
             count[s] = args[s].n;
         }
-        rrl_pack::Idx ix;
-        rrl_pack::ranges(ix, S, count);
-        plan = rrl_pack::store(key, blocks.data(), sizeof(SqrlArgs) * S, st);
+        rrl_pack::Launch l = rrl_pack::place(S, count);
+        l.i0 = (args[0].k + 15) / 16;
+        plan = rrl_pack::publish(key, blocks, l, st);
         if (!plan) return rrl_pack::store_error();
-        plan->grid = rrl_pack::finish(ix);
-        plan->ix = ix;
-        plan->i0 = (args[0].k + 15) / 16;
     }
     switch (plan->i0) {
         case 1: return launch_pack<1>(*plan, st);

@@ -652,16 +652,16 @@ inline int fill_args(StepPushArgs& p, const rrl_step_push_t* a) {
 }
 
 // rrl_*_step_push_packed: the steps of S seeds in one launch (pack.hpp).  `key` arrives holding what the entry point puts
-// in front (its tag, S, and the navigation entry's env kind); the plan is the seeds' argument blocks in device memory.
+// in front (its site, S, and the navigation entry's env kind); the plan is the seeds' argument blocks in device memory.
 template <class ENV>
-inline int launch_packed(rrl_pack::Key& key, int S, const rrl_step_push_t* a, hipStream_t st) {
+inline int launch_packed(rrl_pack::Key key, int S, const rrl_step_push_t* a, hipStream_t st) {
     for (int s = 0; s < S; ++s) {
         key.pod(a[s]);
         if (a[s].memory) key.pod(*a[s].memory);
         if (a[s].recovery_memory) key.pod(*a[s].recovery_memory);
         if (a[s].sel_rec_head) key.pod(*a[s].sel_rec_head);
     }
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    const rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
         std::vector<StepPushArgs> ps(S);
         int count[rrl_pack::kMaxSeeds];
@@ -672,13 +672,10 @@ inline int launch_packed(rrl_pack::Key& key, int S, const rrl_step_push_t* a, hi
             if (a[s].n <= 0 || regime_of(a[s].n) != regime) return RRL_EINVAL;
             count[s] = grid_cover(a[s].n);
         }
-        rrl_pack::Idx ix;
-        rrl_pack::ranges(ix, S, count);
-        plan = rrl_pack::store(key, ps.data(), sizeof(StepPushArgs) * S, st);
+        rrl_pack::Launch l = rrl_pack::place(S, count);
+        l.i0 = regime;
+        plan = rrl_pack::publish(key, ps, l, st);
         if (!plan) return rrl_pack::store_error();
-        plan->grid = rrl_pack::finish(ix);
-        plan->ix = ix;
-        plan->i0 = regime;
     }
     launch_pack<ENV>((const StepPushArgs*)plan->dev, plan->ix, plan->grid, plan->i0, st);
     return rrl_host::check_launch();

@@ -853,19 +853,12 @@ int rrl_policy_heads_fwd_multi(int n, const rrl_policy_head_t* heads, void* stre
 }
 
 int rrl_policy_heads_fwd_multi_packed(int S, const int* n, const rrl_policy_head_t* const* heads, void* stream) {
-    if (S <= 0 || S > rrl_pack::kMaxSeeds || !n || !heads) return RRL_EINVAL;
-    rrl_pack::Key key;
-    key.pod(8);
-    key.pod(S);
-    for (int s = 0; s < S; ++s) {
-        if (n[s] <= 0 || n[s] > kMaxHeads || !heads[s]) return RRL_EINVAL;
-        key.pod(n[s]);
-        key.add(heads[s], sizeof(rrl_policy_head_t) * n[s]);
-    }
+    rrl_pack::Key key(rrl_pack::Site::PolicyHeads, S);
+    if (!key.groups(S, n, heads, kMaxHeads)) return RRL_EINVAL;
     // one seed: the packed launch IS the solo launch (argument block in the kernel arguments, no plan)
     if (S == 1) return rrl_policy_heads_fwd_multi(n[0], heads[0], stream);
     hipStream_t st = (hipStream_t)stream;
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    const rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
         std::vector<HeadGroup> groups(S);
         int count[rrl_pack::kMaxSeeds];
@@ -874,12 +867,8 @@ int rrl_policy_heads_fwd_multi_packed(int S, const int* n, const rrl_policy_head
             if (rc != RRL_OK) return rc;
             count[s] = groups[s].first[n[s]];
         }
-        rrl_pack::Idx ix;
-        rrl_pack::ranges(ix, S, count);
-        plan = rrl_pack::store(key, groups.data(), sizeof(HeadGroup) * S, st);
+        plan = rrl_pack::publish(key, groups, rrl_pack::place(S, count), st);
         if (!plan) return rrl_pack::store_error();
-        plan->grid = rrl_pack::finish(ix);
-        plan->ix = ix;
     }
     hipLaunchKernelGGL(policy_heads_pack_kernel, dim3(plan->grid), dim3(kBlock), 0, st, (const HeadGroup*)plan->dev, plan->ix);
     return check_launch();
@@ -945,16 +934,15 @@ int rrl_rcpo_penalty_packed(int S, const rrl_penalty_args_t* args, void* stream)
         if (!penalty_args_ok(args[s])) return RRL_EINVAL;
     // one seed: the packed launch IS the solo launch
     if (S == 1) return rrl_rcpo_penalty(args, stream);
-    rrl_pack::Key key;
-    key.pod(9);
-    key.pod(S);
+    rrl_pack::Key key(rrl_pack::Site::RcpoPenalty, S);
     key.add(args, sizeof(rrl_penalty_args_t) * S);
     hipStream_t st = (hipStream_t)stream;
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    const rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
-        plan = rrl_pack::store(key, args, sizeof(rrl_penalty_args_t) * S, st);
+        rrl_pack::Launch l;               // one workgroup per seed, blockIdx.x IS the seed: no placement
+        l.grid = S;
+        plan = rrl_pack::publish(key, std::vector<rrl_penalty_args_t>(args, args + S), l, st);
         if (!plan) return rrl_pack::store_error();
-        plan->grid = S;
     }
     hipLaunchKernelGGL(rcpo_penalty_pack_kernel, dim3(plan->grid), dim3(kBlock), 0, st, (const rrl_penalty_args_t*)plan->dev);
     return check_launch();
@@ -1086,9 +1074,7 @@ int rrl_adam_step_multi_duals(int n_seg, const rrl_adam_seg_t* segs, int n_dual,
 int rrl_adam_step_multi_packed(int S, const int* n_seg, const rrl_adam_seg_t* const* segs, const float* lr, float beta1,
                                float beta2, float eps, void* stream) {
     if (S <= 0 || S > rrl_pack::kMaxSeeds || !n_seg || !segs || !lr) return RRL_EINVAL;
-    rrl_pack::Key key;
-    key.pod(4);
-    key.pod(S);
+    rrl_pack::Key key(rrl_pack::Site::Adam, S);
     key.pod(beta1); key.pod(beta2); key.pod(eps);
     for (int s = 0; s < S; ++s) {
         if (n_seg[s] <= 0 || n_seg[s] > RRL_ADAM_MAX_SEGS || !segs[s]) return RRL_EINVAL;
@@ -1099,7 +1085,7 @@ int rrl_adam_step_multi_packed(int S, const int* n_seg, const rrl_adam_seg_t* co
     // one seed: the packed launch IS the solo launch (argument block in the kernel arguments, no plan)
     if (S == 1) return rrl_adam_step_multi(n_seg[0], segs[0], lr[0], beta1, beta2, eps, stream);
     hipStream_t st = (hipStream_t)stream;
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    const rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
         std::vector<AdamPack> packs(S);
         int count[rrl_pack::kMaxSeeds];
@@ -1115,13 +1101,10 @@ int rrl_adam_step_multi_packed(int S, const int* n_seg, const rrl_adam_seg_t* co
             count[s] = most;
             segs_most = std::max(segs_most, n_seg[s]);
         }
-        rrl_pack::Idx ix;
-        rrl_pack::ranges(ix, S, count);
-        plan = rrl_pack::store(key, packs.data(), sizeof(AdamPack) * S, st);
+        rrl_pack::Launch l = rrl_pack::place_members(S, count);
+        l.i0 = segs_most;
+        plan = rrl_pack::publish(key, packs, l, st);
         if (!plan) return rrl_pack::store_error();
-        plan->grid = rrl_pack::finish(ix);
-        plan->ix = ix;
-        plan->i0 = segs_most;
     }
     hipLaunchKernelGGL(adam_pack_kernel, dim3(plan->grid, plan->i0), dim3(kBlock), 0, st, (const AdamPack*)plan->dev, plan->ix);
     return check_launch();
@@ -1131,9 +1114,7 @@ int rrl_adam_step_multi_duals_packed(int S, const int* n_seg, const rrl_adam_seg
                                      const rrl_dual_t* const* duals, const float* lr, float beta1, float beta2, float eps,
                                      void* stream) {
     if (S <= 0 || S > rrl_pack::kMaxSeeds || !n_seg || !segs || !n_dual || !duals || !lr) return RRL_EINVAL;
-    rrl_pack::Key key;
-    key.pod(10);
-    key.pod(S);
+    rrl_pack::Key key(rrl_pack::Site::AdamDuals, S);
     key.pod(beta1); key.pod(beta2); key.pod(eps);
     for (int s = 0; s < S; ++s) {
         if (n_seg[s] < 0 || n_seg[s] > RRL_ADAM_MAX_SEGS || (n_seg[s] > 0 && !segs[s]) || n_dual[s] <= 0 ||
@@ -1148,7 +1129,7 @@ int rrl_adam_step_multi_duals_packed(int S, const int* n_seg, const rrl_adam_seg
     // one seed: the packed launch IS the solo launch (argument block in the kernel arguments, no plan)
     if (S == 1) return rrl_adam_step_multi_duals(n_seg[0], segs[0], n_dual[0], duals[0], lr[0], beta1, beta2, eps, stream);
     hipStream_t st = (hipStream_t)stream;
-    rrl_pack::Plan* plan = rrl_pack::lookup(key);
+    const rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
         std::vector<AdamDualPack> packs(S);
         int count[rrl_pack::kMaxSeeds];
@@ -1165,13 +1146,10 @@ int rrl_adam_step_multi_duals_packed(int S, const int* n_seg, const rrl_adam_seg
             count[s] = most;
             segs_most = std::max(segs_most, n_seg[s]);
         }
-        rrl_pack::Idx ix;
-        rrl_pack::ranges(ix, S, count);
-        plan = rrl_pack::store(key, packs.data(), sizeof(AdamDualPack) * S, st);
+        rrl_pack::Launch l = rrl_pack::place_members(S, count);
+        l.i0 = segs_most + 1;             // one row more: row n_seg of a seed is its dual row
+        plan = rrl_pack::publish(key, packs, l, st);
         if (!plan) return rrl_pack::store_error();
-        plan->grid = rrl_pack::finish(ix);
-        plan->ix = ix;
-        plan->i0 = segs_most + 1;         // one row more: row n_seg of a seed is its dual row
     }
     hipLaunchKernelGGL(adam_pack_dual_kernel, dim3(plan->grid, plan->i0), dim3(kBlock), 0, st, (const AdamDualPack*)plan->dev,
                        plan->ix);

@@ -84,7 +84,7 @@ def test_the_restated_decisions_are_the_sources():
     assert "if (shape != 12)" in mlp and "if (wants_fold(n[s], members[s])) return RRL_ERANGE;" in mlp
     assert "if (first && !hg.fast[k]) return RRL_ERANGE;" in mlp
     assert "if (shape) ok = hidden_blocks(n[s], members[s], hg, shape / 10, shape % 10);" in mlp
-    assert "plan->i1 = shape ? -shape : pack_panel(S);" in mlp
+    assert "l.i1 = shape ? -shape : pack_panel(S);" in mlp
     # launch_head_group: one member with a loss description has a kernel of its own
     body = _one(r"static void launch_head_group\(.*?\) \{(.*?)\n\}", mlp, "launch_head_group", re.S)
     assert _squash(body).startswith("if (n == 1) {") and body.count("head_bwd_loss_kernel<") == 6
