@@ -898,8 +898,11 @@ int rrl_ens_train_epoch_big(const rrl_ens_t* m, int n_seg, const rrl_adam_seg_t*
  *                                          k, env seed, tick, weights, box and traces may differ by seed, and the kind within
  *                                          Navigation or the horizon within Maze; Navigation and Maze seeds in one call:
  *                                          RRL_EINVAL)
+ *   rrl_eval_rollout_sqrl_packed           rrl_eval_rollout_sqrl       (args[s]; the same mapping on the SQRL kernels; n, T, k,
+ *                                          env seed, tick, reset, weights and traces may differ by seed, and the kind within
+ *                                          Navigation or the horizon within Maze; a Navigation + Maze mix: RRL_EINVAL)
  * Every seed's arguments are checked before anything is stored or launched (the stand-alone entry's codes); a NULL array:
- * RRL_EINVAL; S outside 1 .. 16: RRL_EINVAL, except from rrl_eval_rollout[_maze|_qs]_packed, which return RRL_ERANGE for it.
+ * RRL_EINVAL; S outside 1 .. 16: RRL_EINVAL, except from rrl_eval_rollout[_maze|_qs|_sqrl]_packed, which return RRL_ERANGE for it.
  * S == 1 is the stand-alone launch.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
@@ -1162,6 +1165,49 @@ int rrl_eval_rollout_qs(const rrl_eval_rollout_qs_t* a, void* stream);
  * the stand-alone entry checks it, all before anything is stored or launched (RRL_EINVAL of any seed wins); args == NULL:
  * RRL_EINVAL; S outside 1 .. 16: RRL_ERANGE; S == 1 is rrl_eval_rollout_qs(args). */
 int rrl_eval_rollout_qs_packed(int S, const rrl_eval_rollout_qs_t* args, void* stream);
+
+/* The same rollout for SQRL (--use_constraint_sampling without --use_recovery: SAC._sqrl_action, recovery_rl/sac.py:139-161,
+ * inside get_test_rollout): EVERY live row executes, on every step, the pick among k candidates of the task policy's
+ * tanh-Gaussian head -- rrl_sqrl_act's three steps inside the rollout launch, on kernels of their own (Navigation 1 / 2 and
+ * Maze, by base.env_kind), so the kernels above keep their code.  Start, transition, results, tick and the base's traces are
+ * those above; for a row i alive before step j, with ctr = tick + reset + j:
+ *   head       the FOUR last-layer outputs (mean0, mean1, log_std0, log_std1: pW3 / pb3 hold four rows, the stacked head that
+ *              rrl_sqrl_act_t.head describes) of the task policy on float(pos_i); rows 0 .. 1 are the bits of the two-output
+ *              form, so tr_task = tanh(mean) * scale + bias is what the kernels above write.  Under SQRL it is not executed.
+ *   candidate  eps_c = float of the normal pair of Philox (seed, row i k + c, RRL_STREAM_EVAL_SQRL, ctr), c = 0 .. k - 1;
+ *              a_c, logp_c = the tanh-Gaussian head of rrl_sqrl_act (log_std clamped to [-20, 2], kEps = 1e-6, f32, the same
+ *              expression order).  The draws are keyed by (env row, step) alone.
+ *   score      q_c = max(sigmoid z_0, sigmoid z_1) of Q_risk on [float(pos_i) | a_c], NaN propagates: the 64-row tile of
+ *              rrl_sqrl_act -- the bits rrl_sqrl_act gives for the same obs, head and eps
+ *   pick       rrl_sqrl_act's, with safe = q <= base.eps_safe and u = the open-unit double of the low 64 bits of Philox (seed,
+ *              row i, RRL_STREAM_EVAL_SQRL_PICK, ctr): weights in double, the position in the SAFE list applied to the FULL
+ *              list; no safe candidate: argmin q, lowest index on ties, NaN counts as the smallest
+ *   execute    executed = a_pick.  No gate and no recovery policy: bit 4 of tr_flags stays 0, tr_z and tr_eps are never written.
+ * A workgroup flattens the candidates of the live rows of its 16 into passes of up to 64 scoring rows (every row of a pass
+ * carries its own obs), keeps the candidates, logp and q of the whole tile in LDS (103.0 KB in all: one workgroup per CU), and
+ * picks for different rows on different waves.  Dead rows and rows >= n draw and score nothing, a workgroup without a live row
+ * leaves the step loop: none of this changes a bit of any output.  The traces of this struct are written for live rows only.
+ * Checks before any launch, without a device: everything rrl_eval_rollout (rrl_eval_rollout_maze for RRL_ENV_MAZE) checks on
+ * base, with the same codes; no Q_risk group, any pointer of the recovery group given: RRL_EINVAL; k outside 1..128,
+ * n k >= 2^32, a Maze horizon outside 1 .. 2^30: RRL_ERANGE (an invalid field wins). */
+enum { RRL_STREAM_EVAL_SQRL = 14,        /* SQRL candidate noise of the evaluation rollout */
+       RRL_STREAM_EVAL_SQRL_PICK = 15 }; /* its categorical draw */
+typedef struct {
+    rrl_eval_rollout_t base;  /* Q_risk group required; recovery group (rW1 ..) all NULL; pW3 / pb3 hold FOUR rows:
+                                 mean0, mean1, log_std0, log_std1 (the stacked head rrl_sqrl_act_t.head describes) */
+    int k;                    /* candidates per live row, 1..128 (the reference: 100) */
+    int horizon;              /* Maze only (1 .. 2^30); ignored for Navigation */
+    float*   tr_head;         /* nullable trace [T, n, 4]: the policy's last-layer output before the clamp */
+    int32_t *tr_pick, *tr_cstar, *tr_nsafe;   /* nullable traces [T, n]; cstar = -1 on the argmin branch */
+    float*   tr_q;            /* nullable trace [T, n]: q of the executed candidate */
+} rrl_eval_rollout_sqrl_t;
+int rrl_eval_rollout_sqrl(const rrl_eval_rollout_sqrl_t* a, void* stream);
+/* ... and for S seeds side by side (the packed-launch table above): all Navigation (either kind) or all Maze (any horizons),
+ * a mix is RRL_EINVAL; n, T, k, reset and weights may differ by seed; each seed's outputs, traces and tick are the bits of
+ * its stand-alone launch.  Every seed is checked as the stand-alone entry checks it, all before anything is stored or launched
+ * (RRL_EINVAL of any seed wins); args == NULL: RRL_EINVAL; S outside 1 .. 16: RRL_ERANGE; S == 1 is
+ * rrl_eval_rollout_sqrl(args). */
+int rrl_eval_rollout_sqrl_packed(int S, const rrl_eval_rollout_sqrl_t* args, void* stream);
 
 #ifdef __cplusplus
 }

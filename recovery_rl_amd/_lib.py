@@ -55,6 +55,7 @@ EXPORTS = [
     "rrl_qsample_scratch_floats", "rrl_qsample_act", "rrl_qsample_act_gated", "rrl_qsample_act_packed",
     "rrl_eval_rollout", "rrl_eval_rollout_packed", "rrl_eval_rollout_maze", "rrl_eval_rollout_maze_packed",
     "rrl_eval_rollout_qs", "rrl_eval_rollout_qs_packed",
+    "rrl_eval_rollout_sqrl", "rrl_eval_rollout_sqrl_packed",
 ]
 
 class RRLError(RuntimeError):
@@ -337,6 +338,15 @@ class rrl_eval_rollout_qs_t(C.Structure):
         (n, C.c_void_p) for n in ("lo", "hi", "tr_pick", "tr_q")]
 
 
+STREAM_EVAL_SQRL = 14
+STREAM_EVAL_SQRL_PICK = 15
+
+
+class rrl_eval_rollout_sqrl_t(C.Structure):
+    _fields_ = [("base", rrl_eval_rollout_t), ("k", C.c_int), ("horizon", C.c_int)] + [
+        (n, C.c_void_p) for n in ("tr_head", "tr_pick", "tr_cstar", "tr_nsafe", "tr_q")]
+
+
 _lib = None
 
 
@@ -429,6 +439,8 @@ def _declare(lib):
         "rrl_eval_rollout_maze_packed": (ci, [ci, C.POINTER(rrl_eval_rollout_t), C.POINTER(ci), vp]),
         "rrl_eval_rollout_qs": (ci, [C.POINTER(rrl_eval_rollout_qs_t), vp]),
         "rrl_eval_rollout_qs_packed": (ci, [ci, C.POINTER(rrl_eval_rollout_qs_t), vp]),
+        "rrl_eval_rollout_sqrl": (ci, [C.POINTER(rrl_eval_rollout_sqrl_t), vp]),
+        "rrl_eval_rollout_sqrl_packed": (ci, [ci, C.POINTER(rrl_eval_rollout_sqrl_t), vp]),
         "rrl_episode_log_append": (ci, [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(rrl_episode_log_t), vp]),
     }
     for name, (res, args) in sig.items():

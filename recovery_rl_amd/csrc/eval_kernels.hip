@@ -32,6 +32,22 @@
 // CU of the 160 KB -- the launch's shape anyway (4096 envs = 256 workgroups).  A tile with no gated live row skips the
 // phase; rows that are not gated, dead or >= n draw and score nothing.  The NoQs instantiations are the four kernels above,
 // instruction for instruction (profiles/eval_rollout_qsample_fingerprint.txt).
+//
+// SQRL (rrl_eval_rollout_sqrl[_packed], four more kernels) is the same body with the SqOn trait, and a different cost shape:
+// there is no gate, EVERY live row needs k <= 128 candidates of the task policy's tanh-Gaussian head on every step.  The
+// policy stack runs with four outputs (run_stack<2, 4>: mean and log_std rows; rows 0 .. 1 keep the bits of the two-output
+// form, every output is a chain of its own), the candidates of the tile's live rows are drawn by all 512 threads (stream
+// RRL_STREAM_EVAL_SQRL, keyed by (env row, step) alone) and FLATTENED, live rows in ascending order, into passes of up to
+// four row tiles on the same 64-row twin-head tile -- every xs row carries its own obs, so candidates of different env rows
+// share a pass: 25 passes per step at k = 100 with 16 live rows, against 32 when each row is served alone with a ragged
+// second pass.  The candidates, logp and q of the whole tile stay in LDS, and the picks of different rows run on different
+// waves (wave w: rows w and w + 8; the pick's double weights stay in registers and are read across the wave in ascending
+// candidate order, so the sums are those of rrl_sqrl_act).  LDS: the 64-row tile prefix (70.0 KB) + candidates / logp / q
+// (16 x 128 x 4 floats = 32 KB) + head / obs / results / row table / mask (0.9 KB) = 103.0 KB, one workgroup per CU.
+// The candidate-head arithmetic and the pick of sqrl_kernels.hip are RESTATED here (sq_candidates, sq_pick), not shared
+// through a header: rrl_sqrl_act keeps its pick's weights in LDS and serves one env per workgroup, and its kernels keep
+// their code untouched this way; tests/test_eval_sqrl_gpu.py holds the two to the same bits.  The eight kernels
+// above are unchanged, instruction for instruction (profiles/eval_rollout_sqrl_fingerprint.txt).
 #include "maze_device.hpp"
 #include "mfma_tile.hpp"
 #include "pack.hpp"
@@ -77,6 +93,25 @@ constexpr int kQsLdsFloats = kOffQsMask + 4;
 constexpr int kQsLdsBytes = kQsLdsFloats * 4;                // 82.4 KB: one workgroup per CU
 static_assert(kLdsFloats <= rrl_tile::kOffXs, "the rollout's regions lie inside the 64-row tile's activation region");
 
+// SQRL form: the same overlay; the policy stack's four-output partial sums ([4][8][16] at kOffPart) stay inside the 64-row
+// tile's activation region as well
+constexpr uint32_t kStreamEvalSqrl = RRL_STREAM_EVAL_SQRL, kStreamEvalSqrlPick = RRL_STREAM_EVAL_SQRL_PICK;
+constexpr int kSqMaxK = 128;                                 // candidates per live row
+constexpr float kLogSigMax = 2.f, kLogSigMin = -20.f, kEps = 1e-6f;   // model.py:14-16 (sqrl_kernels.hip's)
+constexpr float kHalfLog2Pi = 0.918938533204672742f;
+constexpr int kOffSqCand = rrl_tile::kOffOwn;                // [16][128][2] candidates of the tile's rows
+constexpr int kOffSqLogp = kOffSqCand + kRows * kSqMaxK * 2; // [16][128]
+constexpr int kOffSqQ = kOffSqLogp + kRows * kSqMaxK;        // [16][128] max(sigmoid z0, sigmoid z1)
+constexpr int kOffSqHead = kOffSqQ + kRows * kSqMaxK;        // [16][4] the policy's last-layer output
+constexpr int kOffSqObs = kOffSqHead + kRows * 4;            // [16][2] float(pos)
+constexpr int kOffSqRes = kOffSqObs + kRows * 2;             // [16][8] pick, cstar, n_safe (int bits), q, that candidate
+constexpr int kOffSqRow = kOffSqRes + kRows * 8;             // [16] tile row of the s-th live row (int bits)
+constexpr int kOffSqMask = kOffSqRow + kRows;                // [1] the live rows of the tile, one bit each (int bits)
+constexpr int kSqLdsFloats = kOffSqMask + 4;
+constexpr int kSqLdsBytes = kSqLdsFloats * 4;                // 103.0 KB: one workgroup per CU
+static_assert(kOffPart + 4 * kWaves * kRows <= rrl_tile::kOffXs, "four outputs' partial sums lie inside the activation region");
+static_assert(kSqLdsBytes <= 160 * 1024, "one workgroup's LDS");
+
 struct Net {
     const float *W1, *b1, *W2p, *b2, *W3, *b3;
 };
@@ -111,10 +146,23 @@ struct QsArgs {
     float* tr_q;
 };
 struct NoQs {
-    static constexpr bool on = false;
+    static constexpr bool on = false, sqrl = false;
+    using Args = QsArgs;
 };
 struct QsOn : QsArgs {
-    static constexpr bool on = true;
+    static constexpr bool on = true, sqrl = false;
+    using Args = QsArgs;
+};
+// ... and the SQRL group (rrl_eval_rollout_sqrl_t's own fields)
+struct SqArgs {
+    int k;
+    float* tr_head;
+    int32_t *tr_pick, *tr_cstar, *tr_nsafe;
+    float* tr_q;
+};
+struct SqOn : SqArgs {
+    static constexpr bool on = false, sqrl = true;
+    using Args = SqArgs;
 };
 
 // One 2-hidden-layer stack (head `head` of w) on the row tile in xs: inputs = the first DIN columns of xs, outputs = the
@@ -326,14 +374,198 @@ __device__ __forceinline__ void qs_row(float* lds, const EvArgs& a, const QsArgs
     __syncthreads();                              // res[g] is out; candidates and q are free for the next gated row
 }
 
+// ---- SQRL: candidates, scores and picks of the tile's live rows (sqrl_kernels.hip's arithmetic, restated) ----
+
+// Candidates of the `nl` live rows, flattened: f = slot k + c, slot-th live row g = rowof[slot].  a_c and logp_c are
+// rrl_sqrl_act's tanh-Gaussian head (gauss_head_fwd_row of update_kernels.hip), in the same expression order.
+__device__ __forceinline__ void sq_candidates(float* lds, const EvArgs& a, int k, int nl, unsigned b, uint64_t ctr, int tid) {
+    const int total = nl * k;
+#pragma unroll 1
+    for (int f = tid; f < total; f += kThreads) {
+        const int slot = f / k, c = f - slot * k;
+        const int g = __float_as_int(lds[kOffSqRow + slot]);
+        const long long grow = (long long)b * kRows + g;
+        double d0, d1;
+        rrl::normal_at(a.seed, uint32_t(grow * k + c), kStreamEvalSqrl, ctr, d0, d1);
+        const float e2[2] = {float(d0), float(d1)};
+        float lp = 0.f, act2[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float mean = lds[kOffSqHead + 4 * g + j];
+            const float ls = fminf(fmaxf(lds[kOffSqHead + 4 * g + 2 + j], kLogSigMin), kLogSigMax);
+            const float e = e2[j];
+            const float y = tanhf(mean + expf(ls) * e);
+            act2[j] = y * a.scale[j] + a.bias[j];
+            lp += -0.5f * e * e - ls - kHalfLog2Pi - logf(a.scale[j] * (1.f - y * y) + kEps);
+        }
+        const int qi = g * kSqMaxK + c;
+        lds[kOffSqCand + 2 * qi] = act2[0];
+        lds[kOffSqCand + 2 * qi + 1] = act2[1];
+        lds[kOffSqLogp + qi] = lp;
+    }
+}
+
+// One pass: flattened candidates [f0, f0 + 16 MR) through the twin heads, every row with its own obs; q of the live ones
+template <int MR>
+__device__ __forceinline__ void sq_pass(float* lds, const Net& q, int k, int total, int f0, int tid, int wave, int lane) {
+    int qi = -1;
+    if (tid < rrl_tile::kRows) {
+        const int f = f0 + tid;
+        f32x4 x = {0.f, 0.f, 0.f, 0.f};           // rows past the last candidate: finite inputs, results never read
+        if (f < total) {
+            const int slot = f / k, c = f - slot * k;
+            const int g = __float_as_int(lds[kOffSqRow + slot]);
+            qi = g * kSqMaxK + c;
+            x = f32x4{lds[kOffSqObs + 2 * g], lds[kOffSqObs + 2 * g + 1], lds[kOffSqCand + 2 * qi], lds[kOffSqCand + 2 * qi + 1]};
+        }
+        *reinterpret_cast<f32x4*>(lds + rrl_tile::kOffXs + tid * 4) = x;
+    }
+    __syncthreads();
+    rrl_tile::q_phase<MR>(lds, q, wave, lane);
+    if (qi >= 0) lds[kOffSqQ + qi] = rrl_tile::twin_q(lds, q, tid).q;
+    // xs and qpart are rewritten only behind the next pass's barriers
+}
+
+// lane l's double, l wave-uniform
+__device__ __forceinline__ double lane_double(double v, int l) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+    return __hiloint2double(hi, lo);
+}
+
+// The pick of tile row g (env `grow`) by ONE wave (sac.py:153-158; the position in the SAFE list is applied to the FULL list,
+// as the reference does): rrl_sqrl_act's, with the double weights in registers (lane l holds candidates l and l + 64) read in
+// ascending candidate order -- the same sums.  Leaves res[g].
+__device__ __forceinline__ void sq_pick(float* lds, const EvArgs& a, int k, int g, long long grow, uint64_t ctr, int lane) {
+    const float* qrow = lds + kOffSqQ + g * kSqMaxK;
+    const float* lprow = lds + kOffSqLogp + g * kSqMaxK;
+    float qv[2], lpv[2];
+    bool safe[2];
+    unsigned long long m[2];
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+        const int c = lane + 64 * hf;
+        const bool live = c < k;
+        qv[hf] = live ? qrow[c] : 0.f;
+        lpv[hf] = live ? lprow[c] : 0.f;
+        safe[hf] = live && qv[hf] <= a.eps_safe;
+        m[hf] = __ballot(safe[hf]);
+    }
+    // argmin of q, lowest index on ties; NaN counts as the smallest (torch.argmin)
+    float best = __builtin_inff();
+    int bidx = kSqMaxK;
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+        const int c = lane + 64 * hf;
+        const float key = qv[hf] != qv[hf] ? -__builtin_inff() : qv[hf];
+        if (c < k && key < best) {               // ascending c: strict < keeps the lower index
+            best = key;
+            bidx = c;
+        }
+    }
+    float L = -__builtin_inff();                  // the largest safe logp
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf)
+        if (safe[hf]) L = fmaxf(L, lpv[hf]);
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const float ob = __shfl_xor(best, off, 64);
+        const int oi = __shfl_xor(bidx, off, 64);
+        if (ob < best || (ob == best && oi < bidx)) {
+            best = ob;
+            bidx = oi;
+        }
+        L = fmaxf(L, __shfl_xor(L, off, 64));
+    }
+    double w[2];
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) w[hf] = safe[hf] ? exp(double(lpv[hf]) - double(L)) : 0.0;
+    const int n_safe = __popcll(m[0]) + __popcll(m[1]);
+    int pick = bidx < k ? bidx : 0, cs = -1;      // every q = +inf cannot happen (q <= 1); keeps the reads below in range
+    if (n_safe > 0) {                             // wave-uniform; every lane runs the same scalar chain
+        const unsigned long long m0 = m[0], m1 = m[1];
+        const double u = rrl::unit_open(rrl::philox_at(a.seed, uint32_t(grow), kStreamEvalSqrlPick, ctr).lo);
+        const int k0 = k < 64 ? k : 64;
+        double T = 0.0;
+#pragma unroll 1
+        for (int c = 0; c < k0; ++c) T += lane_double(w[0], c);
+#pragma unroll 1
+        for (int c = 64; c < k; ++c) T += lane_double(w[1], c - 64);
+        const double thr = u * T;
+        double run = 0.0;
+        int last = -1;
+#pragma unroll 1
+        for (int c = 0; c < k0; ++c) {
+            const double wc = lane_double(w[0], c);
+            if (!((m0 >> c) & 1ULL)) continue;
+            last = c;
+            run += wc;
+            if (cs < 0 && run > thr) cs = c;
+        }
+#pragma unroll 1
+        for (int c = 64; c < k; ++c) {
+            const double wc = lane_double(w[1], c - 64);
+            if (!((m1 >> (c - 64)) & 1ULL)) continue;
+            last = c;
+            run += wc;
+            if (cs < 0 && run > thr) cs = c;
+        }
+        if (cs < 0) cs = last;
+        // safe candidates with index <= c*, minus one
+        const unsigned long long lo = cs < 64 ? (m0 & (~0ULL >> (63 - cs))) : m0;
+        const unsigned long long hi = cs < 64 ? 0ULL : (m1 & (~0ULL >> (127 - cs)));
+        pick = __popcll(lo) + __popcll(hi) - 1;
+    }
+    if (lane == 0) {
+        float* res = lds + kOffSqRes + 8 * g;
+        res[0] = __int_as_float(pick);
+        res[1] = __int_as_float(cs);
+        res[2] = __int_as_float(n_safe);
+        res[3] = qrow[pick];
+        res[4] = lds[kOffSqCand + 2 * (g * kSqMaxK + pick)];
+        res[5] = lds[kOffSqCand + 2 * (g * kSqMaxK + pick) + 1];
+    }
+}
+
+// The SQRL phase of one step: starts behind the fold of the policy's four outputs (head / obs of the tile's rows are in LDS
+// behind the barrier in here), ends with res[g] of every live row g behind a barrier.  Every thread takes part.
+__device__ __forceinline__ void sq_phase(float* lds, const EvArgs& a, int k, unsigned b, uint64_t ctr, bool alive, int tid,
+                                         int wave, int lane) {
+    const unsigned long long live = __ballot(alive);         // wave 0: bit t = row t; alive is false elsewhere
+    if (alive) lds[kOffSqRow + __popcll(live & ((1ULL << tid) - 1ULL))] = __int_as_float(tid);
+    if (tid == 0) lds[kOffSqMask] = __int_as_float(int(live));
+    __syncthreads();                              // the policy's fold is behind this barrier: act / xs / part are free
+    const unsigned m = __builtin_amdgcn_readfirstlane(__float_as_int(lds[kOffSqMask]));
+    const int nl = __popc(m), total = nl * k;
+    sq_candidates(lds, a, k, nl, b, ctr, tid);
+    __syncthreads();
+    // ---- scores: the flattened candidates in row tiles of 16, at most four per pass ----
+    const int nt = (total + 15) >> 4;
+#pragma unroll 1
+    for (int f0 = 0; f0 < total; f0 += rrl_tile::kRows) {
+        const int mr = nt - (f0 >> 4);
+        switch (mr) {
+            case 1: sq_pass<1>(lds, a.q, k, total, f0, tid, wave, lane); break;
+            case 2: sq_pass<2>(lds, a.q, k, total, f0, tid, wave, lane); break;
+            case 3: sq_pass<3>(lds, a.q, k, total, f0, tid, wave, lane); break;
+            default: sq_pass<4>(lds, a.q, k, total, f0, tid, wave, lane); break;
+        }
+    }
+    __syncthreads();                              // q of every candidate is in LDS
+    // ---- picks: wave w serves rows w and w + 8 ----
+#pragma unroll 1
+    for (int g = wave; g < kRows; g += kWaves)
+        if ((m >> g) & 1u) sq_pick(lds, a, k, g, (long long)b * kRows + g, ctr, lane);
+    __syncthreads();                              // res is out
+}
+
 // Workgroup b of the argument block's own grid: envs [16 b, 16 (b + 1)) through the whole rollout.  Thread tid < 16
 // owns env 16 b + tid: state and results in its registers, written once at the end.  Qs = QsOn: a gated live row executes
 // the argmin of its k candidates (qs_row) in the place of a recovery policy's action.  The body declares no local for that
 // form (the pick is read back from LDS where it is traced): with two more locals the NoQs instantiations kept their
-// instruction counts but not their register numbering.
+// instruction counts but not their register numbering.  Qs = SqOn: no gate; every live row executes the pick of sq_phase.
 template <class Env, class Qs = NoQs>
 __device__ __forceinline__ void rollout_tile(const EvArgs& a, const Env& env, unsigned b, float* lds,
-                                             const QsArgs* qsp = nullptr) {
+                                             const typename Qs::Args* qsp = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int R = kRows;
@@ -364,7 +596,10 @@ __device__ __forceinline__ void rollout_tile(const EvArgs& a, const Env& env, un
         const uint64_t ctr = tick + uint64_t(a.reset) + uint64_t(j);
 
         // ---- task action: the Gaussian policy's mean rows ----
-        run_stack<2, 2>(lds, a.p, 0, part, wave, lane);
+        if constexpr (Qs::sqrl)
+            run_stack<2, 4>(lds, a.p, 0, part, wave, lane);   // mean rows, then log_std rows
+        else
+            run_stack<2, 2>(lds, a.p, 0, part, wave, lane);
         float t0 = 0.f, t1 = 0.f;
         if (tid < R) {
             t0 = tanhf(fold_part(part, 0, tid, a.p.b3[0])) * a.scale[0] + a.bias[0];
@@ -374,7 +609,20 @@ __device__ __forceinline__ void rollout_tile(const EvArgs& a, const Env& env, un
         }
         float r0 = t0, r1 = t1, z0 = 0.f, z1 = 0.f, e0 = 0.f, e1 = 0.f;
         bool rec = false;
-        if (has_q) {
+        if constexpr (Qs::sqrl) {
+            // ---- SQRL: the head of every row, then candidates, scores and picks of the live ones ----
+            if (tid < R) {
+#pragma unroll
+                for (int o = 0; o < 4; ++o) lds[kOffSqHead + 4 * tid + o] = fold_part(part, o, tid, a.p.b3[o]);
+                lds[kOffSqObs + 2 * tid] = float(x);
+                lds[kOffSqObs + 2 * tid + 1] = float(y);
+            }
+            sq_phase(lds, a, qsp->k, b, ctr, alive, tid, wave, lane);
+            if (alive) {
+                r0 = lds[kOffSqRes + 8 * tid + 4];
+                r1 = lds[kOffSqRes + 8 * tid + 5];
+            }
+        } else if (has_q) {
             // ---- the gate: twin Q_risk on [obs | task action] ----
             __syncthreads();                                  // xs complete
 #pragma unroll 1
@@ -440,10 +688,11 @@ __device__ __forceinline__ void rollout_tile(const EvArgs& a, const Env& env, un
                 a.tr_real[2 * o] = r0;
                 a.tr_real[2 * o + 1] = r1;
             }
-            if (a.tr_z && has_q) {
-                a.tr_z[(long long)(2 * j) * a.n + row] = z0;
-                a.tr_z[(long long)(2 * j + 1) * a.n + row] = z1;
-            }
+            if constexpr (!Qs::sqrl)
+                if (a.tr_z && has_q) {
+                    a.tr_z[(long long)(2 * j) * a.n + row] = z0;
+                    a.tr_z[(long long)(2 * j + 1) * a.n + row] = z1;
+                }
             if (a.tr_eps && has_r) {
                 a.tr_eps[2 * o] = e0;
                 a.tr_eps[2 * o + 1] = e1;
@@ -452,6 +701,16 @@ __device__ __forceinline__ void rollout_tile(const EvArgs& a, const Env& env, un
                 // res[tid] of this step stands until the next step's candidate phase, behind that step's barriers
                 if (rec && qsp->tr_pick) qsp->tr_pick[o] = __float_as_int(lds[kOffQsRes + 4 * tid]);
                 if (rec && qsp->tr_q) qsp->tr_q[o] = lds[kOffQsRes + 4 * tid + 1];
+            }
+            if constexpr (Qs::sqrl) {
+                // head / res[tid] of this step stand until the next step's phase, behind that step's barriers
+                if (qsp->tr_head)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) qsp->tr_head[4 * o + c] = lds[kOffSqHead + 4 * tid + c];
+                if (qsp->tr_pick) qsp->tr_pick[o] = __float_as_int(lds[kOffSqRes + 8 * tid]);
+                if (qsp->tr_cstar) qsp->tr_cstar[o] = __float_as_int(lds[kOffSqRes + 8 * tid + 1]);
+                if (qsp->tr_nsafe) qsp->tr_nsafe[o] = __float_as_int(lds[kOffSqRes + 8 * tid + 2]);
+                if (qsp->tr_q) qsp->tr_q[o] = lds[kOffSqRes + 8 * tid + 3];
             }
             if (a.tr_reward) a.tr_reward[o] = rew;
             if (a.tr_flags) a.tr_flags[o] = uint8_t(1 | (int(dn) << 1) | (int(cons) << 2) | (int(sc) << 3) | (int(rec) << 4));
@@ -569,6 +828,49 @@ void eval_rollout_qs_maze_pack_kernel(const QsBlock* __restrict__ blocks, rrl_pa
     globalize(k.a);
     globalize(k.q);
     rollout_tile<MazeRoll, QsOn>(k.a, MazeRoll{k.horizon}, unsigned(local), lds, &k.q);
+}
+
+// The SQRL kernels: the same body with SqOn, on its own LDS carve-up (103.0 KB: one workgroup = two waves per SIMD on a CU)
+struct SqBlock {
+    EvArgs a;
+    SqOn s;
+    int horizon;
+};
+
+__device__ __forceinline__ void globalize(SqOn& s) { rrl_pack::to_global_all(s.tr_head, s.tr_pick, s.tr_cstar, s.tr_nsafe, s.tr_q); }
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void eval_rollout_sqrl_kernel(const SqBlock k) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    rollout_tile<NavRoll, SqOn>(k.a, NavRoll{}, blockIdx.x, lds, &k.s);
+}
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void eval_rollout_sqrl_maze_kernel(const SqBlock k) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    rollout_tile<MazeRoll, SqOn>(k.a, MazeRoll{k.horizon}, blockIdx.x, lds, &k.s);
+}
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void eval_rollout_sqrl_pack_kernel(const SqBlock* __restrict__ blocks, rrl_pack::Idx ix) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int s, local;
+    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
+    SqBlock k = blocks[s];
+    globalize(k.a);
+    globalize(k.s);
+    rollout_tile<NavRoll, SqOn>(k.a, NavRoll{}, unsigned(local), lds, &k.s);
+}
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void eval_rollout_sqrl_maze_pack_kernel(const SqBlock* __restrict__ blocks, rrl_pack::Idx ix) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int s, local;
+    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
+    SqBlock k = blocks[s];
+    globalize(k.a);
+    globalize(k.s);
+    rollout_tile<MazeRoll, SqOn>(k.a, MazeRoll{k.horizon}, unsigned(local), lds, &k.s);
 }
 
 template <size_t N>
@@ -714,6 +1016,63 @@ int launch_qs_solo(const rrl_eval_rollout_qs_t* p, void* stream) {
     return check_launch();
 }
 
+bool is_maze(const rrl_eval_rollout_sqrl_t* p) { return p && p->base.env_kind == RRL_ENV_MAZE; }
+
+// the checks of an SQRL descriptor, before any launch (rrl_hip.h): check_qs's shape
+int check_sqrl(const rrl_eval_rollout_sqrl_t* p) {
+    if (!p) return RRL_EINVAL;
+    const rrl_eval_rollout_t* e = &p->base;
+    const int rc = check_desc(e, is_maze(p));
+    if (rc == RRL_EINVAL) return rc;
+    const void* const rg[] = {e->rW1, e->rb1, e->rW2p, e->rb2, e->rW3, e->rb3, e->rscale, e->rbias, e->rlog_std};
+    if (!e->qW1 || given(rg) != 0) return RRL_EINVAL;        // (a Q_risk group given in part: check_desc)
+    if (rc != RRL_OK) return rc;
+    if (p->k < 1 || p->k > kSqMaxK || (long long)e->n * p->k >= (1LL << 32)) return RRL_ERANGE;
+    if (is_maze(p) && (p->horizon < 1 || p->horizon > kMaxHorizon)) return RRL_ERANGE;
+    return RRL_OK;
+}
+
+SqBlock sq_block_of(const rrl_eval_rollout_sqrl_t* p) {
+    SqBlock b{};
+    b.a = block_of(&p->base);
+    b.s.k = p->k;
+    b.s.tr_head = p->tr_head;
+    b.s.tr_pick = p->tr_pick;
+    b.s.tr_cstar = p->tr_cstar;
+    b.s.tr_nsafe = p->tr_nsafe;
+    b.s.tr_q = p->tr_q;
+    b.horizon = is_maze(p) ? p->horizon : 0;
+    return b;
+}
+
+struct SqSolo {
+    void (*kernel)(const SqBlock);
+    bool* granted;
+};
+SqSolo sq_solo(bool maze) {
+    static bool nav_set = false, maze_set = false;
+    return maze ? SqSolo{eval_rollout_sqrl_maze_kernel, &maze_set} : SqSolo{eval_rollout_sqrl_kernel, &nav_set};
+}
+struct SqPack {
+    void (*kernel)(const SqBlock*, rrl_pack::Idx);
+    bool* granted;
+};
+SqPack sq_pack(bool maze) {
+    static bool nav_set = false, maze_set = false;
+    return maze ? SqPack{eval_rollout_sqrl_maze_pack_kernel, &maze_set} : SqPack{eval_rollout_sqrl_pack_kernel, &nav_set};
+}
+
+int launch_sqrl_solo(const rrl_eval_rollout_sqrl_t* p, void* stream) {
+    const int rc = check_sqrl(p);
+    if (rc != RRL_OK) return rc;
+    const SqBlock b = sq_block_of(p);
+    const SqSolo k = sq_solo(is_maze(p));
+    const int rl = grant_lds(k.kernel, kSqLdsBytes, *k.granted);
+    if (rl != RRL_OK) return rl;
+    hipLaunchKernelGGL(k.kernel, dim3((unsigned)b.a.blocks), dim3(kThreads), kSqLdsBytes, (hipStream_t)stream, b);
+    return check_launch();
+}
+
 // The packed entries check every seed before anything is stored or launched, and an invalid field (RRL_EINVAL) wins over
 // a size out of range (RRL_ERANGE), whichever seed has it: RRL_EINVAL at once, else the last seed's failure, else RRL_OK
 template <class Check>
@@ -769,6 +1128,25 @@ int rrl_eval_rollout_qs_packed(int S, const rrl_eval_rollout_qs_t* args, void* s
     const QsPack k = qs_pack(maze);
     return launch_pack<QsBlock>(key, S, [&](int s, QsBlock& b) { return (b = qs_block_of(args + s)).a.blocks; }, k.kernel,
                                 kQsLdsBytes, k.granted, stream);
+}
+
+int rrl_eval_rollout_sqrl(const rrl_eval_rollout_sqrl_t* p, void* stream) { return launch_sqrl_solo(p, stream); }
+
+int rrl_eval_rollout_sqrl_packed(int S, const rrl_eval_rollout_sqrl_t* args, void* stream) {
+    if (!args) return RRL_EINVAL;
+    if (S <= 0 || S > rrl_pack::kMaxSeeds) return RRL_ERANGE;
+    const int worst = check_seeds(S, [&](int s) { return check_sqrl(args + s); });
+    if (worst == RRL_EINVAL) return worst;
+    const bool maze = is_maze(args);
+    for (int s = 1; s < S; ++s)
+        if (is_maze(args + s) != maze) return RRL_EINVAL;       // one env family per launch: the kernels differ
+    if (worst != RRL_OK) return worst;
+    if (S == 1) return launch_sqrl_solo(args, stream);
+    rrl_pack::Key key(rrl_pack::Site::EvalRolloutSqrl, S);
+    key.add(args, sizeof(rrl_eval_rollout_sqrl_t) * S);
+    const SqPack k = sq_pack(maze);
+    return launch_pack<SqBlock>(key, S, [&](int s, SqBlock& b) { return (b = sq_block_of(args + s)).a.blocks; }, k.kernel,
+                                kSqLdsBytes, k.granted, stream);
 }
 
 int rrl_eval_rollout(const rrl_eval_rollout_t* p, void* stream) { return launch_solo(p, stream); }

@@ -1079,7 +1079,8 @@ class Experiment:
         if rollout is not None:
             # RRL_FAST_EVAL=1: reset, the horizon + 1 steps and the per-env results in one launch (rrl_eval_rollout; Maze,
             # with RRL_FAST_EVAL_MAZE=1 as well: rrl_eval_rollout_maze, whose rows the env's horizon ends one step earlier;
-            # Q-sampling recovery, with RRL_FAST_EVAL_QSAMPLE=1 as well: rrl_eval_rollout_qs, candidates drawn in the launch)
+            # Q-sampling recovery, with RRL_FAST_EVAL_QSAMPLE=1 as well: rrl_eval_rollout_qs, candidates drawn in the launch;
+            # SQRL, with RRL_FAST_EVAL_SQRL=1 as well: rrl_eval_rollout_sqrl, candidates, scores and picks in the launch)
             rollout.launch(env._max_episode_steps + 1)
             return self._eval_result(rollout.stats(label))
         self.vector_rules.pop("evaluation", None)          # the rule records the path the LAST evaluation took
@@ -1111,14 +1112,15 @@ class Experiment:
     def eval_rollout(self):
         """The EvalRollout of this experiment's evaluation env when evaluation runs on the kernel
         (fast_update.eval_rollout_path), else None: the module code below."""
-        from .fast_update import EvalRollout, eval_qsample_line, eval_rollout_path
+        from .fast_update import EvalRollout, eval_qsample_line, eval_rollout_path, eval_sqrl_line
         cfg = self.exp_cfg
         if eval_rollout_path(cfg) != "hip" or getattr(self.agent, "fast", None) is None:
             return None
         if getattr(self, "_eval_rollout", None) is None:
-            # (eval_rollout_path said "hip" for the Q-sampling line: RRL_FAST_EVAL_QSAMPLE=1 -> rrl_eval_rollout_qs)
+            # (eval_rollout_path said "hip" for the Q-sampling line: RRL_FAST_EVAL_QSAMPLE=1 -> rrl_eval_rollout_qs; for the
+            # SQRL line: RRL_FAST_EVAL_SQRL=1 -> rrl_eval_rollout_sqrl)
             self._eval_rollout = EvalRollout(self.agent.fast, self.eval_env(), cfg.eps_safe, cfg.use_recovery,
-                                             qsample=eval_qsample_line(cfg))
+                                             qsample=eval_qsample_line(cfg), sqrl=eval_sqrl_line(cfg))
         self.vector_rules["evaluation"] = "hip"
         return self._eval_rollout
 

@@ -1236,17 +1236,33 @@ def eval_qsample_line(cfg):
             and not cfg.use_constraint_sampling)
 
 
+def fast_eval_sqrl_enabled():
+    """RRL_FAST_EVAL_SQRL=1, on top of RRL_FAST_EVAL=1: --use_constraint_sampling evaluates on rrl_eval_rollout_sqrl (opt-in;
+    eval_rollout_path)."""
+    return os.environ.get("RRL_FAST_EVAL_SQRL", "0") == "1"
+
+
+def eval_sqrl_line(cfg):
+    """The configuration whose evaluation is SAC._sqrl_action on every step: --use_constraint_sampling without a recovery
+    policy."""
+    return bool(cfg.use_constraint_sampling) and not cfg.use_recovery
+
+
 def eval_rollout_path(cfg):
     """Where Experiment.get_test_rollout_vectorized runs: "hip" (EvalRollout: one launch) under RRL_FAST_EVAL=1 on the fused
     path at hidden width 256, Navigation 1 / 2 -- or Maze with RRL_FAST_EVAL_MAZE=1 as well --, the lock-step loop, without
-    a recovery policy, with the model-free one, or -- with RRL_FAST_EVAL_QSAMPLE=1 as well, whatever RRL_FAST_QSAMPLE says --
-    with Q-sampling recovery; else "modules" (the loop's act() on the torch modules and the eager env), which SQRL, model-based
-    recovery and every other configuration keep."""
+    a recovery policy, with the model-free one, -- with RRL_FAST_EVAL_QSAMPLE=1 as well, whatever RRL_FAST_QSAMPLE says --
+    with Q-sampling recovery, or -- with RRL_FAST_EVAL_SQRL=1 as well, whatever RRL_FAST_SQRL says -- SQRL without a recovery
+    policy; else "modules" (the loop's act() on the torch modules and the eager env), which SQRL with a recovery policy,
+    model-based recovery and every other configuration keep."""
     envs = ("navigation1", "navigation2") + (("maze",) if fast_eval_maze_enabled() else ())
-    hip = (fast_eval_enabled() and fast_path_supported(cfg) and not getattr(cfg, "no_fast_path", False)
-           and int(cfg.hidden_size) == 256 and cfg.env_name in envs
-           and int(getattr(cfg, "num_envs", 1)) > 1 and not cfg.use_constraint_sampling
-           and (not cfg.use_recovery or bool(cfg.MF_recovery) or (fast_eval_qsample_enabled() and eval_qsample_line(cfg))))
+    common = (fast_eval_enabled() and fast_path_supported(cfg) and not getattr(cfg, "no_fast_path", False)
+              and int(cfg.hidden_size) == 256 and cfg.env_name in envs and int(getattr(cfg, "num_envs", 1)) > 1)
+    if cfg.use_constraint_sampling:
+        hip = common and fast_eval_sqrl_enabled() and eval_sqrl_line(cfg)
+    else:
+        hip = common and (not cfg.use_recovery or bool(cfg.MF_recovery)
+                          or (fast_eval_qsample_enabled() and eval_qsample_line(cfg)))
     return "hip" if hip else "modules"
 
 
@@ -1255,19 +1271,27 @@ class EvalRollout:
     weights of `fast`.  Owns the per-env result buffers and its OWN fragment-order copies of the three W2 matrices, re-made
     right before each launch: it depends neither on RRL_W2_FRAG nor on how many seeds a packed run keeps those copies for.
     qsample=True: the Q-sampling form (rrl_eval_rollout_qs) -- no recovery policy; a gated row executes the best of QSAMPLE_K
-    uniform candidates from the action box FastActor.qsample_box takes, drawn inside the launch."""
+    uniform candidates from the action box FastActor.qsample_box takes, drawn inside the launch.
+    sqrl=True: the SQRL form (rrl_eval_rollout_sqrl) -- no gate and no recovery policy; every live row executes the pick
+    among SQRL_K candidates of the task policy's head (its four stacked last-layer rows), scored by Q_risk inside the launch."""
 
     QSAMPLE_K = 1000                   # QRiskWrapper.select_action's candidate count
+    SQRL_K = 100                       # SAC._sqrl_action's
 
-    def __init__(self, fast, env, eps_safe, use_recovery, qsample=False):
+    def __init__(self, fast, env, eps_safe, use_recovery, qsample=False, sqrl=False):
         self.f, self.env, self.n = fast, env, env.num_envs
         self.eps_safe, self.use_recovery, self.qsample = float(eps_safe), bool(use_recovery), bool(qsample)
+        self.sqrl = bool(sqrl)
+        if self.sqrl and (self.use_recovery or self.qsample):
+            raise _lib.RRLError("rrl_eval_rollout_sqrl: SQRL without a recovery policy only")
         dev = fast.dev
         self.ret = torch.zeros(self.n, dtype=torch.float32, device=dev)
         self.success = torch.zeros(self.n, dtype=torch.uint8, device=dev)
         self.violation = torch.zeros(self.n, dtype=torch.uint8, device=dev)
         self.steps = torch.zeros(self.n, dtype=torch.int32, device=dev)
         self.nets = [fast.policy] + ([fast.qrisk] + ([] if self.qsample else [fast.recpolicy]) if self.use_recovery else [])
+        if self.sqrl:
+            self.nets = [fast.policy, fast.qrisk]
         if self.qsample:
             ac = fast.qr.ac_space
             self.box = tuple(torch.as_tensor(b, dtype=torch.float32, device=dev).contiguous() for b in (ac.low, ac.high))
@@ -1279,7 +1303,7 @@ class EvalRollout:
         the env's seed and device tick, the W2 copies made current.  `pos` [n, 2] f64 with reset=False: the start states;
         `trace` = {name: tensor} asks for trace buffers."""
         trace = dict(trace or {})
-        own = {name: trace.pop(name) for name in ("tr_pick", "tr_q") if name in trace}
+        own = {name: trace.pop(name) for name in ("tr_pick", "tr_q", "tr_head", "tr_cstar", "tr_nsafe") if name in trace}
         f, p = self.f, _lib.ptr
         for net, w2p in zip(self.nets, self.w2p):
             W2 = net.p["W2"]
@@ -1292,12 +1316,15 @@ class EvalRollout:
                                     seed=self.env.seed_value, counter=0, counter_dev=p(self.env.tick), ret=p(self.ret),
                                     success=p(self.success), violation=p(self.violation), steps=p(self.steps),
                                     **{name: p(t) for name, t in (trace or {}).items()})
-        if self.use_recovery:
+        if self.use_recovery or self.sqrl:
             Q = f.qrisk.p
             a.qW1, a.qb1, a.qW2p, a.qb2, a.qW3, a.qb3 = (p(Q["W1"]), p(Q["b1"]), p(self.w2p[1]), p(Q["b2"]), p(Q["W3"]),
                                                          p(Q["b3"]))
             a.eps_safe = self.eps_safe
-        if self.qsample:
+        if self.sqrl:
+            a = _lib.rrl_eval_rollout_sqrl_t(base=a, k=self.SQRL_K, horizon=int(self.env.horizon) if self.maze else 0,
+                                             **{name: p(t) for name, t in own.items()})
+        elif self.qsample:
             a = _lib.rrl_eval_rollout_qs_t(base=a, k=self.QSAMPLE_K, horizon=int(self.env.horizon) if self.maze else 0,
                                            lo=p(self.box[0]), hi=p(self.box[1]), **{name: p(t) for name, t in own.items()})
         elif self.use_recovery:
@@ -1315,6 +1342,9 @@ class EvalRollout:
 
     def launch(self, T, **kw):
         a = self.desc(T, **kw)
+        if self.sqrl:      # one entry for both env families, as the Q-sampling form
+            _lib.check(self.f.lib.rrl_eval_rollout_sqrl(C.byref(a), _lib.current_stream()), "rrl_eval_rollout_sqrl")
+            return
         if self.qsample:   # one entry for both env families (the Maze horizon rides in the descriptor)
             _lib.check(self.f.lib.rrl_eval_rollout_qs(C.byref(a), _lib.current_stream()), "rrl_eval_rollout_qs")
             return
@@ -1334,7 +1364,12 @@ class EvalRollout:
 def eval_rollouts_packed(rollouts, T):
     """The evaluations of several seeds (EvalRollout each) as ONE rrl_eval_rollout_packed launch (one env per packed run:
     rrl_eval_rollout_maze_packed with every seed's env horizon when that env is Maze; rrl_eval_rollout_qs_packed for the
-    Q-sampling form)."""
+    Q-sampling form, rrl_eval_rollout_sqrl_packed for the SQRL form)."""
+    if rollouts[0].sqrl:
+        args = (_lib.rrl_eval_rollout_sqrl_t * len(rollouts))(*[r.desc(T) for r in rollouts])
+        _lib.check(_lib.load().rrl_eval_rollout_sqrl_packed(len(rollouts), args, _lib.current_stream()),
+                   "rrl_eval_rollout_sqrl_packed")
+        return
     if rollouts[0].qsample:
         args = (_lib.rrl_eval_rollout_qs_t * len(rollouts))(*[r.desc(T) for r in rollouts])
         _lib.check(_lib.load().rrl_eval_rollout_qs_packed(len(rollouts), args, _lib.current_stream()),
