@@ -883,6 +883,8 @@ int rrl_ens_train_epoch_big(const rrl_ens_t* m, int n_seg, const rrl_adam_seg_t*
  *                                          the row tiles ceil(k / 16) are a template parameter of the kernel -- else RRL_EINVAL;
  *                                          n, weights, eps_safe, seed, tick, n_part, injected draws and the diagnostics that are
  *                                          asked for may differ by seed)
+ *   rrl_sqrl_act_f16x3_packed              rrl_sqrl_act_f16x3          (the same rules on the f16x3 kernels; every seed's W2p is its
+ *                                          rrl_w2_pack_f16x3 stream)
  * The Q-sampling recovery acting call (declared with its descriptors below):
  *   rrl_qsample_act_packed                 rrl_qsample_act / rrl_qsample_act_gated   (args[s], gates[s] or gates == NULL; the
  *                                          score kernel gives seed s its n[s] ceil(k[s] / 128) workgroups, the fold kernel one
@@ -982,6 +984,30 @@ int rrl_sqrl_act(const rrl_sqrl_act_t* a, void* stream);
  * seeds before anything is stored or launched; S outside 1 .. 16, args == NULL or seeds that differ in k: RRL_EINVAL; S == 1 is
  * rrl_sqrl_act(args). */
 int rrl_sqrl_act_packed(int S, const rrl_sqrl_act_t* args, void* stream);
+
+/* The same pass with layer 2 of the twin Q_risk in f16x3 (the planner's arithmetic, rrl_plan_cost_t.f16x3): the descriptor, the
+ * checks, their order and their codes are rrl_sqrl_act's; a->W2p names the rrl_w2_pack_f16x3 stream of the two heads instead of
+ * the rrl_w2_pack one.
+ * W2h = the G row-major [H, H] matrices W2 (out, in -- model.py's nn.Linear weights) in the order the K = 32 f16 MFMA's B operands
+ * consume them, every value w as hi = f16(w), lo = f16(w - hi) (lo unscaled; |w| > 65504 clamped first, as rrl_plan_pack does):
+ * per matrix g, column tile n and 32-wide block jp (n < H / 16, jp < H / 32) two float4 slots of 8 halves per lane,
+ * slot (n, 2 jp, lane) = hi[0..7] and slot (n, 2 jp + 1, lane) = lo[0..7] of W2[g][16 n + lane % 16][32 jp + 8 (lane / 16) + 0..7],
+ * i.e. the float4 lane `lane` of the wave that owns output columns 16 n .. 16 n + 15 needs sits at float4 index
+ * g H H / 4 + (n H / 16 + 2 jp + {0: hi, 1: lo}) 64 + lane.  G H H floats of storage, 16-byte aligned.  NULL pointer, misaligned W2h,
+ * G <= 0 or H not a positive multiple of 32: RRL_EINVAL.
+ * Precision contract of rrl_sqrl_act_f16x3 against rrl_sqrl_act on the same descriptor (W2p apart):
+ *   cand, logp, the candidate noise, the pick's uniform and the tick advance are rrl_sqrl_act's bits.
+ *   score: layer 1 (K = 4) is the exact f32 MFMA.  Its relu output v is held as hi = f16(v), lo = f16(v - hi); layer 2 sums, per
+ *          32-wide k block in ascending order, hi*lo, hi*hi, lo*hi on v_mfma_f32_16x16x32_f16 with f32 accumulators (lo*lo, 2^-22
+ *          of a product, is dropped); the folded last layer, z, q and the pick are rrl_sqrl_act's expressions.  z and q, and so
+ *          n_safe, cstar, pick and action where a decision is within that error of its threshold, differ from rrl_sqrl_act's:
+ *          |z - float64| stays within 4 x the error of the same chain evaluated in f32 (tests/test_sqrl_f16x3_gpu.py).
+ *   Activations above 65504 saturate to 65504; NaN stays NaN.
+ *   A candidate's z does not depend on k, on its row tile or on the pass it falls in. */
+int rrl_w2_pack_f16x3(int G, int H, const float* W2, float* W2h, void* stream);
+int rrl_sqrl_act_f16x3(const rrl_sqrl_act_t* a, void* stream);
+/* ... packed, by the rules of rrl_sqrl_act_packed (a launch site of its own: its plans are not rrl_sqrl_act_packed's) */
+int rrl_sqrl_act_f16x3_packed(int S, const rrl_sqrl_act_t* args, void* stream);
 
 /* --------------------------------------------------------------------------------------------
  * Q-sampling recovery.  Replaces QRiskWrapper.select_action (recovery_rl/qrisk.py:214-225: --Q_sampling_recovery draws 1000

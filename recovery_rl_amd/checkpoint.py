@@ -158,6 +158,7 @@ def loop_state(loop):
            "num_constraint_violations": loop.num_constraint_violations}
     if getattr(loop, "sqrl_hip", False):
         out["sqrl_tick"] = _cpu(loop.sqrl_actor().sqrl_tick)     # the rrl_sqrl_act acting pass's Philox tick (RRL_FAST_SQRL=1)
+        out["sqrl_scoring"] = "f16x3" if getattr(loop, "sqrl_f16x3", False) else "f32"     # ... and its arithmetic (RRL_SQRL_F16X3=1)
     if getattr(loop, "qsample_hip", False):
         out["qsample_tick"] = _cpu(loop.qsample_actor().qsample_tick)     # the rrl_qsample_act acting pass's tick (RRL_FAST_QSAMPLE=1)
     log = loop.episode_log
@@ -254,6 +255,12 @@ def load_experiment_state(exp, sd):
         raise ValueError("checkpoint and run disagree on SQRL's acting pass: the checkpoint was written with the %s path, this "
                          "run takes the %s path (RRL_FAST_SQRL=1 with RRL_FAST_BASELINES=1 selects the kernel)"
                          % (("kernel", "module") if "sqrl_tick" in sd["loop"] else ("module", "kernel")))
+    if "sqrl_tick" in sd["loop"]:
+        was = sd["loop"].get("sqrl_scoring", "f32")      # checkpoints from before the switch: f32
+        now = "f16x3" if getattr(exp.loop, "sqrl_f16x3", False) else "f32"
+        if was != now:
+            raise ValueError("checkpoint and run disagree on the scores of SQRL's acting pass: the checkpoint was written with "
+                             "%s scoring, this run takes %s scoring (RRL_SQRL_F16X3=1 selects f16x3)" % (was, now))
     if ("qsample_tick" in sd["loop"]) != bool(getattr(exp.loop, "qsample_hip", False)):
         raise ValueError("checkpoint and run disagree on the acting pass of --Q_sampling_recovery: the checkpoint was written "
                          "with the %s path, this run takes the %s path (RRL_FAST_QSAMPLE=1 selects the kernel)"

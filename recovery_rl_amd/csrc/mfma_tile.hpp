@@ -159,11 +159,11 @@ __device__ __forceinline__ void q_phase(float* lds, const Args& a, int wave, int
 
 // Row `row` of the pass behind q_phase: z[h] = b3[h] + the eight waves' partial sums in wave order, and q = max(sigmoid z0,
 // sigmoid z1) as torch.max does (NaN propagates).  Returned by value, with the callers' own expressions: the form in which
-// their kernels keep their instructions.
+// their kernels keep their instructions.  OffQpart: where qpart is, for a tile with a carve-up of its own (sqrl_f16x3_kernels.hip).
 struct TwinQ {
     float z[2], q;
 };
-template <class Args>
+template <class Args, int OffQpart = kOffQpart>
 __device__ __forceinline__ TwinQ twin_q(const float* lds, const Args& a, int row) {
     TwinQ t;
     float q[2];
@@ -171,7 +171,7 @@ __device__ __forceinline__ TwinQ twin_q(const float* lds, const Args& a, int row
     for (int h = 0; h < 2; ++h) {
         float v = a.b3[h];
 #pragma unroll
-        for (int w = 0; w < kWaves; ++w) v += lds[kOffQpart + (h * kWaves + w) * kRows + row];
+        for (int w = 0; w < kWaves; ++w) v += lds[OffQpart + (h * kWaves + w) * kRows + row];
         t.z[h] = v;
         q[h] = sigmoidf(v);
     }

@@ -78,6 +78,9 @@ class VectorLoop:
         from .fast_update import sqrl_acting_path
         self.sqrl_hip = bool(getattr(agent, "fast", None) is not None and sqrl_acting_path(cfg) == "hip"
                              and agent.fast.qrisk.w2p is not None)
+        # ... with layer 2 of its scores in f16x3 (RRL_SQRL_F16X3=1, read once, here; ignored where the pass is not the kernel's)
+        from .fast_update import sqrl_f16x3_enabled
+        self.sqrl_f16x3 = bool(self.sqrl_hip and sqrl_f16x3_enabled())
         # the acting pass of --Q_sampling_recovery on the rrl_qsample_act kernels (RRL_FAST_QSAMPLE=1, fast_update.qsample_acting_path)
         from .fast_update import qsample_acting_path
         self.qsample_hip = bool(getattr(agent, "fast", None) is not None and qsample_acting_path(cfg) == "hip"
@@ -153,6 +156,7 @@ class VectorLoop:
             from .fast_update import FastActor
             self._actor = FastActor(self.agent.fast, self.n)
             self._actor.sqrl_seed = int(self.cfg.seed) & 0xFFFFFFFFFFFFFFFF
+            self._actor.sqrl_f16x3 = self.sqrl_f16x3
         return self._actor
 
     def qsample_actor(self):
@@ -667,6 +671,8 @@ class Experiment:
         if exp_cfg.use_constraint_sampling:
             # which code draws, scores and picks SQRL's candidates in the training loop (RRL_FAST_SQRL=1: the kernel)
             self.vector_rules["sqrl_acting"] = "hip" if self.loop.sqrl_hip else "modules"
+            # ... and the arithmetic of the scores (RRL_SQRL_F16X3=1 on the kernel: layer 2 of Q_risk as three f16 products)
+            self.vector_rules["sqrl_scoring"] = "f16x3" if self.loop.sqrl_f16x3 else "f32"
         if exp_cfg.use_recovery and exp_cfg.Q_sampling_recovery and not exp_cfg.MF_recovery:
             # which code draws and scores the 1000 candidates of Q-sampling recovery in the training loop (RRL_FAST_QSAMPLE=1: the kernels)
             self.vector_rules["qsample_acting"] = "hip" if self.loop.qsample_hip else "modules"
@@ -728,6 +734,7 @@ class Experiment:
         self.vector_rules = {"demo_share": share if share > 0 else 0.0, "pinned_demonstrations": int(pinned),
                              **{k: self.vector_rules[k] for k in ("update_path", "replay_capacities", "cover_rows_limit",
                                                                    "buffers_cover_the_run", "plan_warm_start", "sqrl_acting",
+                                                                   "sqrl_scoring",
                                                                    "qsample_acting", "qsample_gate", "evaluation")
                                 if k in self.vector_rules}}
         if cfg.num_envs > 1:
@@ -1193,7 +1200,8 @@ def run_packed(exp_cfg, rank=0, world_size=1):
     acting pass one rrl_sqrl_act_packed launch -- so it needs that pass on the kernel (RRL_FAST_SQRL=1 with
     RRL_FAST_BASELINES=1, no recovery policy, --hidden_size 256: fast_update.sqrl_acting_path) and at most 8 seeds (the launch
     reads Q_risk's fragment-order W2 copy, which packed runs keep up to 8 seeds); every seed's run_stats.pkl then records
-    vector_rules["sqrl_acting"] == "hip".  Q-sampling recovery (--use_recovery --Q_sampling_recovery) packs under
+    vector_rules["sqrl_acting"] == "hip" (and "sqrl_scoring": with RRL_SQRL_F16X3=1 the stage is rrl_sqrl_act_f16x3_packed behind
+    the seeds' rrl_w2_pack_f16x3 calls, within the same limits).  Q-sampling recovery (--use_recovery --Q_sampling_recovery) packs under
     RRL_PACK_QSAMPLE=1 (opt-in): its acting pass is then a policy forward, a Q_risk forward and one rrl_qsample_act_packed stage
     that evaluates the recovery gate itself -- so it needs that pass on the kernels (RRL_FAST_QSAMPLE=1, --hidden_size 256, no
     --MF_recovery: fast_update.qsample_acting_path) and at most 8 seeds; run_stats.pkl records vector_rules["qsample_gate"] ==

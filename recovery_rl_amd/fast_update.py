@@ -948,6 +948,10 @@ class FastActor:
         # SQRL constraint sampling (act_sqrl): Philox seed (the loop sets its own) and the device tick {tick, ticket}
         self.sqrl_seed = int(getattr(fast.agent, "seed", 0)) & 0xFFFFFFFFFFFFFFFF
         self.sqrl_tick = torch.zeros(2, dtype=torch.int64, device=dev)
+        # RRL_SQRL_F16X3=1 (the loop sets it when it is built): act_sqrl scores on rrl_sqrl_act_f16x3, from a hi / lo stream of
+        # Q_risk's W2 this actor owns (sqrl_w2h, made at the first pass)
+        self.sqrl_f16x3 = False
+        self.sqrl_w2h = None
         # Q-sampling recovery (act_qsample): seed and device tick likewise, the action box on the device, the launch's scratch
         self.qsample_seed = self.sqrl_seed
         self.qsample_tick = torch.zeros(2, dtype=torch.int64, device=dev)
@@ -1068,6 +1072,19 @@ class FastActor:
                                 counter=0, counter_dev=p(self.sqrl_tick), counter_inc=1, eps_in=p(eps), u_in=p(u),
                                 action=p(self.task_action), **{name: p(t) for name, t in d.items()})
         self._sqrl_args = a              # keeps the argument block alive until the launch has been issued (and for profiles/)
+        if self.sqrl_f16x3:
+            # layer 2 of the scores in f16x3: the hi / lo fragment stream of the live W2, re-made in front of every launch (inside
+            # the captured graph; no optimiser launch keeps it current), then the f16x3 kernel on the same descriptor
+            if self.sqrl_w2h is None:
+                self.sqrl_w2h = torch.empty(P["W2"].numel(), dtype=torch.float32, device=f.dev)
+            a.W2p = p(self.sqrl_w2h)
+            W2 = P["W2"]
+            pack = (W2.shape[0], W2.shape[1], p(W2), p(self.sqrl_w2h))
+            record("call", f.lib.rrl_w2_pack_f16x3, pack, (W2, self.sqrl_w2h))
+            _lib.check(f.lib.rrl_w2_pack_f16x3(*pack, _lib.current_stream()), "rrl_w2_pack_f16x3")
+            record("sqrl_f16x3", a)
+            _lib.check(f.lib.rrl_sqrl_act_f16x3(C.byref(a), _lib.current_stream()), "rrl_sqrl_act_f16x3")
+            return self.task_action
         record("sqrl", a)
         _lib.check(f.lib.rrl_sqrl_act(C.byref(a), _lib.current_stream()), "rrl_sqrl_act")
         return self.task_action
@@ -1178,6 +1195,18 @@ def pack_sqrl_enabled():
     """RRL_PACK_SQRL=1: --seeds_per_gpu packs SQRL (--use_constraint_sampling), its acting pass as one rrl_sqrl_act_packed
     launch (opt-in; needs sqrl_acting_path(cfg) == "hip" and at most 8 seeds: experiment.run_packed)."""
     return os.environ.get("RRL_PACK_SQRL", "0") == "1"
+
+
+def sqrl_f16x3_enabled():
+    """RRL_SQRL_F16X3=1: the rrl_sqrl_act acting pass scores its candidates with layer 2 of Q_risk in f16x3
+    (rrl_sqrl_act_f16x3; opt-in).  Read once, when the loop is built; it matters only where sqrl_acting_path(cfg) == "hip"."""
+    return os.environ.get("RRL_SQRL_F16X3", "0") == "1"
+
+
+def sqrl_scoring(cfg):
+    """The arithmetic of the kernel acting pass's scores: "f16x3" under RRL_SQRL_F16X3=1 where sqrl_acting_path(cfg) == "hip",
+    else "f32" (the module path's too)."""
+    return "f16x3" if sqrl_f16x3_enabled() and sqrl_acting_path(cfg) == "hip" else "f32"
 
 
 def sqrl_acting_path(cfg):

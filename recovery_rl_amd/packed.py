@@ -33,8 +33,8 @@ class PackedLoop:
             raise ValueError("1 .. %d seeds per GPU" % self.MAX_SEEDS)
         self.loops = list(loops)
         self.S = len(loops)
-        # SQRL's packed acting launch (rrl_sqrl_act_packed) reads Q_risk's fragment-order W2 copy, which the nets give up
-        # beyond FRAG_MAX_SEEDS (below)
+        # SQRL's packed acting launch (rrl_sqrl_act_packed; its f16x3 form keeps the limit) reads Q_risk's fragment-order W2 copy,
+        # which the nets give up beyond FRAG_MAX_SEEDS (below)
         if self.S > self.FRAG_MAX_SEEDS and any(getattr(loop, "sqrl_hip", False) for loop in self.loops):
             raise ValueError("SQRL's constraint-sampling acting pass (rrl_sqrl_act_packed) packs at most %d seeds per GPU: it "
                              "reads the fragment-order W2 copy of Q_risk, which packed runs keep up to that many seeds only "
@@ -139,6 +139,11 @@ class PackedLoop:
                 # SQRL's constraint-sampling acting pass: every seed's stand-alone descriptor, one launch (one k for all seeds)
                 args = (_lib.rrl_sqrl_act_t * S)(*[op[1] for op in ops])
                 stages.append((self.lib.rrl_sqrl_act_packed, (S, args), ops))
+            elif kind == "sqrl_f16x3":
+                # ... with f16x3 scores (RRL_SQRL_F16X3=1): the same descriptors on the f16x3 kernels' packed entry; every seed's
+                # hi / lo stream of W2 is re-made by the per-seed "call" stage in front of it
+                args = (_lib.rrl_sqrl_act_t * S)(*[op[1] for op in ops])
+                stages.append((self.lib.rrl_sqrl_act_f16x3_packed, (S, args), ops))
             elif kind == "qsample":
                 # the Q-sampling recovery call with the gate inside it: every seed's descriptor and gate, one stage (k may
                 # differ by seed).  Without a gate (the mask form) the pass before it has launches the tape cannot pack
@@ -168,8 +173,8 @@ class PackedLoop:
         """Kernel launches of one packed iteration: a head + hidden backward stage is ONE launch when its stacks share a loss
         class and there are at most PAIR_MAX_SEEDS seeds (rrl_mlp_backward_pair_multi_packed: tile form up to two seeds,
         block form beyond), two otherwise; per-seed calls count once per seed; every other kind (the comparison algorithms'
-        "adam_duals", "penalty" and "heads", SQRL's acting launch "sqrl" and the Q-sampling recovery call "qsample" included) counts
-        as one entry."""
+        "adam_duals", "penalty" and "heads", SQRL's acting launch "sqrl" / "sqrl_f16x3" and the Q-sampling recovery call "qsample"
+        included) counts as one entry."""
         total = 0
         for fn, args, ops in self.stages:
             if ops[0][0] == "pair_bwd":
