@@ -891,6 +891,8 @@ int rrl_ens_train_epoch_big(const rrl_ens_t* m, int n_seg, const rrl_adam_seg_t*
  *                                          thread per env; the tick of seed s is advanced by the fold thread of ITS env 0; the
  *                                          chunk count is not a template parameter, so k may differ by seed, as may n, weights,
  *                                          eps_safe, seed, tick, injected candidates and the diagnostics that are asked for)
+ *   rrl_qsample_act_f16x3_packed           rrl_qsample_act_f16x3 / rrl_qsample_act_gated_f16x3   (the same rules on the f16x3 score
+ *                                          kernels; every seed's W2p is its rrl_w2_pack_f16x3 stream)
  * The evaluation rollout (declared with its descriptor below; outside the iteration, at the seeds' evaluation points):
  *   rrl_eval_rollout_packed                rrl_eval_rollout            (args[s]; seed s gets its ceil(n[s] / 16) workgroups and
  *                                          its tick is advanced by the last of them; n, T, env kind, weights, groups, seed, tick
@@ -1074,6 +1076,27 @@ int rrl_qsample_act_gated(const rrl_qsample_act_t* a, const rrl_qsample_gate_t* 
  * codes), all before anything is stored or launched; S outside 1 .. 16 or args == NULL: RRL_EINVAL; a seed with more than
  * INT32_MAX / 16 score workgroups: RRL_ERANGE; S == 1 is the stand-alone (or gated) call. */
 int rrl_qsample_act_packed(int S, const rrl_qsample_act_t* args, const rrl_qsample_gate_t* gates, void* stream);
+
+/* The same three calls with layer 2 of the twin Q_risk in f16x3 (the arithmetic of rrl_sqrl_act_f16x3 above): the descriptors,
+ * the checks, their order, their codes and the scratch size (rrl_qsample_scratch_floats) are rrl_qsample_act's; a->W2p names
+ * the stream rrl_w2_pack_f16x3(2, 256, W2, W2h) writes of the two heads' hidden weights instead of the rrl_w2_pack one, exactly
+ * as rrl_sqrl_act_f16x3 reads it.  Nothing keeps that stream current but the caller: the scores follow the stream, not W2.
+ * Precision contract against rrl_qsample_act / rrl_qsample_act_gated on the same descriptor (W2p apart):
+ *   cand, the candidate draws, the gate, recovery_out, task_out, the partials' layout, the fold and the tick advance are the
+ *   f32 call's bits; pick is the lowest-index argmin of the call's OWN q (NaN smallest) and action = cand[pick], by the f32
+ *   call's text.
+ *   score: layer 1 (K = 4) is the exact f32 MFMA.  Its relu output v is clamped at 65504 and held as hi = f16(v),
+ *          lo = f16(v - hi), lo unscaled; layer 2 sums, per 32-wide k block in ascending order, hi*lo, hi*hi, lo*hi
+ *          (activation * weight) on v_mfma_f32_16x16x32_f16 with f32 accumulators; lo*lo (2^-22 of a product) is dropped; the
+ *          folded last layer, z and q are rrl_qsample_act's expressions.  |z - float64| stays within 4 x the error of the same
+ *          chain evaluated in f32, so the picked candidate's float64 q is within half that bound of the float64 minimum
+ *          (sigmoid is 1/4-Lipschitz; tests/test_qsample_f16x3_gpu.py).
+ *   Activations above 65504 saturate to 65504; NaN stays NaN.
+ *   A candidate's z does not depend on k, on its chunk, its row tile or the pass it falls in. */
+int rrl_qsample_act_f16x3(const rrl_qsample_act_t* a, void* stream);
+int rrl_qsample_act_gated_f16x3(const rrl_qsample_act_t* a, const rrl_qsample_gate_t* g, void* stream);
+/* ... packed, by the rules of rrl_qsample_act_packed (a launch site of its own: its plans are not rrl_qsample_act_packed's) */
+int rrl_qsample_act_f16x3_packed(int S, const rrl_qsample_act_t* args, const rrl_qsample_gate_t* gates, void* stream);
 
 /* --------------------------------------------------------------------------------------------
  * Policy evaluation as ONE launch.  Replaces Experiment.get_test_rollout (recovery_rl/experiment.py:493-538: one

@@ -16,7 +16,7 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 HIP_SOURCES = ["nav_kernels.hip", "replay_kernels.hip", "maze_kernels.hip", "cem_kernels.hip",
                "mlp_kernels.hip", "mlp_fwd_kernels.hip", "update_kernels.hip", "log_kernels.hip", "plan_kernels.hip", "ens_train_kernels.hip",
                "ens_train_big_kernels.hip", "sqrl_kernels.hip", "qsample_kernels.hip", "eval_kernels.hip",
-               "sqrl_f16x3_kernels.hip"]
+               "sqrl_f16x3_kernels.hip", "qsample_f16x3_kernels.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-ffp-contract=off", "-Wall", "-Wno-unused-function",
                "-Wno-bitwise-instead-of-logical"]
@@ -58,6 +58,7 @@ EXPORTS = [
     "rrl_eval_rollout_qs", "rrl_eval_rollout_qs_packed",
     "rrl_eval_rollout_sqrl", "rrl_eval_rollout_sqrl_packed",
     "rrl_w2_pack_f16x3", "rrl_sqrl_act_f16x3", "rrl_sqrl_act_f16x3_packed",
+    "rrl_qsample_act_f16x3", "rrl_qsample_act_gated_f16x3", "rrl_qsample_act_f16x3_packed",
 ]
 
 class RRLError(RuntimeError):
@@ -438,6 +439,9 @@ def _declare(lib):
         "rrl_qsample_act": (ci, [C.POINTER(rrl_qsample_act_t), vp]),
         "rrl_qsample_act_gated": (ci, [C.POINTER(rrl_qsample_act_t), C.POINTER(rrl_qsample_gate_t), vp]),
         "rrl_qsample_act_packed": (ci, [ci, C.POINTER(rrl_qsample_act_t), C.POINTER(rrl_qsample_gate_t), vp]),
+        "rrl_qsample_act_f16x3": (ci, [C.POINTER(rrl_qsample_act_t), vp]),
+        "rrl_qsample_act_gated_f16x3": (ci, [C.POINTER(rrl_qsample_act_t), C.POINTER(rrl_qsample_gate_t), vp]),
+        "rrl_qsample_act_f16x3_packed": (ci, [ci, C.POINTER(rrl_qsample_act_t), C.POINTER(rrl_qsample_gate_t), vp]),
         "rrl_eval_rollout": (ci, [C.POINTER(rrl_eval_rollout_t), vp]),
         "rrl_eval_rollout_packed": (ci, [ci, C.POINTER(rrl_eval_rollout_t), vp]),
         "rrl_eval_rollout_maze": (ci, [C.POINTER(rrl_eval_rollout_t), ci, vp]),

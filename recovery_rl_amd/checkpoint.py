@@ -161,6 +161,7 @@ def loop_state(loop):
         out["sqrl_scoring"] = "f16x3" if getattr(loop, "sqrl_f16x3", False) else "f32"     # ... and its arithmetic (RRL_SQRL_F16X3=1)
     if getattr(loop, "qsample_hip", False):
         out["qsample_tick"] = _cpu(loop.qsample_actor().qsample_tick)     # the rrl_qsample_act acting pass's tick (RRL_FAST_QSAMPLE=1)
+        out["qsample_scoring"] = "f16x3" if getattr(loop, "qsample_f16x3", False) else "f32"     # ... and its arithmetic (RRL_QSAMPLE_F16X3=1)
     log = loop.episode_log
     if log is not None:
         out["episode_log"] = {"ep_len": _cpu(log.ep_len), "ep_ret": _cpu(log.ep_ret), "ep_viol": _cpu(log.ep_viol),
@@ -265,6 +266,13 @@ def load_experiment_state(exp, sd):
         raise ValueError("checkpoint and run disagree on the acting pass of --Q_sampling_recovery: the checkpoint was written "
                          "with the %s path, this run takes the %s path (RRL_FAST_QSAMPLE=1 selects the kernel)"
                          % (("kernel", "module") if "qsample_tick" in sd["loop"] else ("module", "kernel")))
+    if "qsample_tick" in sd["loop"]:
+        was = sd["loop"].get("qsample_scoring", "f32")      # checkpoints from before the switch: f32
+        now = "f16x3" if getattr(exp.loop, "qsample_f16x3", False) else "f32"
+        if was != now:
+            raise ValueError("checkpoint and run disagree on the scores of the acting pass of --Q_sampling_recovery: the checkpoint "
+                             "was written with %s scoring, this run takes %s scoring (RRL_QSAMPLE_F16X3=1 selects f16x3)"
+                             % (was, now))
     if ("mpc" in sd) != (exp.recovery_policy is not None):
         raise ValueError("checkpoint and run disagree on model-based recovery")
     load_agent_state(exp.agent, sd["agent"])

@@ -159,7 +159,7 @@ __device__ __forceinline__ void q_phase(float* lds, const Args& a, int wave, int
 
 // Row `row` of the pass behind q_phase: z[h] = b3[h] + the eight waves' partial sums in wave order, and q = max(sigmoid z0,
 // sigmoid z1) as torch.max does (NaN propagates).  Returned by value, with the callers' own expressions: the form in which
-// their kernels keep their instructions.  OffQpart: where qpart is, for a tile with a carve-up of its own (sqrl_f16x3_kernels.hip).
+// their kernels keep their instructions.  OffQpart: where qpart is, for a tile with a carve-up of its own (mfma_tile_f16x3.hpp).
 struct TwinQ {
     float z[2], q;
 };

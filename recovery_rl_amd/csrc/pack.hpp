@@ -196,7 +196,8 @@ inline Launch place_members(int S, const int* most) {
 // Every packed entry point, once: the first bytes of its keys (process-local values, free to renumber)
 enum class Site : int {
     HiddenBackward = 1, StackForward, HeadBackward, BackwardPair, Adam, AdamDuals, PolicyHeads, RcpoPenalty, ReplayDraw,
-    NavStep, MazeStep, SqrlAct, QsampleAct, EvalRollout, EvalRolloutMaze, EvalRolloutQs, EvalRolloutSqrl, SqrlActF16x3
+    NavStep, MazeStep, SqrlAct, QsampleAct, EvalRollout, EvalRolloutMaze, EvalRolloutQs, EvalRolloutSqrl, SqrlActF16x3,
+    QsampleActF16x3
 };
 
 // A packed launch = (device copy of the S argument blocks, block ranges, launch parameters), built once per distinct

@@ -89,6 +89,9 @@ class VectorLoop:
         # runs is what vector_rules records)
         from .fast_update import pack_qsample_enabled
         self.qsample_gated = bool(self.qsample_hip and pack_qsample_enabled())
+        # ... with layer 2 of its scores in f16x3 (RRL_QSAMPLE_F16X3=1, read once, here; ignored where the pass is not the kernels')
+        from .fast_update import qsample_f16x3_enabled
+        self.qsample_f16x3 = bool(self.qsample_hip and qsample_f16x3_enabled())
         self._graph_ahead = False
         # vectorisation rule 5: at N > 1 an env's CEM warm start does not survive its episode (MPC.forget_plans)
         self.forget_plans = bool(recovery_policy is not None and self.n > 1 and hasattr(recovery_policy, "forget_plans")
@@ -165,6 +168,7 @@ class VectorLoop:
             from .fast_update import FastActor
             self._actor = FastActor(self.agent.fast, self.n)
         self._actor.qsample_seed = int(self.cfg.seed) & 0xFFFFFFFFFFFFFFFF
+        self._actor.qsample_f16x3 = self.qsample_f16x3
         return self._actor
 
     def act(self, obs, random_actions=False, train=True):
@@ -676,6 +680,8 @@ class Experiment:
         if exp_cfg.use_recovery and exp_cfg.Q_sampling_recovery and not exp_cfg.MF_recovery:
             # which code draws and scores the 1000 candidates of Q-sampling recovery in the training loop (RRL_FAST_QSAMPLE=1: the kernels)
             self.vector_rules["qsample_acting"] = "hip" if self.loop.qsample_hip else "modules"
+            # ... and the arithmetic of the scores (RRL_QSAMPLE_F16X3=1 on the kernels: layer 2 of Q_risk as three f16 products)
+            self.vector_rules["qsample_scoring"] = "f16x3" if self.loop.qsample_f16x3 else "f32"
             if self.loop.qsample_gated:
                 # where the recovery gate of that pass is evaluated (RRL_PACK_QSAMPLE=1: inside the qsample call)
                 self.vector_rules["qsample_gate"] = "in_launch"
@@ -735,7 +741,8 @@ class Experiment:
                              **{k: self.vector_rules[k] for k in ("update_path", "replay_capacities", "cover_rows_limit",
                                                                    "buffers_cover_the_run", "plan_warm_start", "sqrl_acting",
                                                                    "sqrl_scoring",
-                                                                   "qsample_acting", "qsample_gate", "evaluation")
+                                                                   "qsample_acting", "qsample_scoring", "qsample_gate",
+                                                                   "evaluation")
                                 if k in self.vector_rules}}
         if cfg.num_envs > 1:
             print("Q_risk batch: %s (--demo_share; 0 = the reference's single uniform draw, replay_memory.py:54-72)"
@@ -1205,7 +1212,8 @@ def run_packed(exp_cfg, rank=0, world_size=1):
     RRL_PACK_QSAMPLE=1 (opt-in): its acting pass is then a policy forward, a Q_risk forward and one rrl_qsample_act_packed stage
     that evaluates the recovery gate itself -- so it needs that pass on the kernels (RRL_FAST_QSAMPLE=1, --hidden_size 256, no
     --MF_recovery: fast_update.qsample_acting_path) and at most 8 seeds; run_stats.pkl records vector_rules["qsample_gate"] ==
-    "in_launch".  Not packed: --use_constraint_sampling and --Q_sampling_recovery without their switches or outside those
+    "in_launch" (and "qsample_scoring": with RRL_QSAMPLE_F16X3=1 the stage is rrl_qsample_act_f16x3_packed behind the seeds'
+    rrl_w2_pack_f16x3 calls, within the same limits).  Not packed: --use_constraint_sampling and --Q_sampling_recovery without their switches or outside those
     limits (their acting passes are module code then), model-based recovery, --dp_mode env_shard, --resume /
     --checkpoint_every."""
     import copy

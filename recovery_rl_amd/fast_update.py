@@ -959,6 +959,10 @@ class FastActor:
         self.qsample_box = None if ac is None else tuple(
             torch.as_tensor(b, dtype=torch.float32, device=dev).contiguous() for b in (ac.low, ac.high))
         self._qsample_scratch = None
+        # RRL_QSAMPLE_F16X3=1 (the loop sets it when it is built): act_qsample scores on rrl_qsample_act_f16x3, from a hi / lo
+        # stream of Q_risk's W2 this actor owns (qsample_w2h, made at the first pass)
+        self.qsample_f16x3 = False
+        self.qsample_w2h = None
 
     # -- two of the three forwards of act(defer_select=True) as riders of the Q_risk update's launches -----------------------
     def ride_policy(self, obs):
@@ -1123,6 +1127,25 @@ class FastActor:
                                    cand_in=p(cand), scratch=p(self._qsample_scratch), action=p(self.real_action),
                                    **{name: p(t) for name, t in d.items()})
         self._qsample_args = a           # keeps the argument block alive until the launch has been issued (and for profiles/)
+        if self.qsample_f16x3:
+            # layer 2 of the scores in f16x3: the hi / lo fragment stream of the live W2, re-made in front of every launch (inside
+            # the captured graph; no optimiser launch keeps it current), then the f16x3 kernels on the same descriptor(s)
+            if self.qsample_w2h is None:
+                self.qsample_w2h = torch.empty(P["W2"].numel(), dtype=torch.float32, device=f.dev)
+            a.W2p = p(self.qsample_w2h)
+            W2 = P["W2"]
+            pack = (W2.shape[0], W2.shape[1], p(W2), p(self.qsample_w2h))
+            record("call", f.lib.rrl_w2_pack_f16x3, pack, (W2, self.qsample_w2h))
+            _lib.check(f.lib.rrl_w2_pack_f16x3(*pack, _lib.current_stream()), "rrl_w2_pack_f16x3")
+            if gated:
+                self._qsample_gate_args = gate
+                record("qsample_f16x3", a, gate)
+                _lib.check(f.lib.rrl_qsample_act_gated_f16x3(C.byref(a), C.byref(gate), _lib.current_stream()),
+                           "rrl_qsample_act_gated_f16x3")
+            else:
+                record("qsample_f16x3", a)
+                _lib.check(f.lib.rrl_qsample_act_f16x3(C.byref(a), _lib.current_stream()), "rrl_qsample_act_f16x3")
+            return self.task_action, self.real_action, self.recovery
         if gated:
             self._qsample_gate_args = gate
             record("qsample", a, gate)
@@ -1229,6 +1252,19 @@ def pack_qsample_enabled():
     (rrl_qsample_act_gated: three launches the tape records), and --seeds_per_gpu packs that line, its acting call as one
     rrl_qsample_act_packed stage (opt-in; needs qsample_acting_path(cfg) == "hip" and at most 8 seeds: experiment.run_packed)."""
     return os.environ.get("RRL_PACK_QSAMPLE", "0") == "1"
+
+
+def qsample_f16x3_enabled():
+    """RRL_QSAMPLE_F16X3=1: the rrl_qsample_act acting pass scores its candidates with layer 2 of Q_risk in f16x3
+    (rrl_qsample_act_f16x3; opt-in).  Read once, when the loop is built; it matters only where qsample_acting_path(cfg) == "hip"
+    (the random-action phase and evaluation keep their f32 code whatever it says)."""
+    return os.environ.get("RRL_QSAMPLE_F16X3", "0") == "1"
+
+
+def qsample_scoring(cfg):
+    """The arithmetic of the kernel acting pass's scores: "f16x3" under RRL_QSAMPLE_F16X3=1 where qsample_acting_path(cfg) ==
+    "hip", else "f32" (the module path's too)."""
+    return "f16x3" if qsample_f16x3_enabled() and qsample_acting_path(cfg) == "hip" else "f32"
 
 
 def qsample_acting_path(cfg):

@@ -144,14 +144,17 @@ class PackedLoop:
                 # hi / lo stream of W2 is re-made by the per-seed "call" stage in front of it
                 args = (_lib.rrl_sqrl_act_t * S)(*[op[1] for op in ops])
                 stages.append((self.lib.rrl_sqrl_act_f16x3_packed, (S, args), ops))
-            elif kind == "qsample":
+            elif kind in ("qsample", "qsample_f16x3"):
                 # the Q-sampling recovery call with the gate inside it: every seed's descriptor and gate, one stage (k may
-                # differ by seed).  Without a gate (the mask form) the pass before it has launches the tape cannot pack
+                # differ by seed).  Without a gate (the mask form) the pass before it has launches the tape cannot pack.
+                # "qsample_f16x3" (RRL_QSAMPLE_F16X3=1): the same descriptors on the f16x3 kernels' packed entry, within the same
+                # limits; every seed's hi / lo stream of W2 is re-made by the per-seed "call" stage in front of it
                 if any(len(op) < 3 for op in ops):
                     raise _lib.RRLError("launch kind 'qsample' packs with the gate in the launch only (RRL_PACK_QSAMPLE=1)")
                 args = (_lib.rrl_qsample_act_t * S)(*[op[1] for op in ops])
                 gates = (_lib.rrl_qsample_gate_t * S)(*[op[2] for op in ops])
-                stages.append((self.lib.rrl_qsample_act_packed, (S, args, gates), ops))
+                entry = self.lib.rrl_qsample_act_f16x3_packed if kind == "qsample_f16x3" else self.lib.rrl_qsample_act_packed
+                stages.append((entry, (S, args, gates), ops))
             elif kind == "step":
                 env_name, env_kind = ops[0][1], ops[0][2]
                 assert all(op[1] == env_name and op[2] == env_kind for op in ops), "one env per packed run"
@@ -173,7 +176,7 @@ class PackedLoop:
         """Kernel launches of one packed iteration: a head + hidden backward stage is ONE launch when its stacks share a loss
         class and there are at most PAIR_MAX_SEEDS seeds (rrl_mlp_backward_pair_multi_packed: tile form up to two seeds,
         block form beyond), two otherwise; per-seed calls count once per seed; every other kind (the comparison algorithms'
-        "adam_duals", "penalty" and "heads", SQRL's acting launch "sqrl" / "sqrl_f16x3" and the Q-sampling recovery call "qsample"
+        "adam_duals", "penalty" and "heads", SQRL's acting launch "sqrl" / "sqrl_f16x3" and the Q-sampling recovery call "qsample" / "qsample_f16x3"
         included) counts as one entry."""
         total = 0
         for fn, args, ops in self.stages:
