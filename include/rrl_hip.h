@@ -905,8 +905,13 @@ int rrl_ens_train_epoch_big(const rrl_ens_t* m, int n_seg, const rrl_adam_seg_t*
  *   rrl_eval_rollout_sqrl_packed           rrl_eval_rollout_sqrl       (args[s]; the same mapping on the SQRL kernels; n, T, k,
  *                                          env seed, tick, reset, weights and traces may differ by seed, and the kind within
  *                                          Navigation or the horizon within Maze; a Navigation + Maze mix: RRL_EINVAL)
+ *   rrl_eval_rollout_qs_f16x3_packed       rrl_eval_rollout_qs_f16x3   (args[s], qW2h[s]; the rules of rrl_eval_rollout_qs_packed
+ *                                          on the f16x3 kernels; the streams are part of the plan key)
+ *   rrl_eval_rollout_sqrl_f16x3_packed     rrl_eval_rollout_sqrl_f16x3 (args[s], qW2h[s]; the rules of
+ *                                          rrl_eval_rollout_sqrl_packed on the f16x3 kernels)
  * Every seed's arguments are checked before anything is stored or launched (the stand-alone entry's codes); a NULL array:
- * RRL_EINVAL; S outside 1 .. 16: RRL_EINVAL, except from rrl_eval_rollout[_maze|_qs|_sqrl]_packed, which return RRL_ERANGE for it.
+ * RRL_EINVAL; S outside 1 .. 16: RRL_EINVAL, except from rrl_eval_rollout[_maze|_qs|_sqrl][_f16x3]_packed, which return RRL_ERANGE
+ * for it.
  * S == 1 is the stand-alone launch.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
@@ -1257,6 +1262,31 @@ int rrl_eval_rollout_sqrl(const rrl_eval_rollout_sqrl_t* a, void* stream);
  * (RRL_EINVAL of any seed wins); args == NULL: RRL_EINVAL; S outside 1 .. 16: RRL_ERANGE; S == 1 is
  * rrl_eval_rollout_sqrl(args). */
 int rrl_eval_rollout_sqrl_packed(int S, const rrl_eval_rollout_sqrl_t* args, void* stream);
+
+/* The two rollouts above with the candidates scored in f16x3 (the arithmetic of rrl_sqrl_act_f16x3 / rrl_qsample_act_f16x3):
+ * the same descriptors on kernels of their own (Navigation 1 / 2 and Maze, solo and packed), so the kernels above keep their
+ * code.  qW2h is the stream rrl_w2_pack_f16x3(2, 256, W2, qW2h) writes of Q_risk's two heads; it rides beside the descriptor,
+ * as the Maze horizon does.  Nothing keeps that stream current but the caller: the scores follow the stream, not W2.
+ * base.qW2p keeps its meaning and its checks: the Q-sampling kernels read it for the gate, the SQRL kernels do not read it.
+ * Precision contract against the f32 entry on the same descriptor:
+ *   Start, task action, tr_head, gate (tr_z, flag bit 4: exact f32 on the 16-row stack from base.qW2p), candidates, logp,
+ *   draws, the results' fold and the tick are the f32 entry's expressions.
+ *   score: for a given state and step, the score of a candidate is the bits rrl_qsample_act_f16x3 / rrl_sqrl_act_f16x3 give
+ *          for the same obs, candidate and stream: layer 1 (K = 4) exact f32; its relu output v held as hi = f16(v),
+ *          lo = f16(v - hi); layer 2 sums, per 32-wide k block in ascending order, hi*lo, hi*hi, lo*hi on
+ *          v_mfma_f32_16x16x32_f16 with f32 accumulators (lo*lo dropped); the folded last layer, z and q are the f32
+ *          expressions.  Those bits are independent of k, row tile, pass and which other rows are live or gated.
+ *   pick:  the f32 entry's rule on those scores.  A pick that falls within the scoring error of a tie or of eps_safe may differ
+ *          from the f32 entry's; from that step on the episode may differ as well.
+ * LDS: the f16 planes are 1 KB larger than the f32 activations: 83.4 KB (Q-sampling) and 104.0 KB (SQRL), one workgroup per CU.
+ * Checks, their order and their codes are the f32 entry's on the same descriptor; in addition qW2h NULL or not 16-byte aligned
+ * is RRL_EINVAL (for the packed entries: the array, or any seed's pointer), which wins over RRL_ERANGE as every invalid field
+ * does.  The packed entries follow rrl_eval_rollout_qs_packed / rrl_eval_rollout_sqrl_packed (launch sites of their own, the
+ * qW2h pointers are part of the plan key, a Navigation / Maze mix is RRL_EINVAL, S == 1 is the solo entry). */
+int rrl_eval_rollout_qs_f16x3(const rrl_eval_rollout_qs_t* a, const float* qW2h, void* stream);
+int rrl_eval_rollout_qs_f16x3_packed(int S, const rrl_eval_rollout_qs_t* args, const float* const* qW2h, void* stream);
+int rrl_eval_rollout_sqrl_f16x3(const rrl_eval_rollout_sqrl_t* a, const float* qW2h, void* stream);
+int rrl_eval_rollout_sqrl_f16x3_packed(int S, const rrl_eval_rollout_sqrl_t* args, const float* const* qW2h, void* stream);
 
 #ifdef __cplusplus
 }

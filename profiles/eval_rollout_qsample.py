@@ -13,6 +13,9 @@ kernel's own trace: flag bit 4 over the live pairs) next to its times:
 ONE evaluation per sample, warm (one untimed call per path first), the paths alternated, the switch read per call.  Timed
 with device events around the call (the call ends with the host reading the three means, so the events span the whole
 evaluation) and with the wall clock between two device synchronisations; median, min and max of the repeats per path.
+--f16x3: ONLY the f16x3 leg (eval_rollout_sqrl.f16x3_leg) -- rrl_eval_rollout_qs_f16x3 against rrl_eval_rollout_qs of the same
+build, alternated over three rounds, with the gate closed (eps_safe 0.99), the fresh agent at 0.3 and every row gated
+(eps_safe -1); written into the "qsample" section of profiles/eval_rollout_f16x3.json.
 Not run by any test.  No number is claimed without the file it writes."""
 import argparse
 import json
@@ -108,7 +111,23 @@ if __name__ == "__main__":
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "eval_rollout_qsample.json"))
+    ap.add_argument("--f16x3", action="store_true")
     a = ap.parse_args()
+    if a.f16x3:
+        from eval_rollout_sqrl import f16x3_leg, write_f16x3
+        set_path("hip")
+        result = {"env": "navigation1", "envs": a.envs, "candidates": 1000, "device": torch.cuda.get_device_name(0), "rounds": 3,
+                  "timer": "device events around EvalRollout.launch + stats(), rrl_w2_pack calls included; both entries of one build"}
+        with tempfile.TemporaryDirectory() as tmp:
+            exp = Experiment(cfg(a.envs, os.path.join(tmp, "run")))
+            exp.loop.start()
+            for name, eps in (("gate_never_fires", 0.99), ("fresh", 0.3), ("every_row_gated", -1.0)):
+                set_eps(exp, eps)
+                exp._eval_rollout = None
+                result[name] = dict(f16x3_leg(exp, 3, a.repeats, qsample=True), eps_safe=eps, **gated_share(exp))
+                print(json.dumps({name: result[name]}), flush=True)
+        write_f16x3("qsample", result)
+        sys.exit(0)
     result = {"env": "navigation1", "envs": a.envs, "candidates": 1000, "device": torch.cuda.get_device_name(0),
               "timer": "device events around Experiment.get_test_rollout_vectorized; wall clock beside them"}
     with tempfile.TemporaryDirectory() as tmp:

@@ -15,7 +15,11 @@ with device events around the call (the call ends with the host reading the thre
 evaluation) and with the wall clock between two device synchronisations; median, min and max of the repeats per path.
 --packed: the launch of S evaluations side by side (rrl_eval_rollout_sqrl_packed through eval_rollouts_packed: S rollouts on
 the pretrained agent's weights, each with its own eval env and seed) against the S solo launches one after another, the same
-way.  Not run by any test.  No number is claimed without the file it writes."""
+way.
+--f16x3: ONLY the f16x3 leg -- rrl_eval_rollout_sqrl_f16x3 (EvalRollout(f16x3=True), its rrl_w2_pack_f16x3 call included)
+against rrl_eval_rollout_sqrl of the same build, on the same eval env from the same tick, the two entries alternated over
+three rounds of --repeats samples each; written into the "sqrl" section of profiles/eval_rollout_f16x3.json.
+Not run by any test.  No number is claimed without the file it writes."""
 import argparse
 import json
 import os
@@ -105,6 +109,43 @@ def measure(exp, repeats):
     return out
 
 
+def f16x3_leg(exp, rounds, repeats, **form):
+    """One evaluation (launch + the three means) on each of the two entries, alternated, `rounds` x `repeats` samples from the
+    same tick: per entry the spread over all samples and the median of every round; `form`: EvalRollout's qsample / sqrl"""
+    c, env = exp.exp_cfg, exp.eval_env()
+    T = env._max_episode_steps + 1
+    rollouts = {name: EvalRollout(exp.agent.fast, env, c.eps_safe, c.use_recovery, f16x3=name == "f16x3", **form)
+                for name in ("f32", "f16x3")}
+    tick0 = env.tick.clone()
+
+    def one(r):
+        env.tick.copy_(tick0)
+        r.launch(T)
+        return r.stats(0)
+
+    stats = {name: one(r) for name, r in rollouts.items()}          # warm, and what the two evaluations report
+    samples = {name: [[] for _ in range(rounds)] for name in rollouts}
+    for k in range(rounds):
+        for _ in range(repeats):
+            for name, r in rollouts.items():
+                samples[name][k].append(timed(lambda: one(r))[0])
+    env.tick.copy_(tick0)
+    out = {name: dict(spread([x for rnd in samples[name] for x in rnd]),
+                      round_medians_ms=[statistics.median(rnd) for rnd in samples[name]], stats=stats[name]) for name in rollouts}
+    out["ratio_of_medians"] = out["f32"]["median_ms"] / out["f16x3"]["median_ms"]
+    out["f16x3_faster_in_rounds"] = sum(a < b for a, b in zip(out["f16x3"]["round_medians_ms"], out["f32"]["round_medians_ms"]))
+    return out
+
+
+def write_f16x3(section, result, path=os.path.join(ROOT, "profiles", "eval_rollout_f16x3.json")):
+    """`result` as the file's `section`, beside what the other line's script wrote"""
+    whole = json.load(open(path)) if os.path.exists(path) else {}
+    whole[section] = result
+    whole["not_measured"] = ["packed launches", "Maze", "other k"]
+    with open(path, "w") as f:
+        json.dump(whole, f, indent=1)
+
+
 def measure_packed(exp, S, repeats):
     """S evaluations on the experiment's weights, each on an eval env of its own: one packed launch against S solo launches"""
     c = exp.exp_cfg
@@ -132,8 +173,27 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--packed", default="2,4")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "eval_rollout_sqrl.json"))
+    ap.add_argument("--f16x3", action="store_true")
     a = ap.parse_args()
     os.environ["RRL_FAST_BASELINES"] = "1"                # the fused update path of the SQRL line: the flat weights the kernel reads
+    if a.f16x3:
+        set_path("hip")
+        result = {"env": "navigation1", "envs": a.envs, "candidates": 100, "device": torch.cuda.get_device_name(0), "rounds": 3,
+                  "timer": "device events around EvalRollout.launch + stats(), rrl_w2_pack calls included; both entries of one build"}
+        with tempfile.TemporaryDirectory() as tmp:
+            exp = Experiment(cfg(a.envs, os.path.join(tmp, "run")))
+            exp.loop.start()
+            result["fresh"] = dict(f16x3_leg(exp, 3, a.repeats, sqrl=True), **shape_of_work(exp))
+            print(json.dumps({"fresh": result["fresh"]}), flush=True)
+            exp.pretrain_critic_recovery()
+            for _ in range(40):
+                exp.loop.vector_step(do_update=len(exp.memory) > exp.exp_cfg.batch_size,
+                                     random_actions=exp.exp_cfg.start_steps > exp.loop.total_numsteps,
+                                     online_qrisk=exp.online_qrisk_enabled())
+            result["pretrained_plus_40_iterations"] = dict(f16x3_leg(exp, 3, a.repeats, sqrl=True), **shape_of_work(exp))
+            print(json.dumps({"pretrained": result["pretrained_plus_40_iterations"]}), flush=True)
+        write_f16x3("sqrl", result)
+        sys.exit(0)
     result = {"env": "navigation1", "envs": a.envs, "candidates": 100, "device": torch.cuda.get_device_name(0),
               "timer": "device events around Experiment.get_test_rollout_vectorized; wall clock beside them"}
     with tempfile.TemporaryDirectory() as tmp:

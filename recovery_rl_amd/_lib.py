@@ -59,6 +59,8 @@ EXPORTS = [
     "rrl_eval_rollout_sqrl", "rrl_eval_rollout_sqrl_packed",
     "rrl_w2_pack_f16x3", "rrl_sqrl_act_f16x3", "rrl_sqrl_act_f16x3_packed",
     "rrl_qsample_act_f16x3", "rrl_qsample_act_gated_f16x3", "rrl_qsample_act_f16x3_packed",
+    "rrl_eval_rollout_qs_f16x3", "rrl_eval_rollout_qs_f16x3_packed",
+    "rrl_eval_rollout_sqrl_f16x3", "rrl_eval_rollout_sqrl_f16x3_packed",
 ]
 
 class RRLError(RuntimeError):
@@ -450,6 +452,10 @@ def _declare(lib):
         "rrl_eval_rollout_qs_packed": (ci, [ci, C.POINTER(rrl_eval_rollout_qs_t), vp]),
         "rrl_eval_rollout_sqrl": (ci, [C.POINTER(rrl_eval_rollout_sqrl_t), vp]),
         "rrl_eval_rollout_sqrl_packed": (ci, [ci, C.POINTER(rrl_eval_rollout_sqrl_t), vp]),
+        "rrl_eval_rollout_qs_f16x3": (ci, [C.POINTER(rrl_eval_rollout_qs_t), vp, vp]),
+        "rrl_eval_rollout_qs_f16x3_packed": (ci, [ci, C.POINTER(rrl_eval_rollout_qs_t), C.POINTER(vp), vp]),
+        "rrl_eval_rollout_sqrl_f16x3": (ci, [C.POINTER(rrl_eval_rollout_sqrl_t), vp, vp]),
+        "rrl_eval_rollout_sqrl_f16x3_packed": (ci, [ci, C.POINTER(rrl_eval_rollout_sqrl_t), C.POINTER(vp), vp]),
         "rrl_episode_log_append": (ci, [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(rrl_episode_log_t), vp]),
     }
     for name, (res, args) in sig.items():

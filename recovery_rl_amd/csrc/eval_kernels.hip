@@ -48,8 +48,16 @@
 // through a header: rrl_sqrl_act keeps its pick's weights in LDS and serves one env per workgroup, and its kernels keep
 // their code untouched this way; tests/test_eval_sqrl_gpu.py holds the two to the same bits.  The eight kernels
 // above are unchanged, instruction for instruction (profiles/eval_rollout_sqrl_fingerprint.txt).
+//
+// f16x3 scoring (rrl_eval_rollout_qs_f16x3 / rrl_eval_rollout_sqrl_f16x3 and their packed forms, eight more kernels): the
+// candidate phases are templates on the scoring tile -- TileF32 (mfma_tile.hpp) or TileF16x3 (mfma_tile_f16x3.hpp: layer 2 as
+// three v_mfma_f32_16x16x32_f16 products of hi / lo splits, the bits of rrl_qsample_act_f16x3 / rrl_sqrl_act_f16x3) -- and the
+// per-form LDS regions start at the tile's kOffOwn (QsLds / SqLds: 83.4 KB and 104.0 KB on TileF16x3, whose planes are 1 KB
+// larger).  The QsOnH / SqOnH traits carry the rrl_w2_pack_f16x3 stream; everything but the scores is the f32 forms' text, and
+// the twelve kernels above are unchanged, instruction for instruction (profiles/eval_f16x3_fingerprint.txt).
 #include "maze_device.hpp"
 #include "mfma_tile.hpp"
+#include "mfma_tile_f16x3.hpp"
 #include "pack.hpp"
 #include "rrl_device.hpp"
 #include "rrl_host.hpp"
@@ -80,18 +88,23 @@ constexpr int kOffPart = kOffXs + kRows * 4;                 // [2 outputs][8 wa
 constexpr int kLdsFloats = kOffPart + 2 * kWaves * kRows;
 constexpr int kLdsBytes = kLdsFloats * 4;                    // 17.5 KB
 
-// Q-sampling form: the 64-row tile's prefix (act / xs / qpart of mfma_tile.hpp) overlays the regions above -- they are dead
-// between the gate's fold and the next step's xs, which is where the candidate phase runs -- and its own regions follow
+// Q-sampling form: the 64-row tile's prefix (act / xs / qpart of the scoring tile: TileF32 = mfma_tile.hpp, TileF16x3 =
+// mfma_tile_f16x3.hpp) overlays the regions above -- they are dead between the gate's fold and the next step's xs, which is
+// where the candidate phase runs -- and its own regions follow at the tile's kOffOwn
 constexpr uint32_t kStreamEvalQs = RRL_STREAM_EVAL_QSAMPLE;
 constexpr int kMaxK = 1024;                                  // candidates per gated row
-constexpr int kOffQsCand = rrl_tile::kOffOwn;                // [1024][2] candidates of the row being served
-constexpr int kOffQsQ = kOffQsCand + kMaxK * 2;              // [1024] max(sigmoid z0, sigmoid z1)
-constexpr int kOffQsObs = kOffQsQ + kMaxK;                   // [16][2] float(pos) of the tile's rows
-constexpr int kOffQsRes = kOffQsObs + kRows * 2;             // [16][4] pick (int bits), its q, that candidate
-constexpr int kOffQsMask = kOffQsRes + kRows * 4;            // [1] the gate of the tile's rows, one bit each (int bits)
-constexpr int kQsLdsFloats = kOffQsMask + 4;
-constexpr int kQsLdsBytes = kQsLdsFloats * 4;                // 82.4 KB: one workgroup per CU
-static_assert(kLdsFloats <= rrl_tile::kOffXs, "the rollout's regions lie inside the 64-row tile's activation region");
+template <class Tile>
+struct QsLds {
+    static constexpr int kOffCand = Tile::kOffOwn;           // [1024][2] candidates of the row being served
+    static constexpr int kOffQ = kOffCand + kMaxK * 2;       // [1024] max(sigmoid z0, sigmoid z1)
+    static constexpr int kOffObs = kOffQ + kMaxK;            // [16][2] float(pos) of the tile's rows
+    static constexpr int kOffRes = kOffObs + kRows * 2;      // [16][4] pick (int bits), its q, that candidate
+    static constexpr int kOffMask = kOffRes + kRows * 4;     // [1] the gate of the tile's rows, one bit each (int bits)
+    static constexpr int kFloats = kOffMask + 4;
+    static constexpr int kBytes = kFloats * 4;               // TileF32: 82.4 KB, TileF16x3: 83.4 KB -- one workgroup per CU
+    static_assert(kLdsFloats <= Tile::kOffXs, "the rollout's regions lie inside the 64-row tile's activation region");
+    static_assert(kBytes <= 160 * 1024, "one workgroup's LDS");
+};
 
 // SQRL form: the same overlay; the policy stack's four-output partial sums ([4][8][16] at kOffPart) stay inside the 64-row
 // tile's activation region as well
@@ -99,18 +112,21 @@ constexpr uint32_t kStreamEvalSqrl = RRL_STREAM_EVAL_SQRL, kStreamEvalSqrlPick =
 constexpr int kSqMaxK = 128;                                 // candidates per live row
 constexpr float kLogSigMax = 2.f, kLogSigMin = -20.f, kEps = 1e-6f;   // model.py:14-16 (sqrl_kernels.hip's)
 constexpr float kHalfLog2Pi = 0.918938533204672742f;
-constexpr int kOffSqCand = rrl_tile::kOffOwn;                // [16][128][2] candidates of the tile's rows
-constexpr int kOffSqLogp = kOffSqCand + kRows * kSqMaxK * 2; // [16][128]
-constexpr int kOffSqQ = kOffSqLogp + kRows * kSqMaxK;        // [16][128] max(sigmoid z0, sigmoid z1)
-constexpr int kOffSqHead = kOffSqQ + kRows * kSqMaxK;        // [16][4] the policy's last-layer output
-constexpr int kOffSqObs = kOffSqHead + kRows * 4;            // [16][2] float(pos)
-constexpr int kOffSqRes = kOffSqObs + kRows * 2;             // [16][8] pick, cstar, n_safe (int bits), q, that candidate
-constexpr int kOffSqRow = kOffSqRes + kRows * 8;             // [16] tile row of the s-th live row (int bits)
-constexpr int kOffSqMask = kOffSqRow + kRows;                // [1] the live rows of the tile, one bit each (int bits)
-constexpr int kSqLdsFloats = kOffSqMask + 4;
-constexpr int kSqLdsBytes = kSqLdsFloats * 4;                // 103.0 KB: one workgroup per CU
-static_assert(kOffPart + 4 * kWaves * kRows <= rrl_tile::kOffXs, "four outputs' partial sums lie inside the activation region");
-static_assert(kSqLdsBytes <= 160 * 1024, "one workgroup's LDS");
+template <class Tile>
+struct SqLds {
+    static constexpr int kOffCand = Tile::kOffOwn;                  // [16][128][2] candidates of the tile's rows
+    static constexpr int kOffLogp = kOffCand + kRows * kSqMaxK * 2; // [16][128]
+    static constexpr int kOffQ = kOffLogp + kRows * kSqMaxK;        // [16][128] max(sigmoid z0, sigmoid z1)
+    static constexpr int kOffHead = kOffQ + kRows * kSqMaxK;        // [16][4] the policy's last-layer output
+    static constexpr int kOffObs = kOffHead + kRows * 4;            // [16][2] float(pos)
+    static constexpr int kOffRes = kOffObs + kRows * 2;             // [16][8] pick, cstar, n_safe (int bits), q, that candidate
+    static constexpr int kOffRow = kOffRes + kRows * 8;             // [16] tile row of the s-th live row (int bits)
+    static constexpr int kOffMask = kOffRow + kRows;                // [1] the live rows of the tile, one bit each (int bits)
+    static constexpr int kFloats = kOffMask + 4;
+    static constexpr int kBytes = kFloats * 4;               // TileF32: 103.0 KB, TileF16x3: 104.0 KB -- one workgroup per CU
+    static_assert(kOffPart + 4 * kWaves * kRows <= Tile::kOffXs, "four outputs' partial sums lie inside the activation region");
+    static_assert(kBytes <= 160 * 1024, "one workgroup's LDS");
+};
 
 struct Net {
     const float *W1, *b1, *W2p, *b2, *W3, *b3;
@@ -149,9 +165,37 @@ struct NoQs {
     static constexpr bool on = false, sqrl = false;
     using Args = QsArgs;
 };
+// the exact-f32 tile of mfma_tile.hpp, as the candidate phases name a tile (TileF16x3 is the other one)
+struct TileF32 {
+    static constexpr int kOffXs = rrl_tile::kOffXs, kOffOwn = rrl_tile::kOffOwn;
+    template <int MR>
+    static __device__ __forceinline__ void q_phase(float* lds, const Net& q, int wave, int lane) {
+        rrl_tile::q_phase<MR>(lds, q, wave, lane);
+    }
+    static __device__ __forceinline__ rrl_tile::TwinQ twin_q(const float* lds, const Net& q, int row) {
+        return rrl_tile::twin_q(lds, q, row);
+    }
+};
+using rrl_tile::TileF16x3;
 struct QsOn : QsArgs {
     static constexpr bool on = true, sqrl = false;
     using Args = QsArgs;
+    using Tile = TileF32;
+    // the Q_risk group the candidates are scored with
+    static __device__ __forceinline__ const Net& score_net(const EvArgs& a, const QsArgs&) { return a.q; }
+};
+// f16x3 scoring (rrl_eval_rollout_qs_f16x3): the gate keeps a.q with its rrl_w2_pack copy, the candidates' layer 2 reads
+// the rrl_w2_pack_f16x3 stream that rides beside the descriptor
+struct QsArgsH : QsArgs {
+    const float* w2h;
+};
+struct QsOnH : QsArgsH {
+    static constexpr bool on = true, sqrl = false;
+    using Args = QsArgsH;
+    using Tile = TileF16x3;
+    static __device__ __forceinline__ Net score_net(const EvArgs& a, const QsArgsH& s) {
+        return Net{a.q.W1, a.q.b1, s.w2h, a.q.b2, a.q.W3, a.q.b3};
+    }
 };
 // ... and the SQRL group (rrl_eval_rollout_sqrl_t's own fields)
 struct SqArgs {
@@ -163,6 +207,20 @@ struct SqArgs {
 struct SqOn : SqArgs {
     static constexpr bool on = false, sqrl = true;
     using Args = SqArgs;
+    using Tile = TileF32;
+    static __device__ __forceinline__ const Net& score_net(const EvArgs& a, const SqArgs&) { return a.q; }
+};
+// f16x3 scoring (rrl_eval_rollout_sqrl_f16x3): a.q.W2p is not read, layer 2 reads the rrl_w2_pack_f16x3 stream
+struct SqArgsH : SqArgs {
+    const float* w2h;
+};
+struct SqOnH : SqArgsH {
+    static constexpr bool on = false, sqrl = true;
+    using Args = SqArgsH;
+    using Tile = TileF16x3;
+    static __device__ __forceinline__ Net score_net(const EvArgs& a, const SqArgsH& s) {
+        return Net{a.q.W1, a.q.b1, s.w2h, a.q.b2, a.q.W3, a.q.b3};
+    }
 };
 
 // One 2-hidden-layer stack (head `head` of w) on the row tile in xs: inputs = the first DIN columns of xs, outputs = the
@@ -292,25 +350,29 @@ struct MazeRoll {
 
 // One pass of the candidate phase: candidates [base, base + 16 MR) of the k in LDS through the twin heads on [obs | candidate];
 // q of the live ones into LDS (score_pass of qsample_kernels.hip on this file's carve-up)
-template <int MR>
+template <int MR, class Tile>
 __device__ __forceinline__ void qs_pass(float* lds, const Net& q, int k, int base, float ox, float oy, int tid, int wave,
                                         int lane) {
+    constexpr int kOffQsCand = QsLds<Tile>::kOffCand, kOffQsQ = QsLds<Tile>::kOffQ;
     if (tid < rrl_tile::kRows) {
         const int r = base + tid;
         f32x4 x = {0.f, 0.f, 0.f, 0.f};           // rows past k: finite inputs, results never read
         if (r < k) x = f32x4{ox, oy, lds[kOffQsCand + 2 * r], lds[kOffQsCand + 2 * r + 1]};
-        *reinterpret_cast<f32x4*>(lds + rrl_tile::kOffXs + tid * 4) = x;
+        *reinterpret_cast<f32x4*>(lds + Tile::kOffXs + tid * 4) = x;
     }
     __syncthreads();
-    rrl_tile::q_phase<MR>(lds, q, wave, lane);
-    if (tid < rrl_tile::kRows && base + tid < k) lds[kOffQsQ + base + tid] = rrl_tile::twin_q(lds, q, tid).q;
+    Tile::template q_phase<MR>(lds, q, wave, lane);
+    if (tid < rrl_tile::kRows && base + tid < k) lds[kOffQsQ + base + tid] = Tile::twin_q(lds, q, tid).q;
     // xs and qpart are rewritten only behind the next pass's barriers
 }
 
-// The candidate phase of tile row g (env `grow`) at step counter ctr: k draws, their scores, the argmin -> res[g] in LDS.
-// Every thread of the workgroup takes part; starts behind a barrier and ends with one.
-__device__ __forceinline__ void qs_row(float* lds, const EvArgs& a, const QsArgs& s, int g, long long grow, uint64_t ctr,
-                                       int tid, int wave, int lane) {
+// The candidate phase of tile row g (env `grow`) at step counter ctr: k draws, their scores on Tile with the Q_risk group q,
+// the argmin -> res[g] in LDS.  Every thread of the workgroup takes part; starts behind a barrier and ends with one.
+template <class Tile>
+__device__ __forceinline__ void qs_row(float* lds, const EvArgs& a, const Net& q, const QsArgs& s, int g, long long grow,
+                                       uint64_t ctr, int tid, int wave, int lane) {
+    constexpr int kOffQsCand = QsLds<Tile>::kOffCand, kOffQsQ = QsLds<Tile>::kOffQ, kOffQsObs = QsLds<Tile>::kOffObs,
+                  kOffQsRes = QsLds<Tile>::kOffRes;
     const int k = s.k;
     // ---- candidates: a_j = float(lo_j + (hi_j - lo_j) u_j) in double, u = the open-unit pair of the row's 128 bits ----
 #pragma unroll 1
@@ -332,10 +394,10 @@ __device__ __forceinline__ void qs_row(float* lds, const EvArgs& a, const QsArgs
     for (int base = 0; base < k; base += rrl_tile::kRows) {
         const int mr = nt - (base >> 4);
         switch (mr) {
-            case 1: qs_pass<1>(lds, a.q, k, base, ox, oy, tid, wave, lane); break;
-            case 2: qs_pass<2>(lds, a.q, k, base, ox, oy, tid, wave, lane); break;
-            case 3: qs_pass<3>(lds, a.q, k, base, ox, oy, tid, wave, lane); break;
-            default: qs_pass<4>(lds, a.q, k, base, ox, oy, tid, wave, lane); break;
+            case 1: qs_pass<1, Tile>(lds, q, k, base, ox, oy, tid, wave, lane); break;
+            case 2: qs_pass<2, Tile>(lds, q, k, base, ox, oy, tid, wave, lane); break;
+            case 3: qs_pass<3, Tile>(lds, q, k, base, ox, oy, tid, wave, lane); break;
+            default: qs_pass<4, Tile>(lds, q, k, base, ox, oy, tid, wave, lane); break;
         }
     }
     __syncthreads();                              // q of every candidate is in LDS
@@ -378,7 +440,10 @@ __device__ __forceinline__ void qs_row(float* lds, const EvArgs& a, const QsArgs
 
 // Candidates of the `nl` live rows, flattened: f = slot k + c, slot-th live row g = rowof[slot].  a_c and logp_c are
 // rrl_sqrl_act's tanh-Gaussian head (gauss_head_fwd_row of update_kernels.hip), in the same expression order.
+template <class Tile>
 __device__ __forceinline__ void sq_candidates(float* lds, const EvArgs& a, int k, int nl, unsigned b, uint64_t ctr, int tid) {
+    constexpr int kOffSqCand = SqLds<Tile>::kOffCand, kOffSqLogp = SqLds<Tile>::kOffLogp, kOffSqHead = SqLds<Tile>::kOffHead,
+                  kOffSqRow = SqLds<Tile>::kOffRow;
     const int total = nl * k;
 #pragma unroll 1
     for (int f = tid; f < total; f += kThreads) {
@@ -406,8 +471,10 @@ __device__ __forceinline__ void sq_candidates(float* lds, const EvArgs& a, int k
 }
 
 // One pass: flattened candidates [f0, f0 + 16 MR) through the twin heads, every row with its own obs; q of the live ones
-template <int MR>
+template <int MR, class Tile>
 __device__ __forceinline__ void sq_pass(float* lds, const Net& q, int k, int total, int f0, int tid, int wave, int lane) {
+    constexpr int kOffSqCand = SqLds<Tile>::kOffCand, kOffSqQ = SqLds<Tile>::kOffQ, kOffSqObs = SqLds<Tile>::kOffObs,
+                  kOffSqRow = SqLds<Tile>::kOffRow;
     int qi = -1;
     if (tid < rrl_tile::kRows) {
         const int f = f0 + tid;
@@ -418,11 +485,11 @@ __device__ __forceinline__ void sq_pass(float* lds, const Net& q, int k, int tot
             qi = g * kSqMaxK + c;
             x = f32x4{lds[kOffSqObs + 2 * g], lds[kOffSqObs + 2 * g + 1], lds[kOffSqCand + 2 * qi], lds[kOffSqCand + 2 * qi + 1]};
         }
-        *reinterpret_cast<f32x4*>(lds + rrl_tile::kOffXs + tid * 4) = x;
+        *reinterpret_cast<f32x4*>(lds + Tile::kOffXs + tid * 4) = x;
     }
     __syncthreads();
-    rrl_tile::q_phase<MR>(lds, q, wave, lane);
-    if (qi >= 0) lds[kOffSqQ + qi] = rrl_tile::twin_q(lds, q, tid).q;
+    Tile::template q_phase<MR>(lds, q, wave, lane);
+    if (qi >= 0) lds[kOffSqQ + qi] = Tile::twin_q(lds, q, tid).q;
     // xs and qpart are rewritten only behind the next pass's barriers
 }
 
@@ -435,7 +502,10 @@ __device__ __forceinline__ double lane_double(double v, int l) {
 // The pick of tile row g (env `grow`) by ONE wave (sac.py:153-158; the position in the SAFE list is applied to the FULL list,
 // as the reference does): rrl_sqrl_act's, with the double weights in registers (lane l holds candidates l and l + 64) read in
 // ascending candidate order -- the same sums.  Leaves res[g].
+template <class Tile>
 __device__ __forceinline__ void sq_pick(float* lds, const EvArgs& a, int k, int g, long long grow, uint64_t ctr, int lane) {
+    constexpr int kOffSqCand = SqLds<Tile>::kOffCand, kOffSqLogp = SqLds<Tile>::kOffLogp, kOffSqQ = SqLds<Tile>::kOffQ,
+                  kOffSqRes = SqLds<Tile>::kOffRes;
     const float* qrow = lds + kOffSqQ + g * kSqMaxK;
     const float* lprow = lds + kOffSqLogp + g * kSqMaxK;
     float qv[2], lpv[2];
@@ -527,16 +597,19 @@ __device__ __forceinline__ void sq_pick(float* lds, const EvArgs& a, int k, int 
 }
 
 // The SQRL phase of one step: starts behind the fold of the policy's four outputs (head / obs of the tile's rows are in LDS
-// behind the barrier in here), ends with res[g] of every live row g behind a barrier.  Every thread takes part.
-__device__ __forceinline__ void sq_phase(float* lds, const EvArgs& a, int k, unsigned b, uint64_t ctr, bool alive, int tid,
-                                         int wave, int lane) {
+// behind the barrier in here), ends with res[g] of every live row g behind a barrier.  Every thread takes part.  The scores
+// come from Tile with the Q_risk group q.
+template <class Tile>
+__device__ __forceinline__ void sq_phase(float* lds, const EvArgs& a, const Net& q, int k, unsigned b, uint64_t ctr, bool alive,
+                                         int tid, int wave, int lane) {
+    constexpr int kOffSqRow = SqLds<Tile>::kOffRow, kOffSqMask = SqLds<Tile>::kOffMask;
     const unsigned long long live = __ballot(alive);         // wave 0: bit t = row t; alive is false elsewhere
     if (alive) lds[kOffSqRow + __popcll(live & ((1ULL << tid) - 1ULL))] = __int_as_float(tid);
     if (tid == 0) lds[kOffSqMask] = __int_as_float(int(live));
     __syncthreads();                              // the policy's fold is behind this barrier: act / xs / part are free
     const unsigned m = __builtin_amdgcn_readfirstlane(__float_as_int(lds[kOffSqMask]));
     const int nl = __popc(m), total = nl * k;
-    sq_candidates(lds, a, k, nl, b, ctr, tid);
+    sq_candidates<Tile>(lds, a, k, nl, b, ctr, tid);
     __syncthreads();
     // ---- scores: the flattened candidates in row tiles of 16, at most four per pass ----
     const int nt = (total + 15) >> 4;
@@ -544,17 +617,17 @@ __device__ __forceinline__ void sq_phase(float* lds, const EvArgs& a, int k, uns
     for (int f0 = 0; f0 < total; f0 += rrl_tile::kRows) {
         const int mr = nt - (f0 >> 4);
         switch (mr) {
-            case 1: sq_pass<1>(lds, a.q, k, total, f0, tid, wave, lane); break;
-            case 2: sq_pass<2>(lds, a.q, k, total, f0, tid, wave, lane); break;
-            case 3: sq_pass<3>(lds, a.q, k, total, f0, tid, wave, lane); break;
-            default: sq_pass<4>(lds, a.q, k, total, f0, tid, wave, lane); break;
+            case 1: sq_pass<1, Tile>(lds, q, k, total, f0, tid, wave, lane); break;
+            case 2: sq_pass<2, Tile>(lds, q, k, total, f0, tid, wave, lane); break;
+            case 3: sq_pass<3, Tile>(lds, q, k, total, f0, tid, wave, lane); break;
+            default: sq_pass<4, Tile>(lds, q, k, total, f0, tid, wave, lane); break;
         }
     }
     __syncthreads();                              // q of every candidate is in LDS
     // ---- picks: wave w serves rows w and w + 8 ----
 #pragma unroll 1
     for (int g = wave; g < kRows; g += kWaves)
-        if ((m >> g) & 1u) sq_pick(lds, a, k, g, (long long)b * kRows + g, ctr, lane);
+        if ((m >> g) & 1u) sq_pick<Tile>(lds, a, k, g, (long long)b * kRows + g, ctr, lane);
     __syncthreads();                              // res is out
 }
 
@@ -611,16 +684,17 @@ __device__ __forceinline__ void rollout_tile(const EvArgs& a, const Env& env, un
         bool rec = false;
         if constexpr (Qs::sqrl) {
             // ---- SQRL: the head of every row, then candidates, scores and picks of the live ones ----
+            using L = SqLds<typename Qs::Tile>;
             if (tid < R) {
 #pragma unroll
-                for (int o = 0; o < 4; ++o) lds[kOffSqHead + 4 * tid + o] = fold_part(part, o, tid, a.p.b3[o]);
-                lds[kOffSqObs + 2 * tid] = float(x);
-                lds[kOffSqObs + 2 * tid + 1] = float(y);
+                for (int o = 0; o < 4; ++o) lds[L::kOffHead + 4 * tid + o] = fold_part(part, o, tid, a.p.b3[o]);
+                lds[L::kOffObs + 2 * tid] = float(x);
+                lds[L::kOffObs + 2 * tid + 1] = float(y);
             }
-            sq_phase(lds, a, qsp->k, b, ctr, alive, tid, wave, lane);
+            sq_phase<typename Qs::Tile>(lds, a, Qs::score_net(a, *qsp), qsp->k, b, ctr, alive, tid, wave, lane);
             if (alive) {
-                r0 = lds[kOffSqRes + 8 * tid + 4];
-                r1 = lds[kOffSqRes + 8 * tid + 5];
+                r0 = lds[L::kOffRes + 8 * tid + 4];
+                r1 = lds[L::kOffRes + 8 * tid + 5];
             }
         } else if (has_q) {
             // ---- the gate: twin Q_risk on [obs | task action] ----
@@ -649,23 +723,24 @@ __device__ __forceinline__ void rollout_tile(const EvArgs& a, const Env& env, un
             }
             if constexpr (Qs::on) {
                 // ---- Q-sampling: the gated live rows of the tile, one after another in ascending row order ----
+                using L = QsLds<typename Qs::Tile>;
                 if (tid < R) {
-                    lds[kOffQsObs + 2 * tid] = float(x);
-                    lds[kOffQsObs + 2 * tid + 1] = float(y);
+                    lds[L::kOffObs + 2 * tid] = float(x);
+                    lds[L::kOffObs + 2 * tid + 1] = float(y);
                 }
                 const unsigned long long fired = __ballot(rec);      // wave 0: bit t = row t; rec is false elsewhere
-                if (tid == 0) lds[kOffQsMask] = __int_as_float(int(fired));
+                if (tid == 0) lds[L::kOffMask] = __int_as_float(int(fired));
                 __syncthreads();                              // the gate's fold is behind this barrier: act / xs / part are free
-                unsigned m = __builtin_amdgcn_readfirstlane(__float_as_int(lds[kOffQsMask]));
+                unsigned m = __builtin_amdgcn_readfirstlane(__float_as_int(lds[L::kOffMask]));
 #pragma unroll 1
                 while (m) {                                   // workgroup-uniform; no gated row: the phase is skipped
                     const int g = __builtin_ctz(m);
                     m &= m - 1;
-                    qs_row(lds, a, *qsp, g, (long long)b * R + g, ctr, tid, wave, lane);
+                    qs_row<typename Qs::Tile>(lds, a, Qs::score_net(a, *qsp), *qsp, g, (long long)b * R + g, ctr, tid, wave, lane);
                 }
                 if (rec) {
-                    r0 = lds[kOffQsRes + 4 * tid + 2];
-                    r1 = lds[kOffQsRes + 4 * tid + 3];
+                    r0 = lds[L::kOffRes + 4 * tid + 2];
+                    r1 = lds[L::kOffRes + 4 * tid + 3];
                 }
             }
         }
@@ -699,18 +774,20 @@ __device__ __forceinline__ void rollout_tile(const EvArgs& a, const Env& env, un
             }
             if constexpr (Qs::on) {
                 // res[tid] of this step stands until the next step's candidate phase, behind that step's barriers
-                if (rec && qsp->tr_pick) qsp->tr_pick[o] = __float_as_int(lds[kOffQsRes + 4 * tid]);
-                if (rec && qsp->tr_q) qsp->tr_q[o] = lds[kOffQsRes + 4 * tid + 1];
+                using L = QsLds<typename Qs::Tile>;
+                if (rec && qsp->tr_pick) qsp->tr_pick[o] = __float_as_int(lds[L::kOffRes + 4 * tid]);
+                if (rec && qsp->tr_q) qsp->tr_q[o] = lds[L::kOffRes + 4 * tid + 1];
             }
             if constexpr (Qs::sqrl) {
                 // head / res[tid] of this step stand until the next step's phase, behind that step's barriers
+                using L = SqLds<typename Qs::Tile>;
                 if (qsp->tr_head)
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) qsp->tr_head[4 * o + c] = lds[kOffSqHead + 4 * tid + c];
-                if (qsp->tr_pick) qsp->tr_pick[o] = __float_as_int(lds[kOffSqRes + 8 * tid]);
-                if (qsp->tr_cstar) qsp->tr_cstar[o] = __float_as_int(lds[kOffSqRes + 8 * tid + 1]);
-                if (qsp->tr_nsafe) qsp->tr_nsafe[o] = __float_as_int(lds[kOffSqRes + 8 * tid + 2]);
-                if (qsp->tr_q) qsp->tr_q[o] = lds[kOffSqRes + 8 * tid + 3];
+                    for (int c = 0; c < 4; ++c) qsp->tr_head[4 * o + c] = lds[L::kOffHead + 4 * tid + c];
+                if (qsp->tr_pick) qsp->tr_pick[o] = __float_as_int(lds[L::kOffRes + 8 * tid]);
+                if (qsp->tr_cstar) qsp->tr_cstar[o] = __float_as_int(lds[L::kOffRes + 8 * tid + 1]);
+                if (qsp->tr_nsafe) qsp->tr_nsafe[o] = __float_as_int(lds[L::kOffRes + 8 * tid + 2]);
+                if (qsp->tr_q) qsp->tr_q[o] = lds[L::kOffRes + 8 * tid + 3];
             }
             if (a.tr_reward) a.tr_reward[o] = rew;
             if (a.tr_flags) a.tr_flags[o] = uint8_t(1 | (int(dn) << 1) | (int(cons) << 2) | (int(sc) << 3) | (int(rec) << 4));
@@ -873,6 +950,98 @@ void eval_rollout_sqrl_maze_pack_kernel(const SqBlock* __restrict__ blocks, rrl_
     rollout_tile<MazeRoll, SqOn>(k.a, MazeRoll{k.horizon}, unsigned(local), lds, &k.s);
 }
 
+// The f16x3 kernels (rrl_eval_rollout_qs_f16x3 / rrl_eval_rollout_sqrl_f16x3 and their packed forms): the eight kernels above
+// with the candidates scored on TileF16x3 -- layer 2 of the twin Q_risk as three v_mfma_f32_16x16x32_f16 products of hi / lo
+// splits, the bits of rrl_qsample_act_f16x3 / rrl_sqrl_act_f16x3.  Start, policy stack, gate (exact f32 on the 16-row stack,
+// from the rrl_w2_pack copy), draws, head, picks, transition, results, traces and tick are the same text.  The f16 planes are
+// 1 KB larger than the f32 activations, so the per-form regions start 256 floats later: 83.4 KB (Q-sampling) and 104.0 KB
+// (SQRL), still one workgroup per CU.  The argument blocks carry the rrl_w2_pack_f16x3 stream as their last pointer.
+struct QsBlockH {
+    EvArgs a;
+    QsOnH q;
+    int horizon;
+};
+struct SqBlockH {
+    EvArgs a;
+    SqOnH s;
+    int horizon;
+};
+static_assert(QsLds<TileF16x3>::kBytes == QsLds<TileF32>::kBytes + 1024 && SqLds<TileF16x3>::kBytes == SqLds<TileF32>::kBytes + 1024,
+              "the f16 planes cost 1 KB over the f32 activations");
+
+__device__ __forceinline__ void globalize(QsOnH& q) { rrl_pack::to_global_all(q.lo, q.hi, q.tr_pick, q.tr_q, q.w2h); }
+__device__ __forceinline__ void globalize(SqOnH& s) {
+    rrl_pack::to_global_all(s.tr_head, s.tr_pick, s.tr_cstar, s.tr_nsafe, s.tr_q, s.w2h);
+}
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void eval_rollout_qs_f16x3_kernel(const QsBlockH k) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    rollout_tile<NavRoll, QsOnH>(k.a, NavRoll{}, blockIdx.x, lds, &k.q);
+}
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void eval_rollout_qs_f16x3_maze_kernel(const QsBlockH k) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    rollout_tile<MazeRoll, QsOnH>(k.a, MazeRoll{k.horizon}, blockIdx.x, lds, &k.q);
+}
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void eval_rollout_qs_f16x3_pack_kernel(const QsBlockH* __restrict__ blocks, rrl_pack::Idx ix) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int s, local;
+    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
+    QsBlockH k = blocks[s];
+    globalize(k.a);
+    globalize(k.q);
+    rollout_tile<NavRoll, QsOnH>(k.a, NavRoll{}, unsigned(local), lds, &k.q);
+}
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void eval_rollout_qs_f16x3_maze_pack_kernel(const QsBlockH* __restrict__ blocks, rrl_pack::Idx ix) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int s, local;
+    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
+    QsBlockH k = blocks[s];
+    globalize(k.a);
+    globalize(k.q);
+    rollout_tile<MazeRoll, QsOnH>(k.a, MazeRoll{k.horizon}, unsigned(local), lds, &k.q);
+}
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void eval_rollout_sqrl_f16x3_kernel(const SqBlockH k) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    rollout_tile<NavRoll, SqOnH>(k.a, NavRoll{}, blockIdx.x, lds, &k.s);
+}
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void eval_rollout_sqrl_f16x3_maze_kernel(const SqBlockH k) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    rollout_tile<MazeRoll, SqOnH>(k.a, MazeRoll{k.horizon}, blockIdx.x, lds, &k.s);
+}
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void eval_rollout_sqrl_f16x3_pack_kernel(const SqBlockH* __restrict__ blocks, rrl_pack::Idx ix) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int s, local;
+    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
+    SqBlockH k = blocks[s];
+    globalize(k.a);
+    globalize(k.s);
+    rollout_tile<NavRoll, SqOnH>(k.a, NavRoll{}, unsigned(local), lds, &k.s);
+}
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void eval_rollout_sqrl_f16x3_maze_pack_kernel(const SqBlockH* __restrict__ blocks, rrl_pack::Idx ix) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    int s, local;
+    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
+    SqBlockH k = blocks[s];
+    globalize(k.a);
+    globalize(k.s);
+    rollout_tile<MazeRoll, SqOnH>(k.a, MazeRoll{k.horizon}, unsigned(local), lds, &k.s);
+}
+
 template <size_t N>
 int given(const void* const (&p)[N]) {
     int k = 0;
@@ -1010,9 +1179,9 @@ int launch_qs_solo(const rrl_eval_rollout_qs_t* p, void* stream) {
     if (rc != RRL_OK) return rc;
     const QsBlock b = qs_block_of(p);
     const QsSolo k = qs_solo(is_maze(p));
-    const int rl = grant_lds(k.kernel, kQsLdsBytes, *k.granted);
+    const int rl = grant_lds(k.kernel, QsLds<TileF32>::kBytes, *k.granted);
     if (rl != RRL_OK) return rl;
-    hipLaunchKernelGGL(k.kernel, dim3((unsigned)b.a.blocks), dim3(kThreads), kQsLdsBytes, (hipStream_t)stream, b);
+    hipLaunchKernelGGL(k.kernel, dim3((unsigned)b.a.blocks), dim3(kThreads), QsLds<TileF32>::kBytes, (hipStream_t)stream, b);
     return check_launch();
 }
 
@@ -1067,9 +1236,9 @@ int launch_sqrl_solo(const rrl_eval_rollout_sqrl_t* p, void* stream) {
     if (rc != RRL_OK) return rc;
     const SqBlock b = sq_block_of(p);
     const SqSolo k = sq_solo(is_maze(p));
-    const int rl = grant_lds(k.kernel, kSqLdsBytes, *k.granted);
+    const int rl = grant_lds(k.kernel, SqLds<TileF32>::kBytes, *k.granted);
     if (rl != RRL_OK) return rl;
-    hipLaunchKernelGGL(k.kernel, dim3((unsigned)b.a.blocks), dim3(kThreads), kSqLdsBytes, (hipStream_t)stream, b);
+    hipLaunchKernelGGL(k.kernel, dim3((unsigned)b.a.blocks), dim3(kThreads), SqLds<TileF32>::kBytes, (hipStream_t)stream, b);
     return check_launch();
 }
 
@@ -1107,6 +1276,87 @@ int launch_pack(const rrl_pack::Key& key, int S, Build build, Kernel kernel, int
     return check_launch();
 }
 
+// ---- the f16x3 entries: the f32 entries' checks in their order, then the stream beside the descriptor ----
+
+// rc of the f32 entry's checks on the same descriptor; a NULL or misaligned stream is an invalid field, so it wins over a
+// size out of range
+int check_w2h(int rc, const float* w2h) {
+    if (rc == RRL_EINVAL) return rc;
+    if (!w2h || (reinterpret_cast<uintptr_t>(w2h) & 15) != 0) return RRL_EINVAL;
+    return rc;
+}
+
+QsBlockH qs_block_h(const rrl_eval_rollout_qs_t* p, const float* w2h) {
+    const QsBlock f = qs_block_of(p);
+    QsBlockH b{};
+    b.a = f.a;
+    static_cast<QsArgs&>(b.q) = f.q;
+    b.q.w2h = w2h;
+    b.horizon = f.horizon;
+    return b;
+}
+
+SqBlockH sq_block_h(const rrl_eval_rollout_sqrl_t* p, const float* w2h) {
+    const SqBlock f = sq_block_of(p);
+    SqBlockH b{};
+    b.a = f.a;
+    static_cast<SqArgs&>(b.s) = f.s;
+    b.s.w2h = w2h;
+    b.horizon = f.horizon;
+    return b;
+}
+
+// the f16x3 kernel of an env family, solo and packed, with the flag of its LDS grant
+template <class Block>
+struct SoloH {
+    void (*kernel)(const Block);
+    bool* granted;
+};
+template <class Block>
+struct PackH {
+    void (*kernel)(const Block*, rrl_pack::Idx);
+    bool* granted;
+};
+SoloH<QsBlockH> qs_solo_h(bool maze) {
+    static bool nav_set = false, maze_set = false;
+    return maze ? SoloH<QsBlockH>{eval_rollout_qs_f16x3_maze_kernel, &maze_set} : SoloH<QsBlockH>{eval_rollout_qs_f16x3_kernel, &nav_set};
+}
+PackH<QsBlockH> qs_pack_h(bool maze) {
+    static bool nav_set = false, maze_set = false;
+    return maze ? PackH<QsBlockH>{eval_rollout_qs_f16x3_maze_pack_kernel, &maze_set}
+                : PackH<QsBlockH>{eval_rollout_qs_f16x3_pack_kernel, &nav_set};
+}
+SoloH<SqBlockH> sq_solo_h(bool maze) {
+    static bool nav_set = false, maze_set = false;
+    return maze ? SoloH<SqBlockH>{eval_rollout_sqrl_f16x3_maze_kernel, &maze_set}
+                : SoloH<SqBlockH>{eval_rollout_sqrl_f16x3_kernel, &nav_set};
+}
+PackH<SqBlockH> sq_pack_h(bool maze) {
+    static bool nav_set = false, maze_set = false;
+    return maze ? PackH<SqBlockH>{eval_rollout_sqrl_f16x3_maze_pack_kernel, &maze_set}
+                : PackH<SqBlockH>{eval_rollout_sqrl_f16x3_pack_kernel, &nav_set};
+}
+
+template <class Block>
+int launch_solo_h(const Block& b, SoloH<Block> k, int lds, void* stream) {
+    const int rl = grant_lds(k.kernel, lds, *k.granted);
+    if (rl != RRL_OK) return rl;
+    hipLaunchKernelGGL(k.kernel, dim3((unsigned)b.a.blocks), dim3(kThreads), lds, (hipStream_t)stream, b);
+    return check_launch();
+}
+
+int launch_qs_solo_h(const rrl_eval_rollout_qs_t* p, const float* w2h, void* stream) {
+    const int rc = check_w2h(check_qs(p), w2h);
+    if (rc != RRL_OK) return rc;
+    return launch_solo_h(qs_block_h(p, w2h), qs_solo_h(is_maze(p)), QsLds<TileF16x3>::kBytes, stream);
+}
+
+int launch_sqrl_solo_h(const rrl_eval_rollout_sqrl_t* p, const float* w2h, void* stream) {
+    const int rc = check_w2h(check_sqrl(p), w2h);
+    if (rc != RRL_OK) return rc;
+    return launch_solo_h(sq_block_h(p, w2h), sq_solo_h(is_maze(p)), SqLds<TileF16x3>::kBytes, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1127,7 +1377,7 @@ int rrl_eval_rollout_qs_packed(int S, const rrl_eval_rollout_qs_t* args, void* s
     key.add(args, sizeof(rrl_eval_rollout_qs_t) * S);
     const QsPack k = qs_pack(maze);
     return launch_pack<QsBlock>(key, S, [&](int s, QsBlock& b) { return (b = qs_block_of(args + s)).a.blocks; }, k.kernel,
-                                kQsLdsBytes, k.granted, stream);
+                                QsLds<TileF32>::kBytes, k.granted, stream);
 }
 
 int rrl_eval_rollout_sqrl(const rrl_eval_rollout_sqrl_t* p, void* stream) { return launch_sqrl_solo(p, stream); }
@@ -1146,7 +1396,51 @@ int rrl_eval_rollout_sqrl_packed(int S, const rrl_eval_rollout_sqrl_t* args, voi
     key.add(args, sizeof(rrl_eval_rollout_sqrl_t) * S);
     const SqPack k = sq_pack(maze);
     return launch_pack<SqBlock>(key, S, [&](int s, SqBlock& b) { return (b = sq_block_of(args + s)).a.blocks; }, k.kernel,
-                                kSqLdsBytes, k.granted, stream);
+                                SqLds<TileF32>::kBytes, k.granted, stream);
+}
+
+int rrl_eval_rollout_qs_f16x3(const rrl_eval_rollout_qs_t* p, const float* qW2h, void* stream) {
+    return launch_qs_solo_h(p, qW2h, stream);
+}
+
+int rrl_eval_rollout_qs_f16x3_packed(int S, const rrl_eval_rollout_qs_t* args, const float* const* qW2h, void* stream) {
+    if (!args || !qW2h) return RRL_EINVAL;
+    if (S <= 0 || S > rrl_pack::kMaxSeeds) return RRL_ERANGE;
+    const int worst = check_seeds(S, [&](int s) { return check_w2h(check_qs(args + s), qW2h[s]); });
+    if (worst == RRL_EINVAL) return worst;
+    const bool maze = is_maze(args);
+    for (int s = 1; s < S; ++s)
+        if (is_maze(args + s) != maze) return RRL_EINVAL;       // one env family per launch: the kernels differ
+    if (worst != RRL_OK) return worst;
+    if (S == 1) return launch_qs_solo_h(args, qW2h[0], stream);
+    rrl_pack::Key key(rrl_pack::site::EvalRolloutQsF16x3, S);
+    key.add(args, sizeof(rrl_eval_rollout_qs_t) * S);
+    key.add(qW2h, sizeof(const float*) * S);
+    const PackH<QsBlockH> k = qs_pack_h(maze);
+    return launch_pack<QsBlockH>(key, S, [&](int s, QsBlockH& b) { return (b = qs_block_h(args + s, qW2h[s])).a.blocks; },
+                                 k.kernel, QsLds<TileF16x3>::kBytes, k.granted, stream);
+}
+
+int rrl_eval_rollout_sqrl_f16x3(const rrl_eval_rollout_sqrl_t* p, const float* qW2h, void* stream) {
+    return launch_sqrl_solo_h(p, qW2h, stream);
+}
+
+int rrl_eval_rollout_sqrl_f16x3_packed(int S, const rrl_eval_rollout_sqrl_t* args, const float* const* qW2h, void* stream) {
+    if (!args || !qW2h) return RRL_EINVAL;
+    if (S <= 0 || S > rrl_pack::kMaxSeeds) return RRL_ERANGE;
+    const int worst = check_seeds(S, [&](int s) { return check_w2h(check_sqrl(args + s), qW2h[s]); });
+    if (worst == RRL_EINVAL) return worst;
+    const bool maze = is_maze(args);
+    for (int s = 1; s < S; ++s)
+        if (is_maze(args + s) != maze) return RRL_EINVAL;       // one env family per launch: the kernels differ
+    if (worst != RRL_OK) return worst;
+    if (S == 1) return launch_sqrl_solo_h(args, qW2h[0], stream);
+    rrl_pack::Key key(rrl_pack::site::EvalRolloutSqrlF16x3, S);
+    key.add(args, sizeof(rrl_eval_rollout_sqrl_t) * S);
+    key.add(qW2h, sizeof(const float*) * S);
+    const PackH<SqBlockH> k = sq_pack_h(maze);
+    return launch_pack<SqBlockH>(key, S, [&](int s, SqBlockH& b) { return (b = sq_block_h(args + s, qW2h[s])).a.blocks; },
+                                 k.kernel, SqLds<TileF16x3>::kBytes, k.granted, stream);
 }
 
 int rrl_eval_rollout(const rrl_eval_rollout_t* p, void* stream) { return launch_solo(p, stream); }

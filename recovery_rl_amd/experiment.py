@@ -685,6 +685,10 @@ class Experiment:
             if self.loop.qsample_gated:
                 # where the recovery gate of that pass is evaluated (RRL_PACK_QSAMPLE=1: inside the qsample call)
                 self.vector_rules["qsample_gate"] = "in_launch"
+        # the two evaluation-scoring switches (RRL_EVAL_SQRL_F16X3, RRL_EVAL_QSAMPLE_F16X3), read once, here: every evaluation
+        # of this experiment, and the resume warning, go by these values (fast_update.eval_scoring)
+        from .fast_update import eval_qsample_f16x3_enabled, eval_sqrl_f16x3_enabled
+        self.eval_f16x3_switches = (eval_sqrl_f16x3_enabled(), eval_qsample_f16x3_enabled())
 
     # -- setup -----------------------------------------------------------------------------------
     def experiment_setup(self):
@@ -742,7 +746,7 @@ class Experiment:
                                                                    "buffers_cover_the_run", "plan_warm_start", "sqrl_acting",
                                                                    "sqrl_scoring",
                                                                    "qsample_acting", "qsample_scoring", "qsample_gate",
-                                                                   "evaluation")
+                                                                   "evaluation", "evaluation_scoring")
                                 if k in self.vector_rules}}
         if cfg.num_envs > 1:
             print("Q_risk batch: %s (--demo_share; 0 = the reference's single uniform draw, replay_memory.py:54-72)"
@@ -956,6 +960,12 @@ class Experiment:
             if was is not None and was != self.vector_rules["demo_share"]:
                 print("WARNING: the checkpoint was written with --demo_share %g, this run continues with %g"
                       % (was, self.vector_rules["demo_share"]))
+            # an evaluation changes no training state: the other evaluation scoring is no reason to refuse the checkpoint
+            from .fast_update import eval_scoring
+            was = extra.get("vector_rules", {}).get("evaluation_scoring")
+            now = eval_scoring(cfg, self.eval_f16x3_switches)
+            if was is not None and was != now:
+                print("WARNING: the checkpoint was written with evaluation scoring %s, this run continues with %s" % (was, now))
             print("Resumed from %s at iteration %d (%d env-steps)" % (cfg.resume, it, loop.total_numsteps))
         # after a resume the offline count comes from the checkpoint's counters (pre-training is skipped)
         start = dist_utils.aggregate_stats(
@@ -1098,6 +1108,7 @@ class Experiment:
             rollout.launch(env._max_episode_steps + 1)
             return self._eval_result(rollout.stats(label))
         self.vector_rules.pop("evaluation", None)          # the rule records the path the LAST evaluation took
+        self.vector_rules.pop("evaluation_scoring", None)
         obs = env.reset()
         n = cfg.num_envs
         alive = torch.ones(n, dtype=torch.bool, device=self.device)
@@ -1126,16 +1137,21 @@ class Experiment:
     def eval_rollout(self):
         """The EvalRollout of this experiment's evaluation env when evaluation runs on the kernel
         (fast_update.eval_rollout_path), else None: the module code below."""
-        from .fast_update import EvalRollout, eval_qsample_line, eval_rollout_path, eval_sqrl_line
+        from .fast_update import EvalRollout, eval_qsample_line, eval_rollout_path, eval_scoring, eval_sqrl_line
         cfg = self.exp_cfg
         if eval_rollout_path(cfg) != "hip" or getattr(self.agent, "fast", None) is None:
             return None
         if getattr(self, "_eval_rollout", None) is None:
             # (eval_rollout_path said "hip" for the Q-sampling line: RRL_FAST_EVAL_QSAMPLE=1 -> rrl_eval_rollout_qs; for the
             # SQRL line: RRL_FAST_EVAL_SQRL=1 -> rrl_eval_rollout_sqrl)
+            # (RRL_EVAL_QSAMPLE_F16X3=1 / RRL_EVAL_SQRL_F16X3=1 on those lines: their _f16x3 entries, by the switches as the
+            # constructor read them)
             self._eval_rollout = EvalRollout(self.agent.fast, self.eval_env(), cfg.eps_safe, cfg.use_recovery,
-                                             qsample=eval_qsample_line(cfg), sqrl=eval_sqrl_line(cfg))
+                                             qsample=eval_qsample_line(cfg), sqrl=eval_sqrl_line(cfg),
+                                             f16x3=eval_scoring(cfg, self.eval_f16x3_switches) == "f16x3")
         self.vector_rules["evaluation"] = "hip"
+        if self._eval_rollout.qsample or self._eval_rollout.sqrl:
+            self.vector_rules["evaluation_scoring"] = "f16x3" if self._eval_rollout.f16x3 else "f32"
         return self._eval_rollout
 
     def eval_env(self):

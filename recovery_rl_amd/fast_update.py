@@ -1257,7 +1257,7 @@ def pack_qsample_enabled():
 def qsample_f16x3_enabled():
     """RRL_QSAMPLE_F16X3=1: the rrl_qsample_act acting pass scores its candidates with layer 2 of Q_risk in f16x3
     (rrl_qsample_act_f16x3; opt-in).  Read once, when the loop is built; it matters only where qsample_acting_path(cfg) == "hip"
-    (the random-action phase and evaluation keep their f32 code whatever it says)."""
+    (the random-action phase keeps its f32 code whatever it says; evaluation has a switch of its own: eval_scoring)."""
     return os.environ.get("RRL_QSAMPLE_F16X3", "0") == "1"
 
 
@@ -1331,6 +1331,35 @@ def eval_rollout_path(cfg):
     return "hip" if hip else "modules"
 
 
+def eval_sqrl_f16x3_enabled():
+    """RRL_EVAL_SQRL_F16X3=1, on top of RRL_FAST_EVAL=1 RRL_FAST_EVAL_SQRL=1: the SQRL evaluation scores its candidates in
+    f16x3 (rrl_eval_rollout_sqrl_f16x3; opt-in, independent of RRL_SQRL_F16X3).  An Experiment reads it once, when it builds its
+    loop (Experiment.eval_f16x3_switches), and evaluates by that value from then on."""
+    return os.environ.get("RRL_EVAL_SQRL_F16X3", "0") == "1"
+
+
+def eval_qsample_f16x3_enabled():
+    """RRL_EVAL_QSAMPLE_F16X3=1, on top of RRL_FAST_EVAL=1 RRL_FAST_EVAL_QSAMPLE=1: the Q-sampling evaluation scores its
+    candidates in f16x3 (rrl_eval_rollout_qs_f16x3; opt-in, independent of RRL_QSAMPLE_F16X3).  An Experiment reads it once, when
+    it builds its loop (Experiment.eval_f16x3_switches), and evaluates by that value from then on."""
+    return os.environ.get("RRL_EVAL_QSAMPLE_F16X3", "0") == "1"
+
+
+def eval_scoring(cfg, switches=None):
+    """The arithmetic of the evaluation rollout's candidate scores: "f16x3" on the SQRL line under RRL_EVAL_SQRL_F16X3=1 and on
+    the Q-sampling line under RRL_EVAL_QSAMPLE_F16X3=1, where eval_rollout_path(cfg) == "hip"; else "f32" (the module path's
+    too, and every configuration that scores no candidates).  `switches` = (SQRL, Q-sampling): the two switches as read
+    earlier (an Experiment's, from when its loop was built); None: the environment now."""
+    sqrl, qsample = (eval_sqrl_f16x3_enabled(), eval_qsample_f16x3_enabled()) if switches is None else switches
+    if eval_rollout_path(cfg) != "hip":
+        return "f32"
+    if eval_sqrl_line(cfg):
+        return "f16x3" if sqrl else "f32"
+    if eval_qsample_line(cfg):
+        return "f16x3" if qsample else "f32"
+    return "f32"
+
+
 class EvalRollout:
     """One evaluation (Experiment.get_test_rollout_vectorized) of `env`'s envs as one rrl_eval_rollout launch on the live flat
     weights of `fast`.  Owns the per-env result buffers and its OWN fragment-order copies of the three W2 matrices, re-made
@@ -1338,17 +1367,21 @@ class EvalRollout:
     qsample=True: the Q-sampling form (rrl_eval_rollout_qs) -- no recovery policy; a gated row executes the best of QSAMPLE_K
     uniform candidates from the action box FastActor.qsample_box takes, drawn inside the launch.
     sqrl=True: the SQRL form (rrl_eval_rollout_sqrl) -- no gate and no recovery policy; every live row executes the pick
-    among SQRL_K candidates of the task policy's head (its four stacked last-layer rows), scored by Q_risk inside the launch."""
+    among SQRL_K candidates of the task policy's head (its four stacked last-layer rows), scored by Q_risk inside the launch.
+    f16x3=True (with qsample or sqrl): the candidates are scored in f16x3 (rrl_eval_rollout_qs_f16x3 / _sqrl_f16x3) on a
+    rrl_w2_pack_f16x3 stream of Q_risk's W2 that is owned here and re-made right before each launch, as the W2 copies are."""
 
     QSAMPLE_K = 1000                   # QRiskWrapper.select_action's candidate count
     SQRL_K = 100                       # SAC._sqrl_action's
 
-    def __init__(self, fast, env, eps_safe, use_recovery, qsample=False, sqrl=False):
+    def __init__(self, fast, env, eps_safe, use_recovery, qsample=False, sqrl=False, f16x3=False):
         self.f, self.env, self.n = fast, env, env.num_envs
         self.eps_safe, self.use_recovery, self.qsample = float(eps_safe), bool(use_recovery), bool(qsample)
-        self.sqrl = bool(sqrl)
+        self.sqrl, self.f16x3 = bool(sqrl), bool(f16x3)
         if self.sqrl and (self.use_recovery or self.qsample):
             raise _lib.RRLError("rrl_eval_rollout_sqrl: SQRL without a recovery policy only")
+        if self.f16x3 and not (self.sqrl or self.qsample):
+            raise _lib.RRLError("f16x3 evaluation scoring: the Q-sampling and SQRL forms only (they score candidates)")
         dev = fast.dev
         self.ret = torch.zeros(self.n, dtype=torch.float32, device=dev)
         self.success = torch.zeros(self.n, dtype=torch.uint8, device=dev)
@@ -1361,6 +1394,7 @@ class EvalRollout:
             ac = fast.qr.ac_space
             self.box = tuple(torch.as_tensor(b, dtype=torch.float32, device=dev).contiguous() for b in (ac.low, ac.high))
         self.w2p = [torch.empty(net.p["W2"].numel(), dtype=torch.float32, device=dev) for net in self.nets]
+        self.qw2h = torch.empty(fast.qrisk.p["W2"].numel(), dtype=torch.float32, device=dev) if self.f16x3 else None
         self.args = None
 
     def desc(self, T, reset=True, pos=None, trace=None):
@@ -1374,6 +1408,10 @@ class EvalRollout:
             W2 = net.p["W2"]
             _lib.check(f.lib.rrl_w2_pack(W2.shape[0], W2.shape[1], W2.data_ptr(), w2p.data_ptr(), _lib.current_stream()),
                        "rrl_w2_pack")
+        if self.f16x3:
+            W2 = f.qrisk.p["W2"]
+            _lib.check(f.lib.rrl_w2_pack_f16x3(W2.shape[0], W2.shape[1], W2.data_ptr(), self.qw2h.data_ptr(),
+                                               _lib.current_stream()), "rrl_w2_pack_f16x3")
         P = f.policy.p
         a = _lib.rrl_eval_rollout_t(n=self.n, T=int(T), H=f.policy.H, d_obs=2, d_act=2, env_kind=self.env.kind,
                                     reset=int(bool(reset)), pos=p(pos), pW1=p(P["W1"]), pb1=p(P["b1"]), pW2p=p(self.w2p[0]),
@@ -1407,6 +1445,10 @@ class EvalRollout:
 
     def launch(self, T, **kw):
         a = self.desc(T, **kw)
+        if self.f16x3:     # the same descriptor; the f16x3 stream rides beside it
+            entry = "rrl_eval_rollout_sqrl_f16x3" if self.sqrl else "rrl_eval_rollout_qs_f16x3"
+            _lib.check(getattr(self.f.lib, entry)(C.byref(a), self.qw2h.data_ptr(), _lib.current_stream()), entry)
+            return
         if self.sqrl:      # one entry for both env families, as the Q-sampling form
             _lib.check(self.f.lib.rrl_eval_rollout_sqrl(C.byref(a), _lib.current_stream()), "rrl_eval_rollout_sqrl")
             return
@@ -1429,7 +1471,17 @@ class EvalRollout:
 def eval_rollouts_packed(rollouts, T):
     """The evaluations of several seeds (EvalRollout each) as ONE rrl_eval_rollout_packed launch (one env per packed run:
     rrl_eval_rollout_maze_packed with every seed's env horizon when that env is Maze; rrl_eval_rollout_qs_packed for the
-    Q-sampling form, rrl_eval_rollout_sqrl_packed for the SQRL form)."""
+    Q-sampling form, rrl_eval_rollout_sqrl_packed for the SQRL form; their _f16x3_packed entries, with every seed's stream,
+    when the rollouts score in f16x3 -- all of them or none)."""
+    if len({r.f16x3 for r in rollouts}) > 1:
+        raise _lib.RRLError("eval_rollouts_packed: f16x3 and f32 rollouts in one call")
+    if rollouts[0].f16x3:
+        sqrl = rollouts[0].sqrl
+        args = ((_lib.rrl_eval_rollout_sqrl_t if sqrl else _lib.rrl_eval_rollout_qs_t) * len(rollouts))(*[r.desc(T) for r in rollouts])
+        streams = (C.c_void_p * len(rollouts))(*[r.qw2h.data_ptr() for r in rollouts])
+        entry = "rrl_eval_rollout_sqrl_f16x3_packed" if sqrl else "rrl_eval_rollout_qs_f16x3_packed"
+        _lib.check(getattr(_lib.load(), entry)(len(rollouts), args, streams, _lib.current_stream()), entry)
+        return
     if rollouts[0].sqrl:
         args = (_lib.rrl_eval_rollout_sqrl_t * len(rollouts))(*[r.desc(T) for r in rollouts])
         _lib.check(_lib.load().rrl_eval_rollout_sqrl_packed(len(rollouts), args, _lib.current_stream()),
