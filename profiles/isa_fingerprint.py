@@ -5,6 +5,9 @@ kernels instruction-identical:
     python profiles/isa_fingerprint.py recovery_rl_amd/csrc/_build/mlp_kernels.o > before.json
     ... edit ...
     python profiles/isa_fingerprint.py recovery_rl_amd/csrc/_build/mlp_kernels.o [more.o] before.json   # the differences
+
+Kernels are matched by name.  Where the clean-up renames kernels (functions that become instantiations of a template),
+--rename=map.json gives {name before: name now}, applied to before.json's names.
 """
 import glob
 import hashlib
@@ -49,15 +52,20 @@ def fingerprint(path):
 
 
 if __name__ == "__main__":
-    objs = [a for a in sys.argv[1:] if not a.endswith(".json")]
-    ref = [a for a in sys.argv[1:] if a.endswith(".json")]
+    argv = [a for a in sys.argv[1:] if not a.startswith("--rename=")]
+    rename = {}
+    for a in sys.argv[1:]:
+        if a.startswith("--rename="):
+            rename.update(json.load(open(a[len("--rename="):])))
+    objs = [a for a in argv if not a.endswith(".json")]
+    ref = [a for a in argv if a.endswith(".json")]
     now = {}
     for o in objs:
         now.update(fingerprint(o))
     if not ref:
         print(json.dumps(now, indent=0, sort_keys=True))
     else:
-        before = json.load(open(ref[0]))
+        before = {rename.get(k, k): v for k, v in json.load(open(ref[0])).items()}
         gone = sorted(set(before) - set(now))
         new = sorted(set(now) - set(before))
         vec = sorted(k for k in now if k in before and before[k][2] != now[k][2] and before[k][3] == now[k][3])

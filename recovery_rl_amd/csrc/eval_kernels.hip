@@ -14,47 +14,52 @@
 // Larger tiles would read W2 less often per env; no other tile size was built or timed, so that trade is NOT measured
 // (DESIGN section 7 has the times as shipped).
 //
-// The stand-alone and the packed kernel (rrl_eval_rollout_packed: S seeds side by side, pack.hpp) have ONE body
-// (rollout_tile); they differ only in where the argument block and the tile index come from.
+// ONE body (rollout_tile<Env, Form>) and two kernel templates over it: eval_rollout_kernel (the argument block in the kernel
+// arguments, the tile index from the grid) and eval_rollout_pack_kernel (S seeds side by side, pack.hpp: block and tile index
+// from a packed plan).  Their instantiations are the grid Env x Form, twenty kernels:
+//   Env   NavRoll restates nav_kernels.hip's NavEnv; MazeRoll is maze_device.hpp's transition (a trait with reset and step, as
+//         step_push.hpp's), so the Navigation kernels carry no Maze branch.
+//   Form  NoQs (rrl_eval_rollout, rrl_eval_rollout_maze); QsOn / QsOnH (rrl_eval_rollout_qs[_f16x3]); SqOn / SqOnH
+//         (rrl_eval_rollout_sqrl[_f16x3]); every entry has a _packed form.  The form names its descriptor, the group its
+//         argument block carries, its LDS bytes and its occupancy; the host path (launch_solo / launch_packed) is one for all.
 //
 // The tile's primitives and layer-2 helpers come from mfma_tile.hpp (one row tile: MR = 1); run_stack is this file's own,
-// for its 16 rows, DIN < 4 inputs and NOUT outputs.  The body is generic over the env (a trait with reset and step, as
-// step_push.hpp's): NavRoll restates nav_kernels.hip's NavEnv, MazeRoll is maze_device.hpp's transition behind kernels of
-// its own (rrl_eval_rollout_maze[_packed]), so the Navigation kernels carry no Maze branch.
+// for its 16 rows, DIN < 4 inputs and NOUT outputs.
 //
-// Q-sampling recovery (rrl_eval_rollout_qs[_packed], four more kernels: Navigation / Maze x solo / packed) is the same body
-// with the QsOn trait: a row whose gate fired while alive draws k uniform candidates (stream RRL_STREAM_EVAL_QSAMPLE, keyed
-// by (env row, step) alone), scores them on the 64-row twin-head tile of mfma_tile.hpp (q_phase / twin_q: the bits of
+// Q-sampling recovery (QsOn): a row whose gate fired while alive draws k uniform candidates (stream RRL_STREAM_EVAL_QSAMPLE,
+// keyed by (env row, step) alone), scores them on the 64-row twin-head tile of mfma_tile.hpp (q_phase / twin_q: the bits of
 // rrl_qsample_act) in passes of up to four row tiles, and executes the argmin.  The gated rows of a tile are served one
 // after another in ascending row order (a workgroup-uniform loop over the gate's ballot), so k up to 1024 stays within one
 // workgroup's LDS: the 64-row tile prefix (70.0 KB; the 16-row rollout regions lie inside its activation region, every
 // hand-over behind a barrier) + candidates and their q (12 KB) + obs / results / mask (0.4 KB) = 82.4 KB, one workgroup per
 // CU of the 160 KB -- the launch's shape anyway (4096 envs = 256 workgroups).  A tile with no gated live row skips the
-// phase; rows that are not gated, dead or >= n draw and score nothing.  The NoQs instantiations are the four kernels above,
-// instruction for instruction (profiles/eval_rollout_qsample_fingerprint.txt).
+// phase; rows that are not gated, dead or >= n draw and score nothing.
 //
-// SQRL (rrl_eval_rollout_sqrl[_packed], four more kernels) is the same body with the SqOn trait, and a different cost shape:
-// there is no gate, EVERY live row needs k <= 128 candidates of the task policy's tanh-Gaussian head on every step.  The
-// policy stack runs with four outputs (run_stack<2, 4>: mean and log_std rows; rows 0 .. 1 keep the bits of the two-output
-// form, every output is a chain of its own), the candidates of the tile's live rows are drawn by all 512 threads (stream
-// RRL_STREAM_EVAL_SQRL, keyed by (env row, step) alone) and FLATTENED, live rows in ascending order, into passes of up to
-// four row tiles on the same 64-row twin-head tile -- every xs row carries its own obs, so candidates of different env rows
-// share a pass: 25 passes per step at k = 100 with 16 live rows, against 32 when each row is served alone with a ragged
-// second pass.  The candidates, logp and q of the whole tile stay in LDS, and the picks of different rows run on different
-// waves (wave w: rows w and w + 8; the pick's double weights stay in registers and are read across the wave in ascending
-// candidate order, so the sums are those of rrl_sqrl_act).  LDS: the 64-row tile prefix (70.0 KB) + candidates / logp / q
-// (16 x 128 x 4 floats = 32 KB) + head / obs / results / row table / mask (0.9 KB) = 103.0 KB, one workgroup per CU.
-// The candidate-head arithmetic and the pick of sqrl_kernels.hip are RESTATED here (sq_candidates, sq_pick), not shared
-// through a header: rrl_sqrl_act keeps its pick's weights in LDS and serves one env per workgroup, and its kernels keep
-// their code untouched this way; tests/test_eval_sqrl_gpu.py holds the two to the same bits.  The eight kernels
-// above are unchanged, instruction for instruction (profiles/eval_rollout_sqrl_fingerprint.txt).
+// SQRL (SqOn) has a different cost shape: there is no gate, EVERY live row needs k <= 128 candidates of the task policy's
+// tanh-Gaussian head on every step.  The policy stack runs with four outputs (run_stack<2, 4>: mean and log_std rows; rows
+// 0 .. 1 keep the bits of the two-output form, every output is a chain of its own), the candidates of the tile's live rows
+// are drawn by all 512 threads (stream RRL_STREAM_EVAL_SQRL, keyed by (env row, step) alone) and FLATTENED, live rows in
+// ascending order, into passes of up to four row tiles on the same 64-row twin-head tile -- every xs row carries its own
+// obs, so candidates of different env rows share a pass: 25 passes per step at k = 100 with 16 live rows, against 32 when
+// each row is served alone with a ragged second pass.  The candidates, logp and q of the whole tile stay in LDS, and the
+// picks of different rows run on different waves (wave w: rows w and w + 8; the pick's double weights stay in registers and
+// are read across the wave in ascending candidate order, so the sums are those of rrl_sqrl_act).  LDS: the 64-row tile
+// prefix (70.0 KB) + candidates / logp / q (16 x 128 x 4 floats = 32 KB) + head / obs / results / row table / mask (0.9 KB)
+// = 103.0 KB, one workgroup per CU.  The candidate-head arithmetic and the pick of sqrl_kernels.hip are RESTATED here
+// (sq_candidates, sq_pick), not shared through a header: rrl_sqrl_act keeps its pick's weights in LDS and serves one env per
+// workgroup, and its kernels keep their code untouched this way; tests/test_eval_sqrl_gpu.py holds the two to the same bits.
 //
-// f16x3 scoring (rrl_eval_rollout_qs_f16x3 / rrl_eval_rollout_sqrl_f16x3 and their packed forms, eight more kernels): the
-// candidate phases are templates on the scoring tile -- TileF32 (mfma_tile.hpp) or TileF16x3 (mfma_tile_f16x3.hpp: layer 2 as
-// three v_mfma_f32_16x16x32_f16 products of hi / lo splits, the bits of rrl_qsample_act_f16x3 / rrl_sqrl_act_f16x3) -- and the
-// per-form LDS regions start at the tile's kOffOwn (QsLds / SqLds: 83.4 KB and 104.0 KB on TileF16x3, whose planes are 1 KB
-// larger).  The QsOnH / SqOnH traits carry the rrl_w2_pack_f16x3 stream; everything but the scores is the f32 forms' text, and
-// the twelve kernels above are unchanged, instruction for instruction (profiles/eval_f16x3_fingerprint.txt).
+// f16x3 scoring (QsOnH / SqOnH): the candidate phases are templates on the scoring tile -- TileF32 (mfma_tile.hpp) or TileF16x3
+// (mfma_tile_f16x3.hpp: layer 2 as three v_mfma_f32_16x16x32_f16 products of hi / lo splits, the bits of rrl_qsample_act_f16x3
+// / rrl_sqrl_act_f16x3) -- and the per-form LDS regions start at the tile's kOffOwn (QsLds / SqLds: 83.4 KB and 104.0 KB on
+// TileF16x3, whose planes are 1 KB larger).  These forms' groups carry the rrl_w2_pack_f16x3 stream as their last pointer;
+// start, policy stack, gate (exact f32 on the 16-row stack, from the rrl_w2_pack copy), draws, head, picks, transition,
+// results, traces and tick are the f32 forms' text.
+//
+// The twenty kernels are, instruction for instruction, the twenty hand-written ones they replace
+// (profiles/eval_one_body_fingerprint.txt).
+#include <type_traits>
+
 #include "maze_device.hpp"
 #include "mfma_tile.hpp"
 #include "mfma_tile_f16x3.hpp"
@@ -153,16 +158,24 @@ struct EvArgs {
     uint8_t* tr_flags;
 };
 
-// The Q-sampling group of a launch (rrl_eval_rollout_qs_t's own fields), beside EvArgs so that the kernels without it keep
-// their argument block
+// A form of the rollout is a trait: what rollout_tile does between the task action and the transition (on / sqrl), the tile
+// its candidates are scored on and the Q_risk group they are scored with, and what a launch of it needs -- the descriptor,
+// the group its argument block carries behind EvArgs (Args; globalize: its pointers in a packed plan's copy), the LDS
+// bytes and the waves per SIMD its kernels are compiled for.
+
+// The Q-sampling group (rrl_eval_rollout_qs_t's own fields)
 struct QsArgs {
     int k;
     const float *lo, *hi;
     int32_t* tr_pick;
     float* tr_q;
 };
+// The base form: no candidate phase and no group (Args only types the pointer rollout_tile never follows), the stack's own
+// 17.5 KB of LDS
 struct NoQs {
     static constexpr bool on = false, sqrl = false;
+    static constexpr int kWavesPerEu = 4, kLds = kLdsBytes;
+    using Desc = rrl_eval_rollout_t;
     using Args = QsArgs;
 };
 // the exact-f32 tile of mfma_tile.hpp, as the candidate phases name a tile (TileF16x3 is the other one)
@@ -177,24 +190,34 @@ struct TileF32 {
     }
 };
 using rrl_tile::TileF16x3;
-struct QsOn : QsArgs {
+// The candidate forms: 82.4 .. 104.0 KB of LDS put one workgroup = two waves per SIMD on a CU, so their kernels ask for that
+// occupancy and its registers (at four waves' budget the rollout state beside the four-row-tile accumulators spilled)
+struct QsOn {
     static constexpr bool on = true, sqrl = false;
+    using Desc = rrl_eval_rollout_qs_t;
     using Args = QsArgs;
     using Tile = TileF32;
+    static constexpr int kWavesPerEu = 2, kLds = QsLds<Tile>::kBytes;
     // the Q_risk group the candidates are scored with
     static __device__ __forceinline__ const Net& score_net(const EvArgs& a, const QsArgs&) { return a.q; }
+    static __device__ __forceinline__ void globalize(QsArgs& g) { rrl_pack::to_global_all(g.lo, g.hi, g.tr_pick, g.tr_q); }
 };
 // f16x3 scoring (rrl_eval_rollout_qs_f16x3): the gate keeps a.q with its rrl_w2_pack copy, the candidates' layer 2 reads
-// the rrl_w2_pack_f16x3 stream that rides beside the descriptor
+// the rrl_w2_pack_f16x3 stream that rides beside the descriptor, the group's last pointer
 struct QsArgsH : QsArgs {
     const float* w2h;
 };
-struct QsOnH : QsArgsH {
+struct QsOnH {
     static constexpr bool on = true, sqrl = false;
+    using Desc = rrl_eval_rollout_qs_t;
     using Args = QsArgsH;
     using Tile = TileF16x3;
+    static constexpr int kWavesPerEu = 2, kLds = QsLds<Tile>::kBytes;
     static __device__ __forceinline__ Net score_net(const EvArgs& a, const QsArgsH& s) {
         return Net{a.q.W1, a.q.b1, s.w2h, a.q.b2, a.q.W3, a.q.b3};
+    }
+    static __device__ __forceinline__ void globalize(QsArgsH& g) {
+        rrl_pack::to_global_all(g.lo, g.hi, g.tr_pick, g.tr_q, g.w2h);
     }
 };
 // ... and the SQRL group (rrl_eval_rollout_sqrl_t's own fields)
@@ -204,24 +227,37 @@ struct SqArgs {
     int32_t *tr_pick, *tr_cstar, *tr_nsafe;
     float* tr_q;
 };
-struct SqOn : SqArgs {
+struct SqOn {
     static constexpr bool on = false, sqrl = true;
+    using Desc = rrl_eval_rollout_sqrl_t;
     using Args = SqArgs;
     using Tile = TileF32;
+    static constexpr int kWavesPerEu = 2, kLds = SqLds<Tile>::kBytes;
     static __device__ __forceinline__ const Net& score_net(const EvArgs& a, const SqArgs&) { return a.q; }
+    static __device__ __forceinline__ void globalize(SqArgs& g) {
+        rrl_pack::to_global_all(g.tr_head, g.tr_pick, g.tr_cstar, g.tr_nsafe, g.tr_q);
+    }
 };
 // f16x3 scoring (rrl_eval_rollout_sqrl_f16x3): a.q.W2p is not read, layer 2 reads the rrl_w2_pack_f16x3 stream
 struct SqArgsH : SqArgs {
     const float* w2h;
 };
-struct SqOnH : SqArgsH {
+struct SqOnH {
     static constexpr bool on = false, sqrl = true;
+    using Desc = rrl_eval_rollout_sqrl_t;
     using Args = SqArgsH;
     using Tile = TileF16x3;
+    static constexpr int kWavesPerEu = 2, kLds = SqLds<Tile>::kBytes;
     static __device__ __forceinline__ Net score_net(const EvArgs& a, const SqArgsH& s) {
         return Net{a.q.W1, a.q.b1, s.w2h, a.q.b2, a.q.W3, a.q.b3};
     }
+    static __device__ __forceinline__ void globalize(SqArgsH& g) {
+        rrl_pack::to_global_all(g.tr_head, g.tr_pick, g.tr_cstar, g.tr_nsafe, g.tr_q, g.w2h);
+    }
 };
+static_assert(QsOnH::kLds == QsOn::kLds + 1024 && SqOnH::kLds == SqOn::kLds + 1024, "the f16 planes cost 1 KB over the f32 activations");
+template <class Form>
+constexpr bool kHasGroup = Form::on || Form::sqrl;
 
 // One 2-hidden-layer stack (head `head` of w) on the row tile in xs: inputs = the first DIN columns of xs, outputs = the
 // first NOUT rows of W3.  Leaves part[o][wave][row] (output o's pre-activation is b3[o] + the sum over the 8 waves, added by
@@ -809,10 +845,40 @@ __device__ __forceinline__ void rollout_tile(const EvArgs& a, const Env& env, un
     rrl::advance_counter_blocks(a.counter_dev, uint64_t(a.T) + uint64_t(a.reset), unsigned(a.blocks));
 }
 
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
-void eval_rollout_kernel(const EvArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    rollout_tile(a, NavRoll{}, blockIdx.x, lds);
+// ---- the kernels: one solo and one packed template over (Env, Form) ----
+
+// The argument block of a launch: EvArgs, the form's group, the Maze horizon (the tail, unused by Navigation: one layout for
+// both env kinds of a candidate form).  The solo kernel takes one as its argument, a packed plan holds S of them.  The base
+// form has no group, and its Navigation block is EvArgs alone.
+template <class Env, class Form>
+struct Block {
+    EvArgs a;
+    typename Form::Args g;
+    int horizon;
+};
+template <>
+struct Block<NavRoll, NoQs> {
+    EvArgs a;
+};
+template <>
+struct Block<MazeRoll, NoQs> {
+    EvArgs a;
+    int horizon;
+};
+
+template <class Env, class Form>
+__device__ __forceinline__ Env env_of(const Block<Env, Form>& k) {
+    if constexpr (std::is_same<Env, MazeRoll>::value)
+        return MazeRoll{k.horizon};
+    else
+        return NavRoll{};
+}
+template <class Env, class Form>
+__device__ __forceinline__ const typename Form::Args* group_of(const Block<Env, Form>& k) {
+    if constexpr (kHasGroup<Form>)
+        return &k.g;
+    else
+        return nullptr;
 }
 
 // The copied argument block's pointers as global ones (pack.hpp: to_global)
@@ -825,222 +891,37 @@ __device__ __forceinline__ void globalize(EvArgs& a) {
                             a.steps, a.tr_pos, a.tr_task, a.tr_real, a.tr_z, a.tr_eps, a.tr_reward, a.tr_flags);
 }
 
+// Workgroup blockIdx.x of the block's own grid.  The kernel's arguments are the block's parts: the block as one argument,
+// but EvArgs and the horizon as two for the base Maze form (launch_block) -- read out of one by-value struct, that
+// kernel's horizon load is scheduled elsewhere.
+template <class Env, class Form, class... Part>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(Form::kWavesPerEu, Form::kWavesPerEu)))
+void eval_rollout_kernel(const Part... part) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const Block<Env, Form> k{part...};
+    rollout_tile<Env, Form>(k.a, env_of(k), blockIdx.x, lds, group_of(k));
+}
+
 // S evaluations side by side (pack.hpp): workgroup b serves tile `local` of seed s's own grid, on seed s's argument block.
 // A padding workgroup of a pinned mapping leaves before it touches anything.
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
-void eval_rollout_pack_kernel(const EvArgs* __restrict__ blocks, rrl_pack::Idx ix) {
+template <class Env, class Form>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(Form::kWavesPerEu, Form::kWavesPerEu)))
+void eval_rollout_pack_kernel(const Block<Env, Form>* __restrict__ blocks, rrl_pack::Idx ix) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int s, local;
     if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
-    EvArgs a = blocks[s];
-    globalize(a);
-    rollout_tile(a, NavRoll{}, unsigned(local), lds);
-}
-
-// The Maze kernels: the same body on MazeRoll.  The argument block is EvArgs unchanged; the horizon rides beside it (the
-// solo kernel's second argument, MazeBlock's tail in a packed plan), so the Navigation kernels' argument offsets stay put.
-struct MazeBlock {
-    EvArgs a;
-    int horizon;
-};
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
-void eval_rollout_maze_kernel(const EvArgs a, int horizon) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    rollout_tile(a, MazeRoll{horizon}, blockIdx.x, lds);
-}
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
-void eval_rollout_maze_pack_kernel(const MazeBlock* __restrict__ blocks, rrl_pack::Idx ix) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    int s, local;
-    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
-    EvArgs a = blocks[s].a;
-    const int horizon = blocks[s].horizon;
-    globalize(a);
-    rollout_tile(a, MazeRoll{horizon}, unsigned(local), lds);
-}
-
-// The Q-sampling kernels: the same body with QsOn, on the larger LDS carve-up.  One argument block for both env kinds (the
-// Maze horizon is its tail, unused by Navigation); a packed plan holds S of them.  82.4 KB of LDS put one workgroup = two
-// waves per SIMD on a CU, so the kernels ask for that occupancy and its registers (at four waves' budget the rollout state
-// beside the four-row-tile accumulators spilled).
-struct QsBlock {
-    EvArgs a;
-    QsOn q;
-    int horizon;
-};
-
-__device__ __forceinline__ void globalize(QsOn& q) { rrl_pack::to_global_all(q.lo, q.hi, q.tr_pick, q.tr_q); }
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void eval_rollout_qs_kernel(const QsBlock k) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    rollout_tile<NavRoll, QsOn>(k.a, NavRoll{}, blockIdx.x, lds, &k.q);
-}
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void eval_rollout_qs_maze_kernel(const QsBlock k) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    rollout_tile<MazeRoll, QsOn>(k.a, MazeRoll{k.horizon}, blockIdx.x, lds, &k.q);
-}
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void eval_rollout_qs_pack_kernel(const QsBlock* __restrict__ blocks, rrl_pack::Idx ix) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    int s, local;
-    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
-    QsBlock k = blocks[s];
+    Block<Env, Form> k = blocks[s];
     globalize(k.a);
-    globalize(k.q);
-    rollout_tile<NavRoll, QsOn>(k.a, NavRoll{}, unsigned(local), lds, &k.q);
+    if constexpr (kHasGroup<Form>) Form::globalize(k.g);
+    rollout_tile<Env, Form>(k.a, env_of(k), unsigned(local), lds, group_of(k));
 }
 
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void eval_rollout_qs_maze_pack_kernel(const QsBlock* __restrict__ blocks, rrl_pack::Idx ix) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    int s, local;
-    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
-    QsBlock k = blocks[s];
-    globalize(k.a);
-    globalize(k.q);
-    rollout_tile<MazeRoll, QsOn>(k.a, MazeRoll{k.horizon}, unsigned(local), lds, &k.q);
-}
+// ---- the host path: one for the twelve entries ----
+// An entry is a form and what rides beside the descriptor, per seed (Side): nothing, the Maze horizon of the base form
+// (rrl_eval_rollout_maze) or the rrl_w2_pack_f16x3 stream of an f16x3 form.
 
-// The SQRL kernels: the same body with SqOn, on its own LDS carve-up (103.0 KB: one workgroup = two waves per SIMD on a CU)
-struct SqBlock {
-    EvArgs a;
-    SqOn s;
-    int horizon;
-};
-
-__device__ __forceinline__ void globalize(SqOn& s) { rrl_pack::to_global_all(s.tr_head, s.tr_pick, s.tr_cstar, s.tr_nsafe, s.tr_q); }
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void eval_rollout_sqrl_kernel(const SqBlock k) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    rollout_tile<NavRoll, SqOn>(k.a, NavRoll{}, blockIdx.x, lds, &k.s);
-}
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void eval_rollout_sqrl_maze_kernel(const SqBlock k) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    rollout_tile<MazeRoll, SqOn>(k.a, MazeRoll{k.horizon}, blockIdx.x, lds, &k.s);
-}
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void eval_rollout_sqrl_pack_kernel(const SqBlock* __restrict__ blocks, rrl_pack::Idx ix) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    int s, local;
-    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
-    SqBlock k = blocks[s];
-    globalize(k.a);
-    globalize(k.s);
-    rollout_tile<NavRoll, SqOn>(k.a, NavRoll{}, unsigned(local), lds, &k.s);
-}
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void eval_rollout_sqrl_maze_pack_kernel(const SqBlock* __restrict__ blocks, rrl_pack::Idx ix) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    int s, local;
-    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
-    SqBlock k = blocks[s];
-    globalize(k.a);
-    globalize(k.s);
-    rollout_tile<MazeRoll, SqOn>(k.a, MazeRoll{k.horizon}, unsigned(local), lds, &k.s);
-}
-
-// The f16x3 kernels (rrl_eval_rollout_qs_f16x3 / rrl_eval_rollout_sqrl_f16x3 and their packed forms): the eight kernels above
-// with the candidates scored on TileF16x3 -- layer 2 of the twin Q_risk as three v_mfma_f32_16x16x32_f16 products of hi / lo
-// splits, the bits of rrl_qsample_act_f16x3 / rrl_sqrl_act_f16x3.  Start, policy stack, gate (exact f32 on the 16-row stack,
-// from the rrl_w2_pack copy), draws, head, picks, transition, results, traces and tick are the same text.  The f16 planes are
-// 1 KB larger than the f32 activations, so the per-form regions start 256 floats later: 83.4 KB (Q-sampling) and 104.0 KB
-// (SQRL), still one workgroup per CU.  The argument blocks carry the rrl_w2_pack_f16x3 stream as their last pointer.
-struct QsBlockH {
-    EvArgs a;
-    QsOnH q;
-    int horizon;
-};
-struct SqBlockH {
-    EvArgs a;
-    SqOnH s;
-    int horizon;
-};
-static_assert(QsLds<TileF16x3>::kBytes == QsLds<TileF32>::kBytes + 1024 && SqLds<TileF16x3>::kBytes == SqLds<TileF32>::kBytes + 1024,
-              "the f16 planes cost 1 KB over the f32 activations");
-
-__device__ __forceinline__ void globalize(QsOnH& q) { rrl_pack::to_global_all(q.lo, q.hi, q.tr_pick, q.tr_q, q.w2h); }
-__device__ __forceinline__ void globalize(SqOnH& s) {
-    rrl_pack::to_global_all(s.tr_head, s.tr_pick, s.tr_cstar, s.tr_nsafe, s.tr_q, s.w2h);
-}
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void eval_rollout_qs_f16x3_kernel(const QsBlockH k) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    rollout_tile<NavRoll, QsOnH>(k.a, NavRoll{}, blockIdx.x, lds, &k.q);
-}
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void eval_rollout_qs_f16x3_maze_kernel(const QsBlockH k) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    rollout_tile<MazeRoll, QsOnH>(k.a, MazeRoll{k.horizon}, blockIdx.x, lds, &k.q);
-}
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void eval_rollout_qs_f16x3_pack_kernel(const QsBlockH* __restrict__ blocks, rrl_pack::Idx ix) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    int s, local;
-    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
-    QsBlockH k = blocks[s];
-    globalize(k.a);
-    globalize(k.q);
-    rollout_tile<NavRoll, QsOnH>(k.a, NavRoll{}, unsigned(local), lds, &k.q);
-}
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void eval_rollout_qs_f16x3_maze_pack_kernel(const QsBlockH* __restrict__ blocks, rrl_pack::Idx ix) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    int s, local;
-    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
-    QsBlockH k = blocks[s];
-    globalize(k.a);
-    globalize(k.q);
-    rollout_tile<MazeRoll, QsOnH>(k.a, MazeRoll{k.horizon}, unsigned(local), lds, &k.q);
-}
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void eval_rollout_sqrl_f16x3_kernel(const SqBlockH k) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    rollout_tile<NavRoll, SqOnH>(k.a, NavRoll{}, blockIdx.x, lds, &k.s);
-}
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void eval_rollout_sqrl_f16x3_maze_kernel(const SqBlockH k) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    rollout_tile<MazeRoll, SqOnH>(k.a, MazeRoll{k.horizon}, blockIdx.x, lds, &k.s);
-}
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void eval_rollout_sqrl_f16x3_pack_kernel(const SqBlockH* __restrict__ blocks, rrl_pack::Idx ix) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    int s, local;
-    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
-    SqBlockH k = blocks[s];
-    globalize(k.a);
-    globalize(k.s);
-    rollout_tile<NavRoll, SqOnH>(k.a, NavRoll{}, unsigned(local), lds, &k.s);
-}
-
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void eval_rollout_sqrl_f16x3_maze_pack_kernel(const SqBlockH* __restrict__ blocks, rrl_pack::Idx ix) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    int s, local;
-    if (!rrl_pack::locate(ix, blockIdx.x, s, local)) return;
-    SqBlockH k = blocks[s];
-    globalize(k.a);
-    globalize(k.s);
-    rollout_tile<MazeRoll, SqOnH>(k.a, MazeRoll{k.horizon}, unsigned(local), lds, &k.s);
-}
+struct None {};
+constexpr None kNoSides[rrl_pack::kMaxSeeds] = {};           // the packed entries' side array, where nothing rides
 
 template <size_t N>
 int given(const void* const (&p)[N]) {
@@ -1050,6 +931,29 @@ int given(const void* const (&p)[N]) {
 }
 
 constexpr int kMaxHorizon = 1 << 30;
+int check_horizon(int horizon) { return horizon < 1 || horizon > kMaxHorizon ? RRL_ERANGE : RRL_OK; }
+
+// The env family of a launch.  A candidate descriptor names it (and carries the Maze horizon); a base entry fixes it -- the
+// Maze one is the one with a horizon beside the descriptor -- and check_desc holds the descriptor to it.
+template <class Desc, class Side>
+bool is_maze(const Desc* p, Side) {
+    if constexpr (std::is_same<Desc, rrl_eval_rollout_t>::value)
+        return std::is_same<Side, int>::value;
+    else
+        return p->base.env_kind == RRL_ENV_MAZE;
+}
+template <class Desc, class Side>
+int horizon_of(const Desc* p, Side side) {
+    if constexpr (std::is_same<Side, int>::value)
+        return side;
+    else if constexpr (std::is_same<Desc, rrl_eval_rollout_t>::value)
+        return 0;                                            // a base Navigation entry: never asked
+    else
+        return p->horizon;
+}
+const rrl_eval_rollout_t* base_of(const rrl_eval_rollout_t* p) { return p; }
+template <class Desc>
+const rrl_eval_rollout_t* base_of(const Desc* p) { return &p->base; }
 
 // the checks of a descriptor, before any launch (rrl_hip.h); maze: the entry's env is Maze, else Navigation 1 / 2
 int check_desc(const rrl_eval_rollout_t* p, bool maze = false) {
@@ -1067,6 +971,48 @@ int check_desc(const rrl_eval_rollout_t* p, bool maze = false) {
         return RRL_EINVAL;
     if (p->T < 1 || p->T > kMaxT || p->n > kMaxN) return RRL_ERANGE;
     return RRL_OK;
+}
+
+// the checks of a candidate form's descriptor: the base's for its env kind, then its own fields (Q-sampling: the box; the
+// k limit is the form's); an invalid field wins over a size out of range
+template <class Form>
+int check_group(const typename Form::Desc* p) {
+    if (!p) return RRL_EINVAL;
+    const rrl_eval_rollout_t* e = &p->base;
+    const bool maze = is_maze(p, None{});
+    const int rc = check_desc(e, maze);
+    if (rc == RRL_EINVAL) return rc;
+    const void* const rg[] = {e->rW1, e->rb1, e->rW2p, e->rb2, e->rW3, e->rb3, e->rscale, e->rbias, e->rlog_std};
+    if (!e->qW1 || given(rg) != 0) return RRL_EINVAL;        // (a Q_risk group given in part: check_desc)
+    if constexpr (Form::on)
+        if (!p->lo || !p->hi) return RRL_EINVAL;
+    if (rc != RRL_OK) return rc;
+    constexpr int kmax = Form::sqrl ? kSqMaxK : kMaxK;
+    if (p->k < 1 || p->k > kmax || (long long)e->n * p->k >= (1LL << 32)) return RRL_ERANGE;
+    return maze ? check_horizon(p->horizon) : RRL_OK;
+}
+
+// rc of the descriptor's checks; a NULL or misaligned stream is an invalid field, so it wins over a size out of range
+int check_w2h(int rc, const float* w2h) {
+    if (rc == RRL_EINVAL) return rc;
+    if (!w2h || (reinterpret_cast<uintptr_t>(w2h) & 15) != 0) return RRL_EINVAL;
+    return rc;
+}
+
+// every check of one seed: the descriptor's, then what rides beside it
+template <class Form, class Side>
+int check(const typename Form::Desc* p, Side side) {
+    int rc;
+    if constexpr (kHasGroup<Form>)
+        rc = check_group<Form>(p);
+    else
+        rc = check_desc(p, is_maze(p, side));
+    if constexpr (std::is_same<Side, int>::value)
+        return rc != RRL_OK ? rc : check_horizon(side);
+    else if constexpr (std::is_same<Side, const float*>::value)
+        return check_w2h(rc, side);
+    else
+        return rc;
 }
 
 EvArgs block_of(const rrl_eval_rollout_t* p) {
@@ -1104,142 +1050,59 @@ EvArgs block_of(const rrl_eval_rollout_t* p) {
     return a;
 }
 
-int launch_solo(const rrl_eval_rollout_t* p, void* stream) {
-    const int rc = check_desc(p);
-    if (rc != RRL_OK) return rc;
-    const EvArgs a = block_of(p);
-    hipLaunchKernelGGL(eval_rollout_kernel, dim3((unsigned)a.blocks), dim3(kThreads), kLdsBytes, (hipStream_t)stream, a);
-    return check_launch();
+void fill(QsArgs& g, const rrl_eval_rollout_qs_t* p) {
+    g.k = p->k;
+    g.lo = p->lo;
+    g.hi = p->hi;
+    g.tr_pick = p->tr_pick;
+    g.tr_q = p->tr_q;
+}
+void fill(SqArgs& g, const rrl_eval_rollout_sqrl_t* p) {
+    g.k = p->k;
+    g.tr_head = p->tr_head;
+    g.tr_pick = p->tr_pick;
+    g.tr_cstar = p->tr_cstar;
+    g.tr_nsafe = p->tr_nsafe;
+    g.tr_q = p->tr_q;
 }
 
-int check_maze(const rrl_eval_rollout_t* p, int horizon) {
-    const int rc = check_desc(p, true);
-    if (rc != RRL_OK) return rc;
-    return horizon < 1 || horizon > kMaxHorizon ? RRL_ERANGE : RRL_OK;
-}
-
-int launch_maze_solo(const rrl_eval_rollout_t* p, int horizon, void* stream) {
-    const int rc = check_maze(p, horizon);
-    if (rc != RRL_OK) return rc;
-    const EvArgs a = block_of(p);
-    hipLaunchKernelGGL(eval_rollout_maze_kernel, dim3((unsigned)a.blocks), dim3(kThreads), kLdsBytes, (hipStream_t)stream, a,
-                       horizon);
-    return check_launch();
-}
-
-bool is_maze(const rrl_eval_rollout_qs_t* p) { return p && p->base.env_kind == RRL_ENV_MAZE; }
-
-// the checks of a Q-sampling descriptor, before any launch (rrl_hip.h): the base's for its env kind, then its own fields;
-// an invalid field wins over a size out of range
-int check_qs(const rrl_eval_rollout_qs_t* p) {
-    if (!p) return RRL_EINVAL;
-    const rrl_eval_rollout_t* e = &p->base;
-    const int rc = check_desc(e, is_maze(p));
-    if (rc == RRL_EINVAL) return rc;
-    const void* const rg[] = {e->rW1, e->rb1, e->rW2p, e->rb2, e->rW3, e->rb3, e->rscale, e->rbias, e->rlog_std};
-    if (!p->lo || !p->hi || !e->qW1 || given(rg) != 0) return RRL_EINVAL;   // (a Q_risk group given in part: check_desc)
-    if (rc != RRL_OK) return rc;
-    if (p->k < 1 || p->k > kMaxK || (long long)e->n * p->k >= (1LL << 32)) return RRL_ERANGE;
-    if (is_maze(p) && (p->horizon < 1 || p->horizon > kMaxHorizon)) return RRL_ERANGE;
-    return RRL_OK;
-}
-
-QsBlock qs_block_of(const rrl_eval_rollout_qs_t* p) {
-    QsBlock b{};
-    b.a = block_of(&p->base);
-    b.q.k = p->k;
-    b.q.lo = p->lo;
-    b.q.hi = p->hi;
-    b.q.tr_pick = p->tr_pick;
-    b.q.tr_q = p->tr_q;
-    b.horizon = is_maze(p) ? p->horizon : 0;
+template <class Env, class Form, class Side>
+Block<Env, Form> block_of(const typename Form::Desc* p, Side side) {
+    Block<Env, Form> b{};
+    b.a = block_of(base_of(p));
+    if constexpr (kHasGroup<Form>) fill(b.g, p);
+    if constexpr (std::is_same<Side, const float*>::value) b.g.w2h = side;
+    if constexpr (std::is_same<Env, MazeRoll>::value) b.horizon = horizon_of(p, side);
     return b;
 }
 
-// the Q-sampling kernel of an env family, solo and packed, with the flag of its LDS grant (> 64 KB: once per kernel)
-struct QsSolo {
-    void (*kernel)(const QsBlock);
-    bool* granted;
-};
-QsSolo qs_solo(bool maze) {
-    static bool nav_set = false, maze_set = false;
-    return maze ? QsSolo{eval_rollout_qs_maze_kernel, &maze_set} : QsSolo{eval_rollout_qs_kernel, &nav_set};
-}
-struct QsPack {
-    void (*kernel)(const QsBlock*, rrl_pack::Idx);
-    bool* granted;
-};
-QsPack qs_pack(bool maze) {
-    static bool nav_set = false, maze_set = false;
-    return maze ? QsPack{eval_rollout_qs_maze_pack_kernel, &maze_set} : QsPack{eval_rollout_qs_pack_kernel, &nav_set};
-}
-
-int launch_qs_solo(const rrl_eval_rollout_qs_t* p, void* stream) {
-    const int rc = check_qs(p);
-    if (rc != RRL_OK) return rc;
-    const QsBlock b = qs_block_of(p);
-    const QsSolo k = qs_solo(is_maze(p));
-    const int rl = grant_lds(k.kernel, QsLds<TileF32>::kBytes, *k.granted);
-    if (rl != RRL_OK) return rl;
-    hipLaunchKernelGGL(k.kernel, dim3((unsigned)b.a.blocks), dim3(kThreads), QsLds<TileF32>::kBytes, (hipStream_t)stream, b);
+// One launch of a form's kernel.  > 64 KB of dynamic LDS is granted once per kernel: `granted` is the flag of the caller's
+// own (Env, Form) instantiation.
+template <class Form, class Kernel, class... Arg>
+int launch(Kernel kernel, bool& granted, int grid, void* stream, const Arg&... arg) {
+    if (Form::kLds > 64 * 1024) {
+        const int rl = grant_lds(kernel, Form::kLds, granted);
+        if (rl != RRL_OK) return rl;
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kThreads), Form::kLds, (hipStream_t)stream, arg...);
     return check_launch();
 }
 
-bool is_maze(const rrl_eval_rollout_sqrl_t* p) { return p && p->base.env_kind == RRL_ENV_MAZE; }
+template <class Env, class Form>
+int launch_block(const Block<Env, Form>& b, void* stream) {
+    static bool granted = false;
+    if constexpr (std::is_same<Block<Env, Form>, Block<MazeRoll, NoQs>>::value)
+        return launch<Form>(eval_rollout_kernel<Env, Form, EvArgs, int>, granted, b.a.blocks, stream, b.a, b.horizon);
+    else
+        return launch<Form>(eval_rollout_kernel<Env, Form, Block<Env, Form>>, granted, b.a.blocks, stream, b);
+}
 
-// the checks of an SQRL descriptor, before any launch (rrl_hip.h): check_qs's shape
-int check_sqrl(const rrl_eval_rollout_sqrl_t* p) {
-    if (!p) return RRL_EINVAL;
-    const rrl_eval_rollout_t* e = &p->base;
-    const int rc = check_desc(e, is_maze(p));
-    if (rc == RRL_EINVAL) return rc;
-    const void* const rg[] = {e->rW1, e->rb1, e->rW2p, e->rb2, e->rW3, e->rb3, e->rscale, e->rbias, e->rlog_std};
-    if (!e->qW1 || given(rg) != 0) return RRL_EINVAL;        // (a Q_risk group given in part: check_desc)
+template <class Form, class Side>
+int launch_solo(const typename Form::Desc* p, Side side, void* stream) {
+    const int rc = check<Form>(p, side);
     if (rc != RRL_OK) return rc;
-    if (p->k < 1 || p->k > kSqMaxK || (long long)e->n * p->k >= (1LL << 32)) return RRL_ERANGE;
-    if (is_maze(p) && (p->horizon < 1 || p->horizon > kMaxHorizon)) return RRL_ERANGE;
-    return RRL_OK;
-}
-
-SqBlock sq_block_of(const rrl_eval_rollout_sqrl_t* p) {
-    SqBlock b{};
-    b.a = block_of(&p->base);
-    b.s.k = p->k;
-    b.s.tr_head = p->tr_head;
-    b.s.tr_pick = p->tr_pick;
-    b.s.tr_cstar = p->tr_cstar;
-    b.s.tr_nsafe = p->tr_nsafe;
-    b.s.tr_q = p->tr_q;
-    b.horizon = is_maze(p) ? p->horizon : 0;
-    return b;
-}
-
-struct SqSolo {
-    void (*kernel)(const SqBlock);
-    bool* granted;
-};
-SqSolo sq_solo(bool maze) {
-    static bool nav_set = false, maze_set = false;
-    return maze ? SqSolo{eval_rollout_sqrl_maze_kernel, &maze_set} : SqSolo{eval_rollout_sqrl_kernel, &nav_set};
-}
-struct SqPack {
-    void (*kernel)(const SqBlock*, rrl_pack::Idx);
-    bool* granted;
-};
-SqPack sq_pack(bool maze) {
-    static bool nav_set = false, maze_set = false;
-    return maze ? SqPack{eval_rollout_sqrl_maze_pack_kernel, &maze_set} : SqPack{eval_rollout_sqrl_pack_kernel, &nav_set};
-}
-
-int launch_sqrl_solo(const rrl_eval_rollout_sqrl_t* p, void* stream) {
-    const int rc = check_sqrl(p);
-    if (rc != RRL_OK) return rc;
-    const SqBlock b = sq_block_of(p);
-    const SqSolo k = sq_solo(is_maze(p));
-    const int rl = grant_lds(k.kernel, SqLds<TileF32>::kBytes, *k.granted);
-    if (rl != RRL_OK) return rl;
-    hipLaunchKernelGGL(k.kernel, dim3((unsigned)b.a.blocks), dim3(kThreads), SqLds<TileF32>::kBytes, (hipStream_t)stream, b);
-    return check_launch();
+    return is_maze(p, side) ? launch_block(block_of<MazeRoll, Form>(p, side), stream)
+                            : launch_block(block_of<NavRoll, Form>(p, side), stream);
 }
 
 // The packed entries check every seed before anything is stored or launched, and an invalid field (RRL_EINVAL) wins over
@@ -1255,224 +1118,78 @@ int check_seeds(int S, Check check) {
     return worst;
 }
 
-// ... and launch alike (pack.hpp): `key` holds the entry's input, build(s, block) fills seed s's argument block and returns
-// its tiles (<= 2^18 workgroups per seed: any mapping's grid fits an int); granted: the kernel's LDS grant, if it needs one
-template <class Block, class Build, class Kernel>
-int launch_pack(const rrl_pack::Key& key, int S, Build build, Kernel kernel, int lds, bool* granted, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
+// ... and launch alike (pack.hpp): `key` holds the entry's input; on a miss every seed's argument block is built and placed
+// by its tiles (<= 2^18 workgroups per seed: any mapping's grid fits an int)
+template <class Env, class Form, class Side>
+int launch_plan(const rrl_pack::Key& key, int S, const typename Form::Desc* args, const Side* sides, void* stream) {
+    static bool granted = false;
     const rrl_pack::Plan* plan = rrl_pack::lookup(key);
     if (!plan) {
-        std::vector<Block> blocks(S);
+        std::vector<Block<Env, Form>> blocks(S);
         int count[rrl_pack::kMaxSeeds];
-        for (int s = 0; s < S; ++s) count[s] = build(s, blocks[s]);
-        plan = rrl_pack::publish(key, blocks, rrl_pack::place(S, count), st);
+        for (int s = 0; s < S; ++s) count[s] = (blocks[s] = block_of<Env, Form>(args + s, sides[s])).a.blocks;
+        plan = rrl_pack::publish(key, blocks, rrl_pack::place(S, count), (hipStream_t)stream);
         if (!plan) return rrl_pack::store_error();
     }
-    if (granted) {
-        const int rl = grant_lds(kernel, lds, *granted);
-        if (rl != RRL_OK) return rl;
-    }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)plan->grid), dim3(kThreads), lds, st, (const Block*)plan->dev, plan->ix);
-    return check_launch();
+    return launch<Form>(eval_rollout_pack_kernel<Env, Form>, granted, plan->grid, stream, (const Block<Env, Form>*)plan->dev,
+                        plan->ix);
 }
 
-// ---- the f16x3 entries: the f32 entries' checks in their order, then the stream beside the descriptor ----
-
-// rc of the f32 entry's checks on the same descriptor; a NULL or misaligned stream is an invalid field, so it wins over a
-// size out of range
-int check_w2h(int rc, const float* w2h) {
-    if (rc == RRL_EINVAL) return rc;
-    if (!w2h || (reinterpret_cast<uintptr_t>(w2h) & 15) != 0) return RRL_EINVAL;
-    return rc;
+template <class Form, class Side>
+int launch_packed(rrl_pack::Site site, int S, const typename Form::Desc* args, const Side* sides, void* stream) {
+    if (!args || !sides) return RRL_EINVAL;
+    if (S <= 0 || S > rrl_pack::kMaxSeeds) return RRL_ERANGE;
+    const int worst = check_seeds(S, [&](int s) { return check<Form>(args + s, sides[s]); });
+    if (worst == RRL_EINVAL) return worst;
+    const bool maze = is_maze(args, sides[0]);
+    if constexpr (kHasGroup<Form>)                           // (a base entry's env is the entry's own)
+        for (int s = 1; s < S; ++s)
+            if (is_maze(args + s, sides[s]) != maze) return RRL_EINVAL;   // one env family per launch: the kernels differ
+    if (worst != RRL_OK) return worst;
+    // one seed: the packed launch IS the solo launch (argument block in the kernel arguments, no plan)
+    if (S == 1) return launch_solo<Form>(args, sides[0], stream);
+    rrl_pack::Key key(site, S);
+    key.add(args, sizeof(*args) * S);
+    if constexpr (!std::is_same<Side, None>::value) key.add(sides, sizeof(Side) * S);
+    return maze ? launch_plan<MazeRoll, Form>(key, S, args, sides, stream) : launch_plan<NavRoll, Form>(key, S, args, sides, stream);
 }
 
-QsBlockH qs_block_h(const rrl_eval_rollout_qs_t* p, const float* w2h) {
-    const QsBlock f = qs_block_of(p);
-    QsBlockH b{};
-    b.a = f.a;
-    static_cast<QsArgs&>(b.q) = f.q;
-    b.q.w2h = w2h;
-    b.horizon = f.horizon;
-    return b;
-}
-
-SqBlockH sq_block_h(const rrl_eval_rollout_sqrl_t* p, const float* w2h) {
-    const SqBlock f = sq_block_of(p);
-    SqBlockH b{};
-    b.a = f.a;
-    static_cast<SqArgs&>(b.s) = f.s;
-    b.s.w2h = w2h;
-    b.horizon = f.horizon;
-    return b;
-}
-
-// the f16x3 kernel of an env family, solo and packed, with the flag of its LDS grant
-template <class Block>
-struct SoloH {
-    void (*kernel)(const Block);
-    bool* granted;
-};
-template <class Block>
-struct PackH {
-    void (*kernel)(const Block*, rrl_pack::Idx);
-    bool* granted;
-};
-SoloH<QsBlockH> qs_solo_h(bool maze) {
-    static bool nav_set = false, maze_set = false;
-    return maze ? SoloH<QsBlockH>{eval_rollout_qs_f16x3_maze_kernel, &maze_set} : SoloH<QsBlockH>{eval_rollout_qs_f16x3_kernel, &nav_set};
-}
-PackH<QsBlockH> qs_pack_h(bool maze) {
-    static bool nav_set = false, maze_set = false;
-    return maze ? PackH<QsBlockH>{eval_rollout_qs_f16x3_maze_pack_kernel, &maze_set}
-                : PackH<QsBlockH>{eval_rollout_qs_f16x3_pack_kernel, &nav_set};
-}
-SoloH<SqBlockH> sq_solo_h(bool maze) {
-    static bool nav_set = false, maze_set = false;
-    return maze ? SoloH<SqBlockH>{eval_rollout_sqrl_f16x3_maze_kernel, &maze_set}
-                : SoloH<SqBlockH>{eval_rollout_sqrl_f16x3_kernel, &nav_set};
-}
-PackH<SqBlockH> sq_pack_h(bool maze) {
-    static bool nav_set = false, maze_set = false;
-    return maze ? PackH<SqBlockH>{eval_rollout_sqrl_f16x3_maze_pack_kernel, &maze_set}
-                : PackH<SqBlockH>{eval_rollout_sqrl_f16x3_pack_kernel, &nav_set};
-}
-
-template <class Block>
-int launch_solo_h(const Block& b, SoloH<Block> k, int lds, void* stream) {
-    const int rl = grant_lds(k.kernel, lds, *k.granted);
-    if (rl != RRL_OK) return rl;
-    hipLaunchKernelGGL(k.kernel, dim3((unsigned)b.a.blocks), dim3(kThreads), lds, (hipStream_t)stream, b);
-    return check_launch();
-}
-
-int launch_qs_solo_h(const rrl_eval_rollout_qs_t* p, const float* w2h, void* stream) {
-    const int rc = check_w2h(check_qs(p), w2h);
-    if (rc != RRL_OK) return rc;
-    return launch_solo_h(qs_block_h(p, w2h), qs_solo_h(is_maze(p)), QsLds<TileF16x3>::kBytes, stream);
-}
-
-int launch_sqrl_solo_h(const rrl_eval_rollout_sqrl_t* p, const float* w2h, void* stream) {
-    const int rc = check_w2h(check_sqrl(p), w2h);
-    if (rc != RRL_OK) return rc;
-    return launch_solo_h(sq_block_h(p, w2h), sq_solo_h(is_maze(p)), SqLds<TileF16x3>::kBytes, stream);
-}
+using rrl_pack::Site;
 
 }  // namespace
 
 extern "C" {
 
-int rrl_eval_rollout_qs(const rrl_eval_rollout_qs_t* p, void* stream) { return launch_qs_solo(p, stream); }
-
-int rrl_eval_rollout_qs_packed(int S, const rrl_eval_rollout_qs_t* args, void* stream) {
-    if (!args) return RRL_EINVAL;
-    if (S <= 0 || S > rrl_pack::kMaxSeeds) return RRL_ERANGE;
-    const int worst = check_seeds(S, [&](int s) { return check_qs(args + s); });
-    if (worst == RRL_EINVAL) return worst;
-    const bool maze = is_maze(args);
-    for (int s = 1; s < S; ++s)
-        if (is_maze(args + s) != maze) return RRL_EINVAL;       // one env family per launch: the kernels differ
-    if (worst != RRL_OK) return worst;
-    if (S == 1) return launch_qs_solo(args, stream);
-    rrl_pack::Key key(rrl_pack::Site::EvalRolloutQs, S);
-    key.add(args, sizeof(rrl_eval_rollout_qs_t) * S);
-    const QsPack k = qs_pack(maze);
-    return launch_pack<QsBlock>(key, S, [&](int s, QsBlock& b) { return (b = qs_block_of(args + s)).a.blocks; }, k.kernel,
-                                QsLds<TileF32>::kBytes, k.granted, stream);
+int rrl_eval_rollout(const rrl_eval_rollout_t* p, void* stream) { return launch_solo<NoQs>(p, None{}, stream); }
+int rrl_eval_rollout_packed(int S, const rrl_eval_rollout_t* args, void* stream) {
+    return launch_packed<NoQs>(Site::EvalRollout, S, args, kNoSides, stream);
+}
+int rrl_eval_rollout_maze(const rrl_eval_rollout_t* p, int horizon, void* stream) { return launch_solo<NoQs>(p, horizon, stream); }
+int rrl_eval_rollout_maze_packed(int S, const rrl_eval_rollout_t* args, const int* horizon, void* stream) {
+    return launch_packed<NoQs>(Site::EvalRolloutMaze, S, args, horizon, stream);
 }
 
-int rrl_eval_rollout_sqrl(const rrl_eval_rollout_sqrl_t* p, void* stream) { return launch_sqrl_solo(p, stream); }
-
+int rrl_eval_rollout_qs(const rrl_eval_rollout_qs_t* p, void* stream) { return launch_solo<QsOn>(p, None{}, stream); }
+int rrl_eval_rollout_qs_packed(int S, const rrl_eval_rollout_qs_t* args, void* stream) {
+    return launch_packed<QsOn>(Site::EvalRolloutQs, S, args, kNoSides, stream);
+}
+int rrl_eval_rollout_sqrl(const rrl_eval_rollout_sqrl_t* p, void* stream) { return launch_solo<SqOn>(p, None{}, stream); }
 int rrl_eval_rollout_sqrl_packed(int S, const rrl_eval_rollout_sqrl_t* args, void* stream) {
-    if (!args) return RRL_EINVAL;
-    if (S <= 0 || S > rrl_pack::kMaxSeeds) return RRL_ERANGE;
-    const int worst = check_seeds(S, [&](int s) { return check_sqrl(args + s); });
-    if (worst == RRL_EINVAL) return worst;
-    const bool maze = is_maze(args);
-    for (int s = 1; s < S; ++s)
-        if (is_maze(args + s) != maze) return RRL_EINVAL;       // one env family per launch: the kernels differ
-    if (worst != RRL_OK) return worst;
-    if (S == 1) return launch_sqrl_solo(args, stream);
-    rrl_pack::Key key(rrl_pack::Site::EvalRolloutSqrl, S);
-    key.add(args, sizeof(rrl_eval_rollout_sqrl_t) * S);
-    const SqPack k = sq_pack(maze);
-    return launch_pack<SqBlock>(key, S, [&](int s, SqBlock& b) { return (b = sq_block_of(args + s)).a.blocks; }, k.kernel,
-                                SqLds<TileF32>::kBytes, k.granted, stream);
+    return launch_packed<SqOn>(Site::EvalRolloutSqrl, S, args, kNoSides, stream);
 }
 
 int rrl_eval_rollout_qs_f16x3(const rrl_eval_rollout_qs_t* p, const float* qW2h, void* stream) {
-    return launch_qs_solo_h(p, qW2h, stream);
+    return launch_solo<QsOnH>(p, qW2h, stream);
 }
-
 int rrl_eval_rollout_qs_f16x3_packed(int S, const rrl_eval_rollout_qs_t* args, const float* const* qW2h, void* stream) {
-    if (!args || !qW2h) return RRL_EINVAL;
-    if (S <= 0 || S > rrl_pack::kMaxSeeds) return RRL_ERANGE;
-    const int worst = check_seeds(S, [&](int s) { return check_w2h(check_qs(args + s), qW2h[s]); });
-    if (worst == RRL_EINVAL) return worst;
-    const bool maze = is_maze(args);
-    for (int s = 1; s < S; ++s)
-        if (is_maze(args + s) != maze) return RRL_EINVAL;       // one env family per launch: the kernels differ
-    if (worst != RRL_OK) return worst;
-    if (S == 1) return launch_qs_solo_h(args, qW2h[0], stream);
-    rrl_pack::Key key(rrl_pack::site::EvalRolloutQsF16x3, S);
-    key.add(args, sizeof(rrl_eval_rollout_qs_t) * S);
-    key.add(qW2h, sizeof(const float*) * S);
-    const PackH<QsBlockH> k = qs_pack_h(maze);
-    return launch_pack<QsBlockH>(key, S, [&](int s, QsBlockH& b) { return (b = qs_block_h(args + s, qW2h[s])).a.blocks; },
-                                 k.kernel, QsLds<TileF16x3>::kBytes, k.granted, stream);
+    return launch_packed<QsOnH>(Site::EvalRolloutQsF16x3, S, args, qW2h, stream);
 }
-
 int rrl_eval_rollout_sqrl_f16x3(const rrl_eval_rollout_sqrl_t* p, const float* qW2h, void* stream) {
-    return launch_sqrl_solo_h(p, qW2h, stream);
+    return launch_solo<SqOnH>(p, qW2h, stream);
 }
-
 int rrl_eval_rollout_sqrl_f16x3_packed(int S, const rrl_eval_rollout_sqrl_t* args, const float* const* qW2h, void* stream) {
-    if (!args || !qW2h) return RRL_EINVAL;
-    if (S <= 0 || S > rrl_pack::kMaxSeeds) return RRL_ERANGE;
-    const int worst = check_seeds(S, [&](int s) { return check_w2h(check_sqrl(args + s), qW2h[s]); });
-    if (worst == RRL_EINVAL) return worst;
-    const bool maze = is_maze(args);
-    for (int s = 1; s < S; ++s)
-        if (is_maze(args + s) != maze) return RRL_EINVAL;       // one env family per launch: the kernels differ
-    if (worst != RRL_OK) return worst;
-    if (S == 1) return launch_sqrl_solo_h(args, qW2h[0], stream);
-    rrl_pack::Key key(rrl_pack::site::EvalRolloutSqrlF16x3, S);
-    key.add(args, sizeof(rrl_eval_rollout_sqrl_t) * S);
-    key.add(qW2h, sizeof(const float*) * S);
-    const PackH<SqBlockH> k = sq_pack_h(maze);
-    return launch_pack<SqBlockH>(key, S, [&](int s, SqBlockH& b) { return (b = sq_block_h(args + s, qW2h[s])).a.blocks; },
-                                 k.kernel, SqLds<TileF16x3>::kBytes, k.granted, stream);
-}
-
-int rrl_eval_rollout(const rrl_eval_rollout_t* p, void* stream) { return launch_solo(p, stream); }
-
-int rrl_eval_rollout_packed(int S, const rrl_eval_rollout_t* args, void* stream) {
-    if (!args) return RRL_EINVAL;
-    if (S <= 0 || S > rrl_pack::kMaxSeeds) return RRL_ERANGE;
-    const int rc = check_seeds(S, [&](int s) { return check_desc(args + s); });
-    if (rc != RRL_OK) return rc;
-    // one seed: the packed launch IS the solo launch (argument block in the kernel arguments, no plan)
-    if (S == 1) return launch_solo(args, stream);
-    rrl_pack::Key key(rrl_pack::Site::EvalRollout, S);
-    key.add(args, sizeof(rrl_eval_rollout_t) * S);
-    return launch_pack<EvArgs>(key, S, [&](int s, EvArgs& b) { return (b = block_of(args + s)).blocks; },
-                               eval_rollout_pack_kernel, kLdsBytes, nullptr, stream);
-}
-
-int rrl_eval_rollout_maze(const rrl_eval_rollout_t* p, int horizon, void* stream) {
-    return launch_maze_solo(p, horizon, stream);
-}
-
-int rrl_eval_rollout_maze_packed(int S, const rrl_eval_rollout_t* args, const int* horizon, void* stream) {
-    if (!args || !horizon) return RRL_EINVAL;
-    if (S <= 0 || S > rrl_pack::kMaxSeeds) return RRL_ERANGE;
-    const int rc = check_seeds(S, [&](int s) { return check_maze(args + s, horizon[s]); });
-    if (rc != RRL_OK) return rc;
-    if (S == 1) return launch_maze_solo(args, horizon[0], stream);
-    rrl_pack::Key key(rrl_pack::Site::EvalRolloutMaze, S);
-    key.add(args, sizeof(rrl_eval_rollout_t) * S);
-    key.add(horizon, sizeof(int) * S);
-    const auto build = [&](int s, MazeBlock& b) { return (b = MazeBlock{block_of(args + s), horizon[s]}).a.blocks; };
-    return launch_pack<MazeBlock>(key, S, build, eval_rollout_maze_pack_kernel, kLdsBytes, nullptr, stream);
+    return launch_packed<SqOnH>(Site::EvalRolloutSqrlF16x3, S, args, qW2h, stream);
 }
 
 }  // extern "C"
+

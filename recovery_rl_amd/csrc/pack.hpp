@@ -197,18 +197,8 @@ inline Launch place_members(int S, const int* most) {
 enum class Site : int {
     HiddenBackward = 1, StackForward, HeadBackward, BackwardPair, Adam, AdamDuals, PolicyHeads, RcpoPenalty, ReplayDraw,
     NavStep, MazeStep, SqrlAct, QsampleAct, EvalRollout, EvalRolloutMaze, EvalRolloutQs, EvalRolloutSqrl, SqrlActF16x3,
-    QsampleActF16x3
+    QsampleActF16x3, EvalRolloutQsF16x3, EvalRolloutSqrlF16x3
 };
-// Two more launch sites (the f16x3 evaluation rollouts of eval_kernels.hip).  They stand beside the enum, not in it: its member
-// list is pinned as it stands (tests/test_qsample_f16x3_cpu.py), and a key needs nothing of its site but a value no other
-// site has.  Their values start at kFirstOutside, far above the enum's consecutive ones, so a member appended to the enum
-// cannot meet them; the static_assert holds the enum below that range (its last member: update it with the enum).
-namespace site {
-constexpr int kFirstOutside = 1000;
-constexpr Site EvalRolloutQsF16x3 = Site(kFirstOutside);
-constexpr Site EvalRolloutSqrlF16x3 = Site(kFirstOutside + 1);
-static_assert(int(Site::QsampleActF16x3) < kFirstOutside, "enum Site has grown into the values of namespace site");
-}  // namespace site
 
 // A packed launch = (device copy of the S argument blocks, block ranges, launch parameters), built once per distinct
 // INPUT and looked up by the bytes of that input (the caller's descriptor arrays, which the Python side builds in zeroed

@@ -1443,23 +1443,24 @@ class EvalRollout:
     def maze(self):
         return self.env.kind == _lib.ENV_MAZE
 
+    @property
+    def entry(self):
+        """(entry, descriptor type, side) of this rollout's form: the stand-alone entry's name -- the packed one is that name +
+        "_packed" --, the descriptor it takes, and what rides beside the descriptor (per seed, in a packed launch): None, the
+        env's own horizon for the base form on Maze (it ends a row; T stays horizon + 1) or the f16x3 stream.  The Q-sampling
+        and SQRL forms have one entry for both env families: the Maze horizon rides in their descriptor."""
+        if self.sqrl or self.qsample:
+            name, desc_t = (("rrl_eval_rollout_sqrl", _lib.rrl_eval_rollout_sqrl_t) if self.sqrl else
+                            ("rrl_eval_rollout_qs", _lib.rrl_eval_rollout_qs_t))
+            return (name + "_f16x3", desc_t, C.c_void_p(self.qw2h.data_ptr())) if self.f16x3 else (name, desc_t, None)
+        if self.maze:
+            return "rrl_eval_rollout_maze", _lib.rrl_eval_rollout_t, C.c_int(int(self.env.horizon))
+        return "rrl_eval_rollout", _lib.rrl_eval_rollout_t, None
+
     def launch(self, T, **kw):
         a = self.desc(T, **kw)
-        if self.f16x3:     # the same descriptor; the f16x3 stream rides beside it
-            entry = "rrl_eval_rollout_sqrl_f16x3" if self.sqrl else "rrl_eval_rollout_qs_f16x3"
-            _lib.check(getattr(self.f.lib, entry)(C.byref(a), self.qw2h.data_ptr(), _lib.current_stream()), entry)
-            return
-        if self.sqrl:      # one entry for both env families, as the Q-sampling form
-            _lib.check(self.f.lib.rrl_eval_rollout_sqrl(C.byref(a), _lib.current_stream()), "rrl_eval_rollout_sqrl")
-            return
-        if self.qsample:   # one entry for both env families (the Maze horizon rides in the descriptor)
-            _lib.check(self.f.lib.rrl_eval_rollout_qs(C.byref(a), _lib.current_stream()), "rrl_eval_rollout_qs")
-            return
-        if self.maze:      # the env's own horizon ends a row: a launch argument of the Maze entry (T stays horizon + 1)
-            _lib.check(self.f.lib.rrl_eval_rollout_maze(C.byref(a), int(self.env.horizon), _lib.current_stream()),
-                       "rrl_eval_rollout_maze")
-            return
-        _lib.check(self.f.lib.rrl_eval_rollout(C.byref(a), _lib.current_stream()), "rrl_eval_rollout")
+        name, _, side = self.entry
+        _lib.check(getattr(self.f.lib, name)(C.byref(a), *([] if side is None else [side]), _lib.current_stream()), name)
 
     def stats(self, label):
         """The three means of the per-env arrays, as the module path takes them."""
@@ -1475,30 +1476,11 @@ def eval_rollouts_packed(rollouts, T):
     when the rollouts score in f16x3 -- all of them or none)."""
     if len({r.f16x3 for r in rollouts}) > 1:
         raise _lib.RRLError("eval_rollouts_packed: f16x3 and f32 rollouts in one call")
-    if rollouts[0].f16x3:
-        sqrl = rollouts[0].sqrl
-        args = ((_lib.rrl_eval_rollout_sqrl_t if sqrl else _lib.rrl_eval_rollout_qs_t) * len(rollouts))(*[r.desc(T) for r in rollouts])
-        streams = (C.c_void_p * len(rollouts))(*[r.qw2h.data_ptr() for r in rollouts])
-        entry = "rrl_eval_rollout_sqrl_f16x3_packed" if sqrl else "rrl_eval_rollout_qs_f16x3_packed"
-        _lib.check(getattr(_lib.load(), entry)(len(rollouts), args, streams, _lib.current_stream()), entry)
-        return
-    if rollouts[0].sqrl:
-        args = (_lib.rrl_eval_rollout_sqrl_t * len(rollouts))(*[r.desc(T) for r in rollouts])
-        _lib.check(_lib.load().rrl_eval_rollout_sqrl_packed(len(rollouts), args, _lib.current_stream()),
-                   "rrl_eval_rollout_sqrl_packed")
-        return
-    if rollouts[0].qsample:
-        args = (_lib.rrl_eval_rollout_qs_t * len(rollouts))(*[r.desc(T) for r in rollouts])
-        _lib.check(_lib.load().rrl_eval_rollout_qs_packed(len(rollouts), args, _lib.current_stream()),
-                   "rrl_eval_rollout_qs_packed")
-        return
-    args = (_lib.rrl_eval_rollout_t * len(rollouts))(*[r.desc(T) for r in rollouts])
-    if rollouts[0].maze:
-        horizon = (C.c_int * len(rollouts))(*[int(r.env.horizon) for r in rollouts])
-        _lib.check(_lib.load().rrl_eval_rollout_maze_packed(len(rollouts), args, horizon, _lib.current_stream()),
-                   "rrl_eval_rollout_maze_packed")
-        return
-    _lib.check(_lib.load().rrl_eval_rollout_packed(len(rollouts), args, _lib.current_stream()), "rrl_eval_rollout_packed")
+    name, desc_t, side = rollouts[0].entry
+    S = len(rollouts)
+    args = (desc_t * S)(*[r.desc(T) for r in rollouts])
+    sides = [] if side is None else [(type(side) * S)(*[r.entry[2] for r in rollouts])]
+    _lib.check(getattr(_lib.load(), name + "_packed")(S, args, *sides, _lib.current_stream()), name + "_packed")
 
 
 def uses_baseline_terms(cfg):

@@ -213,11 +213,21 @@ def test_lds_of_the_new_carve_ups():
     stack = {n: _value(n, roll, tile) for n in ("kLdsFloats", "kOffPart", "kWaves")}
     assert stack["kLdsFloats"] <= T16["kOffXs"]
     assert stack["kOffPart"] + 4 * stack["kWaves"] * 16 <= T16["kOffXs"]
-    # ... and the kernels are built on them
-    for name in ("QsLds<TileF16x3>::kBytes", "SqLds<TileF16x3>::kBytes", "kLdsFloats <= Tile::kOffXs",
-                 "kOffPart + 4 * kWaves * kRows <= Tile::kOffXs"):
+    # ... and the kernels are built on them: every form's trait declares the carve-up of its own tile as its LDS and its
+    # occupancy (two waves per SIMD for the four candidate forms, four for the base form) ...
+    for name in ("kLdsFloats <= Tile::kOffXs", "kOffPart + 4 * kWaves * kRows <= Tile::kOffXs"):
         assert name in ev, name
-    for kernel in ("qs", "sqrl"):
-        for form in ("", "_maze", "_pack", "_maze_pack"):
-            m = re.search(r"amdgpu_waves_per_eu\((\d), (\d)\)\)\)\s*void eval_rollout_%s_f16x3%s_kernel\(" % (kernel, form), ev)
-            assert m and m.groups() == ("2", "2"), (kernel, form)
+    forms = dict(re.findall(r"\nstruct (NoQs|QsOn|QsOnH|SqOn|SqOnH) \{(.*?)\n\};", ev, flags=re.S))
+    for form, (tile, lds) in {"QsOn": ("TileF32", "QsLds"), "QsOnH": ("TileF16x3", "QsLds"), "SqOn": ("TileF32", "SqLds"),
+                              "SqOnH": ("TileF16x3", "SqLds")}.items():
+        own = _constants(forms[form])
+        assert re.findall(r"using Tile = (\w+);", forms[form]) == [tile], form
+        assert own["kLds"] == lds + "<Tile>::kBytes" and own["kWavesPerEu"] == "2", form
+    base = _constants(forms["NoQs"])
+    assert base["kLds"] == "kLdsBytes" and base["kWavesPerEu"] == "4" and "Tile" not in forms["NoQs"]
+    # ... and the two kernel templates and the one launch take both from that declaration and from nowhere else
+    assert len(re.findall(r"__global__", re.sub(r"//[^\n]*", "", ev))) == 2
+    assert re.findall(r"amdgpu_waves_per_eu\(([^)]*)\)", ev) == ["Form::kWavesPerEu, Form::kWavesPerEu"] * 2
+    assert not re.search(r"amdgpu_waves_per_eu\(\s*\d", ev)
+    assert re.findall(r"hipLaunchKernelGGL\(kernel, [^,]*, dim3\(kThreads\), ([^,]*),", ev) == ["Form::kLds"]
+    assert ev.count("hipLaunchKernelGGL") == 1 and len(re.findall(r"grant_lds\(kernel, ([^,]*),", ev)) == 1

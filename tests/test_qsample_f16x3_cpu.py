@@ -58,7 +58,7 @@ def test_pack_site_is_appended():
     src = open(os.path.join(_lib.CSRC, "pack.hpp")).read()
     body = re.search(r"enum class Site : int \{(.*?)\};", src, flags=re.S).group(1)
     names = [n.split("=")[0].strip() for n in body.split(",") if n.strip()]
-    assert names == PARENT_SITES + ["QsampleActF16x3"]
+    assert names == PARENT_SITES + ["QsampleActF16x3", "EvalRolloutQsF16x3", "EvalRolloutSqrlF16x3"]
     assert re.search(r"HiddenBackward\s*=\s*1\b", body)
 
 
