@@ -6,6 +6,8 @@ import os
 
 import torch
 
+from .paths import switch
+
 METRIC_KEYS = ("env_steps", "episodes", "num_viols", "viol_and_recovery", "viol_and_no_recovery",
                "num_successes", "recovery_steps", "constraint_steps", "sac_updates", "qrisk_updates",
                "reward_sum", "episode_return_sum")
@@ -27,7 +29,7 @@ def init(backend=None, force=None):
     import torch.distributed as dist
     rank, local_rank, world = env_rank()
     if force is None:
-        force = os.environ.get("RRL_DIST_FORCE_INIT", "") not in ("", "0")
+        force = switch("RRL_DIST_FORCE_INIT")
     if world == 1 and force:
         _FORCED = True
     if (world > 1 or force) and not dist.is_initialized():

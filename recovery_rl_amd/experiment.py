@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import distributed as dist_utils
+from . import paths
 from .env import make_env, make_vec_env, register_env
 from .replay_memory import ConstraintReplayMemory, ReplayMemory
 from .sac import SAC
@@ -71,27 +72,14 @@ class VectorLoop:
         self.host_updates = [0, 0]        # SAC / Q_risk update counts are known on the host
         self._graph_updates = (0, 0)
         self._actor = None
-        self.carry_actor = os.environ.get("RRL_CARRY_ACTOR", "1") != "0"
+        self.carry_actor = paths.switch("RRL_CARRY_ACTOR")
         # the task batch's keys selected one step ahead, no draw launch (FastUpdater.update_pair); RRL_DRAW_AHEAD=0: off
-        self.draw_ahead = os.environ.get("RRL_DRAW_AHEAD", "1") != "0"
-        # SQRL's constraint-sampling acting pass on the rrl_sqrl_act kernel (RRL_FAST_SQRL=1, fast_update.sqrl_acting_path)
-        from .fast_update import sqrl_acting_path
-        self.sqrl_hip = bool(getattr(agent, "fast", None) is not None and sqrl_acting_path(cfg) == "hip"
-                             and agent.fast.qrisk.w2p is not None)
-        # ... with layer 2 of its scores in f16x3 (RRL_SQRL_F16X3=1, read once, here; ignored where the pass is not the kernel's)
-        from .fast_update import sqrl_f16x3_enabled
-        self.sqrl_f16x3 = bool(self.sqrl_hip and sqrl_f16x3_enabled())
-        # the acting pass of --Q_sampling_recovery on the rrl_qsample_act kernels (RRL_FAST_QSAMPLE=1, fast_update.qsample_acting_path)
-        from .fast_update import qsample_acting_path
-        self.qsample_hip = bool(getattr(agent, "fast", None) is not None and qsample_acting_path(cfg) == "hip"
-                                and agent.fast.qrisk.w2p is not None)
-        # ... with the recovery gate evaluated inside the qsample call (RRL_PACK_QSAMPLE=1, read once, here: what the loop
-        # runs is what vector_rules records)
-        from .fast_update import pack_qsample_enabled
-        self.qsample_gated = bool(self.qsample_hip and pack_qsample_enabled())
-        # ... with layer 2 of its scores in f16x3 (RRL_QSAMPLE_F16X3=1, read once, here; ignored where the pass is not the kernels')
-        from .fast_update import qsample_f16x3_enabled
-        self.qsample_f16x3 = bool(self.qsample_hip and qsample_f16x3_enabled())
+        self.draw_ahead = paths.switch("RRL_DRAW_AHEAD")
+        # the acting pass of the SQRL and Q-sampling lines: on their kernels or not, with f16x3 scores, with the recovery gate inside
+        # the qsample call -- the switches read once, here: what the loop runs is what vector_rules records (paths.acting)
+        fast = getattr(agent, "fast", None)
+        self.sqrl_hip, self.sqrl_f16x3, self.qsample_hip, self.qsample_gated, self.qsample_f16x3 = paths.acting(
+            cfg, fast is not None, fast is not None and fast.qrisk.w2p is not None)
         self._graph_ahead = False
         # vectorisation rule 5: at N > 1 an env's CEM warm start does not survive its episode (MPC.forget_plans)
         self.forget_plans = bool(recovery_policy is not None and self.n > 1 and hasattr(recovery_policy, "forget_plans")
@@ -662,8 +650,7 @@ class Experiment:
             self.nu_schedule = linear_schedule(exp_cfg.nu_start, exp_cfg.nu_end, exp_cfg.num_eps)
         else:
             self.nu_schedule = linear_schedule(exp_cfg.nu, exp_cfg.nu, 0)
-        from .fast_update import fast_path_supported
-        if fast_path_supported(exp_cfg) and not getattr(exp_cfg, "no_fast_path", False):
+        if paths.fast_path_supported(exp_cfg) and not getattr(exp_cfg, "no_fast_path", False):
             self.agent.enable_fast_path(exp_cfg.batch_size)
         # which update path ran (run_stats.pkl, the checkpoint): the comparison algorithms take the fused one under
         # RRL_FAST_BASELINES=1 only
@@ -672,23 +659,11 @@ class Experiment:
             self.agent.fast.enable_grad_sync(world_size)
         self.loop = VectorLoop(exp_cfg, self.env, self.agent, self.memory, self.recovery_memory,
                                self.recovery_policy, self.nu_schedule)
-        if exp_cfg.use_constraint_sampling:
-            # which code draws, scores and picks SQRL's candidates in the training loop (RRL_FAST_SQRL=1: the kernel)
-            self.vector_rules["sqrl_acting"] = "hip" if self.loop.sqrl_hip else "modules"
-            # ... and the arithmetic of the scores (RRL_SQRL_F16X3=1 on the kernel: layer 2 of Q_risk as three f16 products)
-            self.vector_rules["sqrl_scoring"] = "f16x3" if self.loop.sqrl_f16x3 else "f32"
-        if exp_cfg.use_recovery and exp_cfg.Q_sampling_recovery and not exp_cfg.MF_recovery:
-            # which code draws and scores the 1000 candidates of Q-sampling recovery in the training loop (RRL_FAST_QSAMPLE=1: the kernels)
-            self.vector_rules["qsample_acting"] = "hip" if self.loop.qsample_hip else "modules"
-            # ... and the arithmetic of the scores (RRL_QSAMPLE_F16X3=1 on the kernels: layer 2 of Q_risk as three f16 products)
-            self.vector_rules["qsample_scoring"] = "f16x3" if self.loop.qsample_f16x3 else "f32"
-            if self.loop.qsample_gated:
-                # where the recovery gate of that pass is evaluated (RRL_PACK_QSAMPLE=1: inside the qsample call)
-                self.vector_rules["qsample_gate"] = "in_launch"
+        # what the loop's acting pass runs on the SQRL and Q-sampling lines (sqrl_acting, sqrl_scoring, qsample_acting, ...)
+        self.vector_rules.update(paths.acting_rules(exp_cfg, self.loop))
         # the two evaluation-scoring switches (RRL_EVAL_SQRL_F16X3, RRL_EVAL_QSAMPLE_F16X3), read once, here: every evaluation
-        # of this experiment, and the resume warning, go by these values (fast_update.eval_scoring)
-        from .fast_update import eval_qsample_f16x3_enabled, eval_sqrl_f16x3_enabled
-        self.eval_f16x3_switches = (eval_sqrl_f16x3_enabled(), eval_qsample_f16x3_enabled())
+        # of this experiment, and the resume warning, go by these values (paths.eval_scoring)
+        self.eval_f16x3_switches = paths.eval_f16x3_switches()
 
     # -- setup -----------------------------------------------------------------------------------
     def experiment_setup(self):
@@ -743,10 +718,8 @@ class Experiment:
         # run_stats.pkl ("vector_rules") and the checkpoint
         self.vector_rules = {"demo_share": share if share > 0 else 0.0, "pinned_demonstrations": int(pinned),
                              **{k: self.vector_rules[k] for k in ("update_path", "replay_capacities", "cover_rows_limit",
-                                                                   "buffers_cover_the_run", "plan_warm_start", "sqrl_acting",
-                                                                   "sqrl_scoring",
-                                                                   "qsample_acting", "qsample_scoring", "qsample_gate",
-                                                                   "evaluation", "evaluation_scoring")
+                                                                   "buffers_cover_the_run", "plan_warm_start",
+                                                                   *paths.ACTING_RULES, "evaluation", "evaluation_scoring")
                                 if k in self.vector_rules}}
         if cfg.num_envs > 1:
             print("Q_risk batch: %s (--demo_share; 0 = the reference's single uniform draw, replay_memory.py:54-72)"
@@ -961,9 +934,8 @@ class Experiment:
                 print("WARNING: the checkpoint was written with --demo_share %g, this run continues with %g"
                       % (was, self.vector_rules["demo_share"]))
             # an evaluation changes no training state: the other evaluation scoring is no reason to refuse the checkpoint
-            from .fast_update import eval_scoring
             was = extra.get("vector_rules", {}).get("evaluation_scoring")
-            now = eval_scoring(cfg, self.eval_f16x3_switches)
+            now = paths.eval_scoring(cfg, self.eval_f16x3_switches)
             if was is not None and was != now:
                 print("WARNING: the checkpoint was written with evaluation scoring %s, this run continues with %s" % (was, now))
             print("Resumed from %s at iteration %d (%d env-steps)" % (cfg.resume, it, loop.total_numsteps))
@@ -1136,10 +1108,10 @@ class Experiment:
 
     def eval_rollout(self):
         """The EvalRollout of this experiment's evaluation env when evaluation runs on the kernel
-        (fast_update.eval_rollout_path), else None: the module code below."""
-        from .fast_update import EvalRollout, eval_qsample_line, eval_rollout_path, eval_scoring, eval_sqrl_line
+        (paths.eval_rollout_path), else None: the module code below."""
+        from .fast_update import EvalRollout
         cfg = self.exp_cfg
-        if eval_rollout_path(cfg) != "hip" or getattr(self.agent, "fast", None) is None:
+        if paths.eval_rollout_path(cfg) != "hip" or getattr(self.agent, "fast", None) is None:
             return None
         if getattr(self, "_eval_rollout", None) is None:
             # (eval_rollout_path said "hip" for the Q-sampling line: RRL_FAST_EVAL_QSAMPLE=1 -> rrl_eval_rollout_qs; for the
@@ -1147,8 +1119,8 @@ class Experiment:
             # (RRL_EVAL_QSAMPLE_F16X3=1 / RRL_EVAL_SQRL_F16X3=1 on those lines: their _f16x3 entries, by the switches as the
             # constructor read them)
             self._eval_rollout = EvalRollout(self.agent.fast, self.eval_env(), cfg.eps_safe, cfg.use_recovery,
-                                             qsample=eval_qsample_line(cfg), sqrl=eval_sqrl_line(cfg),
-                                             f16x3=eval_scoring(cfg, self.eval_f16x3_switches) == "f16x3")
+                                             qsample=paths.qsample_line(cfg), sqrl=paths.sqrl_line(cfg),
+                                             f16x3=paths.eval_scoring(cfg, self.eval_f16x3_switches) == "f16x3")
         self.vector_rules["evaluation"] = "hip"
         if self._eval_rollout.qsample or self._eval_rollout.sqrl:
             self.vector_rules["evaluation_scoring"] = "f16x3" if self._eval_rollout.f16x3 else "f32"
@@ -1221,79 +1193,45 @@ def run_packed(exp_cfg, rank=0, world_size=1):
     nu_schedule(1) (the lock-step loop has no episode index; the recorded launches carry that value).  SQRL
     (--DGD_constraints --use_constraint_sampling --update_nu) packs under RRL_PACK_SQRL=1 (opt-in): its update is LR's, its
     acting pass one rrl_sqrl_act_packed launch -- so it needs that pass on the kernel (RRL_FAST_SQRL=1 with
-    RRL_FAST_BASELINES=1, no recovery policy, --hidden_size 256: fast_update.sqrl_acting_path) and at most 8 seeds (the launch
+    RRL_FAST_BASELINES=1, no recovery policy, --hidden_size 256: paths.sqrl_acting_path) and at most 8 seeds (the launch
     reads Q_risk's fragment-order W2 copy, which packed runs keep up to 8 seeds); every seed's run_stats.pkl then records
     vector_rules["sqrl_acting"] == "hip" (and "sqrl_scoring": with RRL_SQRL_F16X3=1 the stage is rrl_sqrl_act_f16x3_packed behind
     the seeds' rrl_w2_pack_f16x3 calls, within the same limits).  Q-sampling recovery (--use_recovery --Q_sampling_recovery) packs under
     RRL_PACK_QSAMPLE=1 (opt-in): its acting pass is then a policy forward, a Q_risk forward and one rrl_qsample_act_packed stage
     that evaluates the recovery gate itself -- so it needs that pass on the kernels (RRL_FAST_QSAMPLE=1, --hidden_size 256, no
-    --MF_recovery: fast_update.qsample_acting_path) and at most 8 seeds; run_stats.pkl records vector_rules["qsample_gate"] ==
+    --MF_recovery: paths.qsample_acting_path) and at most 8 seeds; run_stats.pkl records vector_rules["qsample_gate"] ==
     "in_launch" (and "qsample_scoring": with RRL_QSAMPLE_F16X3=1 the stage is rrl_qsample_act_f16x3_packed behind the seeds'
     rrl_w2_pack_f16x3 calls, within the same limits).  Not packed: --use_constraint_sampling and --Q_sampling_recovery without their switches or outside those
     limits (their acting passes are module code then), model-based recovery, --dp_mode env_shard, --resume /
     --checkpoint_every."""
     import copy
-    from .fast_update import (eval_rollouts_packed, fast_baselines_enabled, fast_path_supported, fast_qsample_enabled,
-                              fast_sqrl_enabled, pack_qsample_enabled, pack_sqrl_enabled, qsample_acting_path, sqrl_acting_path,
-                              uses_baseline_terms)
+    from .fast_update import eval_rollouts_packed
     from .packed import PackedLoop
     S = int(exp_cfg.seeds_per_gpu)
     if exp_cfg.num_envs < 2:
         raise ValueError("--seeds_per_gpu needs the lock-step loop (--num_envs > 1)")
-    if exp_cfg.use_constraint_sampling and not pack_sqrl_enabled():
+    if exp_cfg.use_constraint_sampling and not paths.switch("RRL_PACK_SQRL"):
         raise ValueError("--seeds_per_gpu does not pack --use_constraint_sampling (SQRL's acting pass draws its candidates "
                          "through module code, or with RRL_FAST_SQRL=1 in a launch that has no packed form): run the seeds "
                          "one at a time")
-    if exp_cfg.use_constraint_sampling:
-        # RRL_PACK_SQRL=1: the acting pass has to be the kernel (one packed launch), within the limits of its packed form
-        missing = None
-        if not fast_sqrl_enabled():
-            missing = "the acting pass on the rrl_sqrl_act kernel: set RRL_FAST_SQRL=1"
-        elif not fast_baselines_enabled():
-            missing = "the fused update path: set RRL_FAST_BASELINES=1"
-        elif exp_cfg.use_recovery:
-            missing = "a run without a recovery policy (--use_recovery takes SQRL's acting pass through module code)"
-        elif int(exp_cfg.hidden_size) != 256:
-            missing = "--hidden_size 256 (the kernel's Q_risk width; got %d)" % int(exp_cfg.hidden_size)
-        elif sqrl_acting_path(exp_cfg) != "hip":
-            missing = ("the acting pass on the rrl_sqrl_act kernel (Gaussian policy, fixed alpha, --target_update_interval 1, "
-                       "no --no_fast_path, RRL_W2_FRAG not 0)")
-        elif S > PackedLoop.FRAG_MAX_SEEDS:
-            missing = ("at most %d seeds per GPU (its launch reads Q_risk's fragment-order W2 copy, which packed runs keep up "
-                       "to that many seeds; got %d)" % (PackedLoop.FRAG_MAX_SEEDS, S))
+    # RRL_PACK_SQRL=1 / RRL_PACK_QSAMPLE=1: the acting pass has to be the kernel's (one packed launch or stage), within the limits
+    # of its packed form
+    qsample = bool(exp_cfg.use_recovery and exp_cfg.Q_sampling_recovery and paths.switch("RRL_PACK_QSAMPLE"))
+    for packs, needs, what in ((exp_cfg.use_constraint_sampling, paths.SQRL_NEEDS, "RRL_PACK_SQRL=1 packs --use_constraint_sampling"),
+                               (qsample, paths.QSAMPLE_NEEDS, "RRL_PACK_QSAMPLE=1 packs --Q_sampling_recovery")):
+        missing = paths.missing(needs, exp_cfg, S) if packs else None
         if missing:
-            raise ValueError("--seeds_per_gpu with RRL_PACK_SQRL=1 packs --use_constraint_sampling only with " + missing)
-    qsample = bool(exp_cfg.use_recovery and exp_cfg.Q_sampling_recovery and pack_qsample_enabled())
-    if qsample:
-        # RRL_PACK_QSAMPLE=1: the acting pass has to be the kernels (one packed stage), within the limits of the packed form
-        missing = None
-        if not fast_qsample_enabled():
-            missing = "the acting pass on the rrl_qsample_act kernels: set RRL_FAST_QSAMPLE=1"
-        elif exp_cfg.MF_recovery:
-            missing = ("a run without --MF_recovery (the model-free recovery policy wins over --Q_sampling_recovery, and packs "
-                       "without this switch)")
-        elif exp_cfg.use_constraint_sampling:
-            missing = "a run without --use_constraint_sampling (SQRL's acting pass is another one)"
-        elif int(exp_cfg.hidden_size) != 256:
-            missing = "--hidden_size 256 (the kernels' Q_risk width; got %d)" % int(exp_cfg.hidden_size)
-        elif qsample_acting_path(exp_cfg) != "hip":
-            missing = ("the acting pass on the rrl_qsample_act kernels (Gaussian policy, fixed alpha, --target_update_interval "
-                       "1, no --no_fast_path, RRL_W2_FRAG not 0)")
-        elif S > PackedLoop.FRAG_MAX_SEEDS:
-            missing = ("at most %d seeds per GPU (its launch reads Q_risk's fragment-order W2 copy, which packed runs keep up "
-                       "to that many seeds; got %d)" % (PackedLoop.FRAG_MAX_SEEDS, S))
-        if missing:
-            raise ValueError("--seeds_per_gpu with RRL_PACK_QSAMPLE=1 packs --Q_sampling_recovery only with " + missing)
+            raise ValueError("--seeds_per_gpu with %s only with %s" % (what, missing))
     if exp_cfg.use_recovery and not exp_cfg.MF_recovery and not qsample:
         raise ValueError("--seeds_per_gpu packs the model-free recovery policy only (--use_recovery needs --MF_recovery; "
                          "model-based recovery and --Q_sampling_recovery run one seed at a time)")
     if getattr(exp_cfg, "dp_mode", "replicas") != "replicas":
         raise ValueError("--seeds_per_gpu does not combine with --dp_mode env_shard (every rank of a multi-GPU launch packs "
                          "its own seeds: replicas, no exchange)")
-    if uses_baseline_terms(exp_cfg) and not fast_baselines_enabled():
+    if paths.uses_baseline_terms(exp_cfg) and not paths.switch("RRL_FAST_BASELINES"):
         raise ValueError("--seeds_per_gpu packs the comparison algorithms (--DGD_constraints, --update_nu, --nu_schedule, "
                          "--RCPO) on the fused update path only: set RRL_FAST_BASELINES=1")
-    if not fast_path_supported(exp_cfg) or getattr(exp_cfg, "no_fast_path", False):
+    if not paths.fast_path_supported(exp_cfg) or getattr(exp_cfg, "no_fast_path", False):
         raise ValueError("--seeds_per_gpu needs the fused update path (Gaussian policy, fixed alpha, "
                          "--target_update_interval 1, no --no_fast_path)")
     if getattr(exp_cfg, "resume", "") or getattr(exp_cfg, "checkpoint_every", 0):
@@ -1324,7 +1262,7 @@ def run_packed(exp_cfg, rank=0, world_size=1):
         exps.append(exp)
     cfg = exp_cfg
     histories = [[] for _ in exps]
-    # RRL_FAST_EVAL=1 (fast_update.eval_rollout_path): every seed evaluates every 10 episodes per env, as its solo run, and the
+    # RRL_FAST_EVAL=1 (paths.eval_rollout_path): every seed evaluates every 10 episodes per env, as its solo run, and the
     # seeds due at a log point go out as ONE rrl_eval_rollout_packed launch; otherwise packed runs do not evaluate
     rollouts = [e.eval_rollout() for e in exps] if cfg.eval else [None] * S
     evals = [[] for _ in exps]

@@ -16,12 +16,17 @@ import math
 
 import ctypes as C
 
-import os
-
 import torch
 
-from . import _lib
+from . import _lib, paths
 from .fused import NN, NT, TN, gemm, mlp3_forward, mlp3_supported
+# the switches and path decisions live in paths.py; the names below stay importable from here
+from .paths import (BASELINE_FLAGS, eval_qsample_f16x3_enabled, eval_qsample_line, eval_rollout_path,  # noqa: F401
+                    eval_scoring, eval_sqrl_f16x3_enabled, eval_sqrl_line, fast_baselines_enabled, fast_eval_enabled,
+                    fast_eval_maze_enabled, fast_eval_qsample_enabled, fast_eval_sqrl_enabled, fast_path_supported,
+                    fast_qsample_enabled, fast_sqrl_enabled, pack_qsample_enabled, pack_sqrl_enabled, qsample_acting_path,
+                    qsample_f16x3_enabled, qsample_scoring, sqrl_acting_path, sqrl_f16x3_enabled, sqrl_scoring,
+                    uses_baseline_terms)
 
 
 # -- launch tape (seed packing, recovery_rl_amd/packed.py) -----------------------------------------------------------
@@ -72,7 +77,7 @@ class FlatNet:
         shape = self.shapes.get("W2")
         self.w2p = None
         if shape is not None and len(shape) == 3 and shape[1] == shape[2] == 256 and self.offset["W2"] % 4 == 0 \
-                and torch.device(device).type == "cuda" and os.environ.get("RRL_W2_FRAG", "1") != "0":   # (0: A/B runs of profiles/)
+                and torch.device(device).type == "cuda" and paths.switch("RRL_W2_FRAG"):
             self.w2p = torch.empty(int(torch.Size(shape).numel()), dtype=torch.float32, device=device)
 
     def w2_packed(self):
@@ -930,6 +935,18 @@ class FastUpdater:
         return self.losses
 
 
+# The acting launches of the SQRL and Q-sampling lines: (line, gate inside the call, f16x3 scores) -> (tape kind, entry point).
+# The packed entry of a kind (packed.PackedLoop) is the stand-alone name plus "_packed"; the gated entries' drops "_gated" (the
+# packed Q-sampling stage exists with the gate inside it only).
+ACT_ENTRIES = {("sqrl", False, False): ("sqrl", "rrl_sqrl_act"),
+               ("sqrl", False, True): ("sqrl_f16x3", "rrl_sqrl_act_f16x3"),
+               ("qsample", False, False): ("qsample", "rrl_qsample_act"),
+               ("qsample", True, False): ("qsample", "rrl_qsample_act_gated"),
+               ("qsample", False, True): ("qsample_f16x3", "rrl_qsample_act_f16x3"),
+               ("qsample", True, True): ("qsample_f16x3", "rrl_qsample_act_gated_f16x3")}
+ACT_PACKED = {kind: entry.replace("_gated", "") + "_packed" for kind, entry in ACT_ENTRIES.values()}
+
+
 class FastActor:
     """Batched get_action (experiment.py:546-577) for N envs on the fused kernels: task policy sample,
     Q_risk of (s, a_task), model-free recovery action and the recovery gate -- 8 launches instead of
@@ -1077,21 +1094,28 @@ class FastActor:
                                 action=p(self.task_action), **{name: p(t) for name, t in d.items()})
         self._sqrl_args = a              # keeps the argument block alive until the launch has been issued (and for profiles/)
         if self.sqrl_f16x3:
-            # layer 2 of the scores in f16x3: the hi / lo fragment stream of the live W2, re-made in front of every launch (inside
-            # the captured graph; no optimiser launch keeps it current), then the f16x3 kernel on the same descriptor
-            if self.sqrl_w2h is None:
-                self.sqrl_w2h = torch.empty(P["W2"].numel(), dtype=torch.float32, device=f.dev)
-            a.W2p = p(self.sqrl_w2h)
-            W2 = P["W2"]
-            pack = (W2.shape[0], W2.shape[1], p(W2), p(self.sqrl_w2h))
-            record("call", f.lib.rrl_w2_pack_f16x3, pack, (W2, self.sqrl_w2h))
-            _lib.check(f.lib.rrl_w2_pack_f16x3(*pack, _lib.current_stream()), "rrl_w2_pack_f16x3")
-            record("sqrl_f16x3", a)
-            _lib.check(f.lib.rrl_sqrl_act_f16x3(C.byref(a), _lib.current_stream()), "rrl_sqrl_act_f16x3")
-            return self.task_action
-        record("sqrl", a)
-        _lib.check(f.lib.rrl_sqrl_act(C.byref(a), _lib.current_stream()), "rrl_sqrl_act")
+            self._f16x3_stream(a, "sqrl_w2h")
+        self._launch("sqrl", False, self.sqrl_f16x3, a)
         return self.task_action
+
+    def _f16x3_stream(self, a, attr):
+        """Layer 2 of the scores of descriptor `a` in f16x3: the hi / lo fragment stream of Q_risk's live W2 (this actor's `attr`,
+        made at the first pass) takes the place of a.W2p and is re-made in front of every launch (inside the captured graph; no
+        optimiser launch keeps it current) by a call the tape records."""
+        f, W2 = self.f, self.f.qrisk.p["W2"]
+        if getattr(self, attr) is None:
+            setattr(self, attr, torch.empty(W2.numel(), dtype=torch.float32, device=f.dev))
+        w2h = getattr(self, attr)
+        a.W2p = _lib.ptr(w2h)
+        pack = (W2.shape[0], W2.shape[1], _lib.ptr(W2), _lib.ptr(w2h))
+        record("call", f.lib.rrl_w2_pack_f16x3, pack, (W2, w2h))
+        _lib.check(f.lib.rrl_w2_pack_f16x3(*pack, _lib.current_stream()), "rrl_w2_pack_f16x3")
+
+    def _launch(self, line, gated, f16x3, *blocks):
+        """The acting launch of `line` on its argument blocks: recorded under its tape kind, issued and checked (ACT_ENTRIES)."""
+        kind, entry = ACT_ENTRIES[line, bool(gated), bool(f16x3)]
+        record(kind, *blocks)
+        _lib.check(getattr(self.f.lib, entry)(*map(C.byref, blocks), _lib.current_stream()), entry)
 
     def act_qsample(self, obs, eps_safe, k=1000, cand=None, diag=None, gated=False):
         """Q-sampling recovery (QRiskWrapper.select_action, qrisk.py:214-225) for the n envs on the fused kernels: the sequence of
@@ -1128,31 +1152,10 @@ class FastActor:
                                    **{name: p(t) for name, t in d.items()})
         self._qsample_args = a           # keeps the argument block alive until the launch has been issued (and for profiles/)
         if self.qsample_f16x3:
-            # layer 2 of the scores in f16x3: the hi / lo fragment stream of the live W2, re-made in front of every launch (inside
-            # the captured graph; no optimiser launch keeps it current), then the f16x3 kernels on the same descriptor(s)
-            if self.qsample_w2h is None:
-                self.qsample_w2h = torch.empty(P["W2"].numel(), dtype=torch.float32, device=f.dev)
-            a.W2p = p(self.qsample_w2h)
-            W2 = P["W2"]
-            pack = (W2.shape[0], W2.shape[1], p(W2), p(self.qsample_w2h))
-            record("call", f.lib.rrl_w2_pack_f16x3, pack, (W2, self.qsample_w2h))
-            _lib.check(f.lib.rrl_w2_pack_f16x3(*pack, _lib.current_stream()), "rrl_w2_pack_f16x3")
-            if gated:
-                self._qsample_gate_args = gate
-                record("qsample_f16x3", a, gate)
-                _lib.check(f.lib.rrl_qsample_act_gated_f16x3(C.byref(a), C.byref(gate), _lib.current_stream()),
-                           "rrl_qsample_act_gated_f16x3")
-            else:
-                record("qsample_f16x3", a)
-                _lib.check(f.lib.rrl_qsample_act_f16x3(C.byref(a), _lib.current_stream()), "rrl_qsample_act_f16x3")
-            return self.task_action, self.real_action, self.recovery
+            self._f16x3_stream(a, "qsample_w2h")
         if gated:
             self._qsample_gate_args = gate
-            record("qsample", a, gate)
-            _lib.check(f.lib.rrl_qsample_act_gated(C.byref(a), C.byref(gate), _lib.current_stream()), "rrl_qsample_act_gated")
-            return self.task_action, self.real_action, self.recovery
-        record("qsample", a)
-        _lib.check(f.lib.rrl_qsample_act(C.byref(a), _lib.current_stream()), "rrl_qsample_act")
+        self._launch("qsample", gated, self.qsample_f16x3, *((a, gate) if gated else (a,)))
         return self.task_action, self.real_action, self.recovery
 
     def _qsample_gate(self, obs, eps_safe):
@@ -1199,165 +1202,6 @@ def dual_state(opt, param):
         st["exp_avg"] = torch.zeros_like(param, memory_format=torch.preserve_format)
         st["exp_avg_sq"] = torch.zeros_like(param, memory_format=torch.preserve_format)
     return st
-
-
-BASELINE_FLAGS = ("DGD_constraints", "update_nu", "nu_schedule", "use_constraint_sampling", "RCPO")
-
-
-def fast_baselines_enabled():
-    """RRL_FAST_BASELINES=1: the comparison algorithms (LR, RSPO, SQRL, RCPO) take the fused update path too (opt-in)."""
-    return os.environ.get("RRL_FAST_BASELINES", "0") == "1"
-
-
-def fast_sqrl_enabled():
-    """RRL_FAST_SQRL=1: SQRL's constraint-sampling acting pass on the rrl_sqrl_act kernel (opt-in; sqrl_acting_path)."""
-    return os.environ.get("RRL_FAST_SQRL", "0") == "1"
-
-
-def pack_sqrl_enabled():
-    """RRL_PACK_SQRL=1: --seeds_per_gpu packs SQRL (--use_constraint_sampling), its acting pass as one rrl_sqrl_act_packed
-    launch (opt-in; needs sqrl_acting_path(cfg) == "hip" and at most 8 seeds: experiment.run_packed)."""
-    return os.environ.get("RRL_PACK_SQRL", "0") == "1"
-
-
-def sqrl_f16x3_enabled():
-    """RRL_SQRL_F16X3=1: the rrl_sqrl_act acting pass scores its candidates with layer 2 of Q_risk in f16x3
-    (rrl_sqrl_act_f16x3; opt-in).  Read once, when the loop is built; it matters only where sqrl_acting_path(cfg) == "hip"."""
-    return os.environ.get("RRL_SQRL_F16X3", "0") == "1"
-
-
-def sqrl_scoring(cfg):
-    """The arithmetic of the kernel acting pass's scores: "f16x3" under RRL_SQRL_F16X3=1 where sqrl_acting_path(cfg) == "hip",
-    else "f32" (the module path's too)."""
-    return "f16x3" if sqrl_f16x3_enabled() and sqrl_acting_path(cfg) == "hip" else "f32"
-
-
-def sqrl_acting_path(cfg):
-    """Where the training actions of --use_constraint_sampling come from: "hip" (FastActor.act_sqrl) under RRL_FAST_SQRL=1
-    on the fused path (RRL_FAST_BASELINES=1), without a recovery policy, at hidden width 256; else "modules"
-    (SAC._sqrl_action), which evaluation, the one-state call and every other configuration keep."""
-    hip = (fast_sqrl_enabled() and fast_baselines_enabled() and bool(cfg.use_constraint_sampling)
-           and not cfg.use_recovery and int(cfg.hidden_size) == 256 and fast_path_supported(cfg)
-           and not getattr(cfg, "no_fast_path", False) and os.environ.get("RRL_W2_FRAG", "1") != "0")
-    return "hip" if hip else "modules"
-
-
-def fast_qsample_enabled():
-    """RRL_FAST_QSAMPLE=1: the acting pass of --Q_sampling_recovery on the rrl_qsample_act kernels (opt-in; qsample_acting_path)."""
-    return os.environ.get("RRL_FAST_QSAMPLE", "0") == "1"
-
-
-def pack_qsample_enabled():
-    """RRL_PACK_QSAMPLE=1: the acting pass of --Q_sampling_recovery with the recovery gate evaluated inside the qsample call
-    (rrl_qsample_act_gated: three launches the tape records), and --seeds_per_gpu packs that line, its acting call as one
-    rrl_qsample_act_packed stage (opt-in; needs qsample_acting_path(cfg) == "hip" and at most 8 seeds: experiment.run_packed)."""
-    return os.environ.get("RRL_PACK_QSAMPLE", "0") == "1"
-
-
-def qsample_f16x3_enabled():
-    """RRL_QSAMPLE_F16X3=1: the rrl_qsample_act acting pass scores its candidates with layer 2 of Q_risk in f16x3
-    (rrl_qsample_act_f16x3; opt-in).  Read once, when the loop is built; it matters only where qsample_acting_path(cfg) == "hip"
-    (the random-action phase keeps its f32 code whatever it says; evaluation has a switch of its own: eval_scoring)."""
-    return os.environ.get("RRL_QSAMPLE_F16X3", "0") == "1"
-
-
-def qsample_scoring(cfg):
-    """The arithmetic of the kernel acting pass's scores: "f16x3" under RRL_QSAMPLE_F16X3=1 where qsample_acting_path(cfg) ==
-    "hip", else "f32" (the module path's too)."""
-    return "f16x3" if qsample_f16x3_enabled() and qsample_acting_path(cfg) == "hip" else "f32"
-
-
-def qsample_acting_path(cfg):
-    """Where the recovery actions of --use_recovery --Q_sampling_recovery come from in the training loop: "hip"
-    (FastActor.act_qsample) under RRL_FAST_QSAMPLE=1 on the fused path at hidden width 256; else "modules"
-    (QRiskWrapper.select_action), which evaluation, the one-state call and every other configuration keep.  --MF_recovery wins
-    over --Q_sampling_recovery in the module code, so it does here."""
-    hip = (fast_qsample_enabled() and bool(cfg.use_recovery) and bool(cfg.Q_sampling_recovery) and not cfg.MF_recovery
-           and not cfg.use_constraint_sampling and int(cfg.hidden_size) == 256 and fast_path_supported(cfg)
-           and not getattr(cfg, "no_fast_path", False) and os.environ.get("RRL_W2_FRAG", "1") != "0")
-    return "hip" if hip else "modules"
-
-
-def fast_eval_enabled():
-    """RRL_FAST_EVAL=1: policy evaluation as one rrl_eval_rollout launch (opt-in; eval_rollout_path)."""
-    return os.environ.get("RRL_FAST_EVAL", "0") == "1"
-
-
-def fast_eval_maze_enabled():
-    """RRL_FAST_EVAL_MAZE=1, on top of RRL_FAST_EVAL=1: Maze evaluates on rrl_eval_rollout_maze (opt-in; eval_rollout_path)."""
-    return os.environ.get("RRL_FAST_EVAL_MAZE", "0") == "1"
-
-
-def fast_eval_qsample_enabled():
-    """RRL_FAST_EVAL_QSAMPLE=1, on top of RRL_FAST_EVAL=1: --Q_sampling_recovery evaluates on rrl_eval_rollout_qs (opt-in;
-    eval_rollout_path)."""
-    return os.environ.get("RRL_FAST_EVAL_QSAMPLE", "0") == "1"
-
-
-def eval_qsample_line(cfg):
-    """The configuration whose evaluation draws Q-sampling candidates: --use_recovery --Q_sampling_recovery without
-    --MF_recovery (model-free wins in the module code) and without --use_constraint_sampling."""
-    return (bool(cfg.use_recovery) and bool(getattr(cfg, "Q_sampling_recovery", False)) and not cfg.MF_recovery
-            and not cfg.use_constraint_sampling)
-
-
-def fast_eval_sqrl_enabled():
-    """RRL_FAST_EVAL_SQRL=1, on top of RRL_FAST_EVAL=1: --use_constraint_sampling evaluates on rrl_eval_rollout_sqrl (opt-in;
-    eval_rollout_path)."""
-    return os.environ.get("RRL_FAST_EVAL_SQRL", "0") == "1"
-
-
-def eval_sqrl_line(cfg):
-    """The configuration whose evaluation is SAC._sqrl_action on every step: --use_constraint_sampling without a recovery
-    policy."""
-    return bool(cfg.use_constraint_sampling) and not cfg.use_recovery
-
-
-def eval_rollout_path(cfg):
-    """Where Experiment.get_test_rollout_vectorized runs: "hip" (EvalRollout: one launch) under RRL_FAST_EVAL=1 on the fused
-    path at hidden width 256, Navigation 1 / 2 -- or Maze with RRL_FAST_EVAL_MAZE=1 as well --, the lock-step loop, without
-    a recovery policy, with the model-free one, -- with RRL_FAST_EVAL_QSAMPLE=1 as well, whatever RRL_FAST_QSAMPLE says --
-    with Q-sampling recovery, or -- with RRL_FAST_EVAL_SQRL=1 as well, whatever RRL_FAST_SQRL says -- SQRL without a recovery
-    policy; else "modules" (the loop's act() on the torch modules and the eager env), which SQRL with a recovery policy,
-    model-based recovery and every other configuration keep."""
-    envs = ("navigation1", "navigation2") + (("maze",) if fast_eval_maze_enabled() else ())
-    common = (fast_eval_enabled() and fast_path_supported(cfg) and not getattr(cfg, "no_fast_path", False)
-              and int(cfg.hidden_size) == 256 and cfg.env_name in envs and int(getattr(cfg, "num_envs", 1)) > 1)
-    if cfg.use_constraint_sampling:
-        hip = common and fast_eval_sqrl_enabled() and eval_sqrl_line(cfg)
-    else:
-        hip = common and (not cfg.use_recovery or bool(cfg.MF_recovery)
-                          or (fast_eval_qsample_enabled() and eval_qsample_line(cfg)))
-    return "hip" if hip else "modules"
-
-
-def eval_sqrl_f16x3_enabled():
-    """RRL_EVAL_SQRL_F16X3=1, on top of RRL_FAST_EVAL=1 RRL_FAST_EVAL_SQRL=1: the SQRL evaluation scores its candidates in
-    f16x3 (rrl_eval_rollout_sqrl_f16x3; opt-in, independent of RRL_SQRL_F16X3).  An Experiment reads it once, when it builds its
-    loop (Experiment.eval_f16x3_switches), and evaluates by that value from then on."""
-    return os.environ.get("RRL_EVAL_SQRL_F16X3", "0") == "1"
-
-
-def eval_qsample_f16x3_enabled():
-    """RRL_EVAL_QSAMPLE_F16X3=1, on top of RRL_FAST_EVAL=1 RRL_FAST_EVAL_QSAMPLE=1: the Q-sampling evaluation scores its
-    candidates in f16x3 (rrl_eval_rollout_qs_f16x3; opt-in, independent of RRL_QSAMPLE_F16X3).  An Experiment reads it once, when
-    it builds its loop (Experiment.eval_f16x3_switches), and evaluates by that value from then on."""
-    return os.environ.get("RRL_EVAL_QSAMPLE_F16X3", "0") == "1"
-
-
-def eval_scoring(cfg, switches=None):
-    """The arithmetic of the evaluation rollout's candidate scores: "f16x3" on the SQRL line under RRL_EVAL_SQRL_F16X3=1 and on
-    the Q-sampling line under RRL_EVAL_QSAMPLE_F16X3=1, where eval_rollout_path(cfg) == "hip"; else "f32" (the module path's
-    too, and every configuration that scores no candidates).  `switches` = (SQRL, Q-sampling): the two switches as read
-    earlier (an Experiment's, from when its loop was built); None: the environment now."""
-    sqrl, qsample = (eval_sqrl_f16x3_enabled(), eval_qsample_f16x3_enabled()) if switches is None else switches
-    if eval_rollout_path(cfg) != "hip":
-        return "f32"
-    if eval_sqrl_line(cfg):
-        return "f16x3" if sqrl else "f32"
-    if eval_qsample_line(cfg):
-        return "f16x3" if qsample else "f32"
-    return "f32"
 
 
 class EvalRollout:
@@ -1481,16 +1325,3 @@ def eval_rollouts_packed(rollouts, T):
     args = (desc_t * S)(*[r.desc(T) for r in rollouts])
     sides = [] if side is None else [(type(side) * S)(*[r.entry[2] for r in rollouts])]
     _lib.check(getattr(_lib.load(), name + "_packed")(S, args, *sides, _lib.current_stream()), name + "_packed")
-
-
-def uses_baseline_terms(cfg):
-    return any(bool(getattr(cfg, f, False)) for f in BASELINE_FLAGS)
-
-
-def fast_path_supported(cfg):
-    """The fused path covers the Recovery-RL configurations (task SAC + Q_risk, model-free or
-    model-based recovery, reward penalty); the comparison algorithms (BASELINE_FLAGS) use the autograd path
-    unless RRL_FAST_BASELINES=1."""
-    return (cfg.policy == "Gaussian" and not cfg.automatic_entropy_tuning
-            and (fast_baselines_enabled() or not uses_baseline_terms(cfg))
-            and cfg.target_update_interval == 1 and not getattr(cfg, "cnn", False))

@@ -16,7 +16,7 @@ import os
 import torch
 
 from . import _lib
-from . import fast_update
+from . import fast_update, paths
 from .fast_update import FLAT_NETS
 
 
@@ -25,7 +25,7 @@ class PackedLoop:
     # seeds up to which the library issues a head + hidden backward as ONE launch (csrc pack_pair_block_max_seeds)
     PAIR_MAX_SEEDS = int(os.environ.get("RRL_PACK_PAIR_BLOCK_MAX_SEEDS", "8"))
 
-    FRAG_MAX_SEEDS = 8
+    FRAG_MAX_SEEDS = paths.FRAG_MAX_SEEDS
 
     def __init__(self, loops, online_qrisk=True):
         """loops: VectorLoops in steady state (past start_steps, batch available), each on the fused grouped path."""
@@ -33,17 +33,11 @@ class PackedLoop:
             raise ValueError("1 .. %d seeds per GPU" % self.MAX_SEEDS)
         self.loops = list(loops)
         self.S = len(loops)
-        # SQRL's packed acting launch (rrl_sqrl_act_packed; its f16x3 form keeps the limit) reads Q_risk's fragment-order W2 copy,
-        # which the nets give up beyond FRAG_MAX_SEEDS (below)
-        if self.S > self.FRAG_MAX_SEEDS and any(getattr(loop, "sqrl_hip", False) for loop in self.loops):
-            raise ValueError("SQRL's constraint-sampling acting pass (rrl_sqrl_act_packed) packs at most %d seeds per GPU: it "
-                             "reads the fragment-order W2 copy of Q_risk, which packed runs keep up to that many seeds only "
-                             "(got %d)" % (self.FRAG_MAX_SEEDS, self.S))
-        # ... and so does the Q-sampling recovery call (rrl_qsample_act_packed)
-        if self.S > self.FRAG_MAX_SEEDS and any(getattr(loop, "qsample_hip", False) for loop in self.loops):
-            raise ValueError("the Q-sampling recovery acting pass (rrl_qsample_act_packed) packs at most %d seeds per GPU: it "
-                             "reads the fragment-order W2 copy of Q_risk, which packed runs keep up to that many seeds only "
-                             "(got %d)" % (self.FRAG_MAX_SEEDS, self.S))
+        # the packed acting launches of the SQRL and Q-sampling lines (their f16x3 forms keep the limit) read Q_risk's
+        # fragment-order W2 copy, which the nets give up beyond FRAG_MAX_SEEDS (below)
+        for flag, text in paths.PACKED_SEED_LIMITS:
+            if self.S > self.FRAG_MAX_SEEDS and any(getattr(loop, flag, False) for loop in self.loops):
+                raise ValueError(text % (self.FRAG_MAX_SEEDS, self.S))
         self.online_qrisk = online_qrisk
         self.lib = _lib.load()
         self.graph = None
@@ -135,26 +129,16 @@ class PackedLoop:
                 n = (C.c_int * S)(*[op[2] for op in ops])
                 heads = (p(_lib.rrl_policy_head_t) * S)(*[C.cast(op[1], p(_lib.rrl_policy_head_t)) for op in ops])
                 stages.append((self.lib.rrl_policy_heads_fwd_multi_packed, (S, n, heads), ops))
-            elif kind == "sqrl":
-                # SQRL's constraint-sampling acting pass: every seed's stand-alone descriptor, one launch (one k for all seeds)
-                args = (_lib.rrl_sqrl_act_t * S)(*[op[1] for op in ops])
-                stages.append((self.lib.rrl_sqrl_act_packed, (S, args), ops))
-            elif kind == "sqrl_f16x3":
-                # ... with f16x3 scores (RRL_SQRL_F16X3=1): the same descriptors on the f16x3 kernels' packed entry; every seed's
-                # hi / lo stream of W2 is re-made by the per-seed "call" stage in front of it
-                args = (_lib.rrl_sqrl_act_t * S)(*[op[1] for op in ops])
-                stages.append((self.lib.rrl_sqrl_act_f16x3_packed, (S, args), ops))
-            elif kind in ("qsample", "qsample_f16x3"):
-                # the Q-sampling recovery call with the gate inside it: every seed's descriptor and gate, one stage (k may
-                # differ by seed).  Without a gate (the mask form) the pass before it has launches the tape cannot pack.
-                # "qsample_f16x3" (RRL_QSAMPLE_F16X3=1): the same descriptors on the f16x3 kernels' packed entry, within the same
-                # limits; every seed's hi / lo stream of W2 is re-made by the per-seed "call" stage in front of it
-                if any(len(op) < 3 for op in ops):
+            elif kind in fast_update.ACT_PACKED:
+                # the acting launch of the SQRL line (one k for all seeds) or of the Q-sampling line (k may differ by seed): every
+                # seed's stand-alone argument blocks -- the descriptor; for Q-sampling the gate too -- as one stage.  The f16x3
+                # kinds: the same blocks on the f16x3 kernels' packed entry, within the same limits; every seed's hi / lo stream
+                # of W2 is re-made by the per-seed "call" stage in front of it.  Q-sampling without a gate (the mask form): the
+                # pass before it has launches the tape cannot pack.
+                if kind.startswith("qsample") and any(len(op) < 3 for op in ops):
                     raise _lib.RRLError("launch kind 'qsample' packs with the gate in the launch only (RRL_PACK_QSAMPLE=1)")
-                args = (_lib.rrl_qsample_act_t * S)(*[op[1] for op in ops])
-                gates = (_lib.rrl_qsample_gate_t * S)(*[op[2] for op in ops])
-                entry = self.lib.rrl_qsample_act_f16x3_packed if kind == "qsample_f16x3" else self.lib.rrl_qsample_act_packed
-                stages.append((entry, (S, args, gates), ops))
+                blocks = [(type(b) * S)(*[op[i] for op in ops]) for i, b in enumerate(ops[0][1:], 1)]
+                stages.append((getattr(self.lib, fast_update.ACT_PACKED[kind]), (S, *blocks), ops))
             elif kind == "step":
                 env_name, env_kind = ops[0][1], ops[0][2]
                 assert all(op[1] == env_name and op[2] == env_kind for op in ops), "one env per packed run"

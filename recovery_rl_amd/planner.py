@@ -3,11 +3,11 @@ launch: either precision, host or device count of problems) behind `MPC._compile
 (recovery_rl/MPC.py:374-416).  The PyTorch path in MPC.py stays as the general path (other widths) and as the
 cross-check (tests/test_plan_gpu.py)."""
 import ctypes as C
-import os
 
 import torch
 
 from . import _lib
+from .paths import switch
 
 
 class FusedPlanner:
@@ -18,7 +18,7 @@ class FusedPlanner:
         f32 MFMA; default from RRL_PLAN_F16X3 (off)."""
         self.mpc = mpc
         self.lib = _lib.load()
-        self.f16x3 = (os.environ.get("RRL_PLAN_F16X3", "") not in ("", "0")) if f16x3 is None else bool(f16x3)
+        self.f16x3 = switch("RRL_PLAN_F16X3") if f16x3 is None else bool(f16x3)
         self.device = mpc.device
         model = mpc.model
         self.hq = int(mpc.value_func.safety_critic.linear1.weight.shape[0])

@@ -1,13 +1,13 @@
 """Small helpers of the hot path (reference: recovery_rl/utils.py:46-64)."""
-import os
-
 import torch
+
+from .paths import switch
 
 # RRL_ROCTX=1: roctx ranges (torch.cuda.nvtx maps to roctx on ROCm) around the stages of the lock-step iteration, so a
 # `rocprofv3 --marker-trace --kernel-trace` run of the EAGER loop (bench.py --no_graph) attributes kernels to
 # sample / sac_update / qrisk_update / act / env_step / cem without name matching.  Off by default: a range is two host
 # calls per stage, and ranges inside a captured hipGraph mean nothing (the graph is one launch).
-TRACE = os.environ.get("RRL_ROCTX", "") not in ("", "0")
+TRACE = switch("RRL_ROCTX")
 
 
 class trace_range:
