@@ -17,8 +17,8 @@
 // ONE body (rollout_tile<Env, Form>) and two kernel templates over it: eval_rollout_kernel (the argument block in the kernel
 // arguments, the tile index from the grid) and eval_rollout_pack_kernel (S seeds side by side, pack.hpp: block and tile index
 // from a packed plan).  Their instantiations are the grid Env x Form, twenty kernels:
-//   Env   NavRoll restates nav_kernels.hip's NavEnv; MazeRoll is maze_device.hpp's transition (a trait with reset and step, as
-//         step_push.hpp's), so the Navigation kernels carry no Maze branch.
+//   Env   NavRoll / MazeRoll adapt env_models.hpp's NavEnv / MazeEnv (a trait with reset and step, as step_push.hpp's), so the
+//         Navigation kernels carry no Maze branch.
 //   Form  NoQs (rrl_eval_rollout, rrl_eval_rollout_maze); QsOn / QsOnH (rrl_eval_rollout_qs[_f16x3]); SqOn / SqOnH
 //         (rrl_eval_rollout_sqrl[_f16x3]); every entry has a _packed form.  The form names its descriptor, the group its
 //         argument block carries, its LDS bytes and its occupancy; the host path (launch_solo / launch_packed) is one for all.
@@ -60,6 +60,7 @@
 // (profiles/eval_one_body_fingerprint.txt).
 #include <type_traits>
 
+#include "env_models.hpp"
 #include "maze_device.hpp"
 #include "mfma_tile.hpp"
 #include "mfma_tile_f16x3.hpp"
@@ -71,6 +72,7 @@ using namespace rrl_host;
 
 namespace {
 
+using rrl_env::Outcome;
 using rrl_tile::f32x4;
 using rrl_tile::kActStride;
 using rrl_tile::kH;
@@ -325,61 +327,36 @@ __device__ __forceinline__ float fold_part(const float* part, int o, int row, fl
     return v;
 }
 
-// NavEnv::step of nav_kernels.hip: (next state, cost, constraint) of one transition
-__device__ __forceinline__ bool nav_step(int kind, double x, double y, float ax, float ay, double ex, double ey, double& nx,
-                                         double& ny, double& cost) {
-    if (kind == RRL_ENV_NAV1) {
-        rrl::nav_transition<0>(x, y, double(ax), double(ay), ex, ey, nx, ny, cost);
-        return rrl::in_obstacle<0>(nx, ny);
-    }
-    rrl::nav_transition<1>(x, y, double(ax), double(ay), ex, ey, nx, ny, cost);
-    return rrl::in_obstacle<1>(nx, ny);
-}
-
-// What one transition leaves: the next state, the reward and the three flags of the eager env's step()
-struct Outcome {
-    double nx, ny;
-    float rew;
-    bool cons, succ, done;
-};
-
-// Navigation 1 / 2: start at START + N(0, I); the cost is judged at the OLD state, done = success | constraint
+// The rollout's env traits over env_models.hpp: step(a, row, ctr, j, x, y, ax, ay) and reset(a, row, tick, x, y).
+// Navigation 1 / 2: the kind is an argument of the launch, so the step draws its noise once and picks the kind's transition
 struct NavRoll {
     __device__ __forceinline__ void reset(const EvArgs& a, long long row, uint64_t tick, double& x, double& y) const {
-        double z0, z1;                                       // NavEnv::reset: START_STATE + randn(2)
-        rrl::normal_at(a.seed, uint32_t(row), rrl::kStreamReset, tick, z0, z1);
-        x = -50.0 + z0;
-        y = 0.0 + z1;
+        const double2 p = rrl_env::NavEnv<0>::reset(a.seed, uint32_t(row), tick);     // one start state for both kinds
+        x = p.x;
+        y = p.y;
     }
     __device__ __forceinline__ Outcome step(const EvArgs& a, long long row, uint64_t ctr, int, double x, double y, float ax,
                                             float ay) const {
-        double ex, ey, nx, ny, cost;
-        rrl::normal_at(a.seed, uint32_t(row), rrl::kStreamStep, ctr, ex, ey);
-        const bool cons = nav_step(a.kind, x, y, ax, ay, ex, ey, nx, ny, cost);
-        const bool sc = cost > -4.0;
-        const bool dn = sc | cons;
-        return Outcome{nx, ny, float(cost), cons, sc, dn};
+        const double2 e = rrl_env::nav_step_noise(a.seed, uint32_t(row), ctr), p = make_double2(x, y);
+        double nx, ny, cost;
+        const bool cons = a.kind == RRL_ENV_NAV1 ? rrl_env::NavEnv<0>::move(p, double(ax), double(ay), e.x, e.y, nx, ny, cost)
+                                                 : rrl_env::NavEnv<1>::move(p, double(ax), double(ay), e.x, e.y, nx, ny, cost);
+        return rrl_env::nav_outcome(nx, ny, cost, cons);
     }
 };
 
-// Maze (MazeVecEnv(auto_reset=False), maze_kernels.hip's maze_step_kernel / MazeEnv): reset of mode 0 with the rejection
-// loop; the step draws nothing, the reward is judged at the NEW state, and the env's own horizon ends a row with neither flag
+// Maze (MazeVecEnv(auto_reset=False)): the env's own horizon is the block's
 struct MazeRoll {
     int horizon;
     __device__ __forceinline__ void reset(const EvArgs& a, long long row, uint64_t tick, double& x, double& y) const {
-        rrl_maze::reset_one(a.seed, uint32_t(row), tick, 0, true, x, y);
+        const double2 p = rrl_env::MazeEnv::reset(a.seed, uint32_t(row), tick);
+        x = p.x;
+        y = p.y;
     }
     __device__ __forceinline__ Outcome step(const EvArgs&, long long, uint64_t, int j, double x, double y, float ax,
                                             float ay) const {
-        Outcome o;
-        o.nx = x;
-        o.ny = y;
-        rrl_maze::move(o.nx, o.ny, double(ax), double(ay));  // clamps to +-0.1 itself
-        const double d = rrl_maze::goal_distance(o.nx, o.ny);
-        o.rew = float(-d);
-        o.cons = rrl_maze::in_contact(o.nx, o.ny);
-        o.succ = -d > -0.03;
-        o.done = (j + 1 >= horizon) | o.cons | (d < rrl_maze::kGoalThresh);
+        Outcome o = rrl_env::MazeEnv::step(make_double2(x, y), double(ax), double(ay));
+        o.done = rrl_env::MazeEnv::timed_out(j + 1, horizon) | o.done;
         return o;
     }
 };
@@ -785,8 +762,8 @@ __device__ __forceinline__ void rollout_tile(const EvArgs& a, const Env& env, un
         if (alive) {
             const long long o = (long long)j * a.n + row;
             const Outcome t = env.step(a, row, ctr, j, x, y, r0, r1);
-            const bool cons = t.cons, sc = t.succ, dn = t.done;
-            const float rew = t.rew;
+            const bool cons = t.constraint, sc = t.success, dn = t.done;
+            const float rew = t.reward;
             if (a.tr_pos) {
                 a.tr_pos[2 * o] = x;
                 a.tr_pos[2 * o + 1] = y;
@@ -831,8 +808,8 @@ __device__ __forceinline__ void rollout_tile(const EvArgs& a, const Env& env, un
             succ |= sc;
             viol |= cons;
             ++steps;
-            x = t.nx;
-            y = t.ny;
+            x = t.x;
+            y = t.y;
             alive = !dn;
         }
     }

@@ -7,6 +7,7 @@
 // layout and launch shape as the navigation kernels: one lane per env, SoA, HBM-bound.
 #include <hip/hip_runtime.h>
 
+#include "env_models.hpp"
 #include "maze_device.hpp"
 #include "replay_device.hpp"
 #include "rrl_device.hpp"
@@ -22,56 +23,7 @@ using rrl_host::grid_for;
 using rrl_host::kBlock;
 
 using namespace rrl_maze;
-
-struct MazeArgs {
-    int64_t n;
-    double2* pos;
-    const float2* action;
-    uint64_t seed, counter;
-    uint64_t* counter_dev;
-    uint64_t counter_inc;
-    float2* next_obs;
-    float2* obs;
-    float* reward;
-    uint8_t* done;
-    uint8_t* constraint;
-    uint8_t* success;
-    uint8_t* ep_done;
-    int32_t* t;
-    int32_t horizon, auto_reset;
-};
-
-__global__ __launch_bounds__(kBlock) void maze_step_kernel(MazeArgs a) {
-    const uint64_t ctr = rrl::effective_counter(a.counter, a.counter_dev);
-    const int64_t stride = int64_t(gridDim.x) * kBlock;
-    for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < a.n; i += stride) {
-        const double2 p = a.pos[i];
-        const float2 act = a.action[i];
-        double x = p.x, y = p.y;
-        move(x, y, double(act.x), double(act.y));
-        int32_t ti = a.t[i] + 1;
-        const bool cons = in_contact(x, y);
-        const double d = goal_distance(x, y);
-        const bool dn = (ti >= a.horizon) | cons | (d < kGoalThresh);
-        const double rew = -d;
-        const bool succ = rew > -0.03;
-        const bool epd = dn | (ti == a.horizon);
-        a.next_obs[i] = make_float2(float(x), float(y));
-        a.reward[i] = float(rew);
-        a.done[i] = uint8_t(dn);
-        a.constraint[i] = uint8_t(cons);
-        a.success[i] = uint8_t(succ);
-        if (a.ep_done) a.ep_done[i] = uint8_t(epd);
-        if (a.auto_reset && epd) {
-            reset_one(a.seed, uint32_t(i), ctr, 0, true, x, y);
-            ti = 0;
-        }
-        a.pos[i] = make_double2(x, y);
-        a.t[i] = ti;
-        if (a.obs) a.obs[i] = make_float2(float(x), float(y));
-    }
-    rrl::advance_counter(a.counter_dev, a.counter_inc);
-}
+using rrl_env::MazeEnv;
 
 __global__ __launch_bounds__(kBlock) void maze_reset_kernel(int64_t n, double2* pos, float2* obs,
                                                             int32_t* t, const uint8_t* mask, int mode,
@@ -116,41 +68,18 @@ __global__ __launch_bounds__(kBlock) void maze_offline_kernel(int64_t half, int6
             expert_action(x, y, ax, ay);                             // float64 into step() (:88-89)
         }
         const float axf = float(ax), ayf = float(ay);
-        double nx = x, ny = y;
-        move(nx, ny, ax, ay);
+        const rrl_env::Outcome o = MazeEnv::step(make_double2(x, y), ax, ay);
         steps += 1;
-        const bool cons = in_contact(nx, ny);
-        const bool dn = (steps >= 100) | cons | (goal_distance(nx, ny) < kGoalThresh);
+        const bool dn = MazeEnv::timed_out(steps, 100) | o.done;
         s[w] = make_float2(float(x), float(y));
         a[w] = make_float2(axf, ayf);
-        c[w] = cons ? 1.0f : 0.0f;
-        s2[w] = make_float2(float(nx), float(ny));
+        c[w] = o.constraint ? 1.0f : 0.0f;
+        s2[w] = make_float2(float(o.x), float(o.y));
         m[w] = dn ? 0.0f : 1.0f;
-        x = nx;
-        y = ny;
+        x = o.x;
+        y = o.y;
     }
 }
-
-// the maze transition plugged into the fused step + push kernel (step_push.hpp)
-struct MazeEnv {
-    static __device__ __forceinline__ rrl_step::Outcome step(const StepArgs& a, int64_t, uint64_t, double2 p,
-                                                             float2 act, int32_t t_after) {
-        double x = p.x, y = p.y;
-        move(x, y, double(act.x), double(act.y));
-        const double d = goal_distance(x, y);
-        rrl_step::Outcome o;
-        o.x = x;
-        o.y = y;
-        o.reward = float(-d);
-        o.constraint = in_contact(x, y);
-        o.success = -d > -0.03;
-        o.done = (t_after >= a.horizon) | o.constraint | (d < kGoalThresh);      // env/maze.py:207-213
-        return o;
-    }
-    static __device__ __forceinline__ void reset(const StepArgs& a, int64_t i, uint64_t ctr, double& x, double& y) {
-        reset_one(a.seed, uint32_t(i), ctr, 0, true, x, y);
-    }
-};
 
 }  // namespace
 
@@ -164,10 +93,10 @@ int rrl_maze_step(int64_t n, double* pos, const float* action, uint64_t seed, ui
     if (!pos || !action || !next_obs || !reward || !done || !constraint || !success || !t)
         return RRL_EINVAL;
     if (n == 0) return RRL_OK;
-    MazeArgs a{n, (double2*)pos, (const float2*)action, seed, counter, counter_dev, counter_inc,
+    StepArgs a{n, (double2*)pos, (const float2*)action, nullptr, seed, counter, counter_dev, counter_inc,
                (float2*)next_obs, (float2*)obs, reward, done, constraint, success, ep_done, t, horizon,
                auto_reset};
-    hipLaunchKernelGGL(maze_step_kernel, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((env_step_kernel<MazeEnv, false>), dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, a);
     return check_launch();
 }
 

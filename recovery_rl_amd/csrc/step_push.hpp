@@ -1,8 +1,7 @@
 // step_push.hpp -- the lock-step iteration tail as ONE kernel, shared by the navigation and maze envs:
 // env.step + reward penalty + bootstrap mask + memory.push + recovery_memory.push + episode counters
 // (recovery_rl/experiment.py:420-461).  ENV supplies the transition and the reset draw:
-//   static Outcome ENV::step(const StepArgs&, int64_t i, uint64_t ctr, double2 pos, float2 action, int32_t t_after)
-//   static void    ENV::reset(const StepArgs&, int64_t i, uint64_t ctr, double& x, double& y)
+// (env_models.hpp): ENV::step(seed, row, ctr, pos, action), ENV::timed_out(t_after, horizon), ENV::reset(seed, row, ctr)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,6 +9,7 @@
 
 #include <type_traits>
 
+#include "env_models.hpp"
 #include "pack.hpp"
 #include "replay_device.hpp"
 #include "rrl_device.hpp"
@@ -40,14 +40,55 @@ struct StepArgs {
     uint16_t* status;
 };
 
+// The stand-alone step in the arrays layout, one env per thread (rrl_maze_step; rrl_nav_step below 2^19 envs, where the
+// launch is latency-bound: a short dependent chain per thread matters more than wide accesses).  EXT_NOISE: the step noise
+// is a.noise instead of the row's draw (navigation only).
+template <class ENV, bool EXT_NOISE>
+__global__ __launch_bounds__(rrl_host::kBlock) void env_step_kernel(StepArgs a) {
+    constexpr int kBlock = rrl_host::kBlock;
+    const uint64_t ctr = rrl::effective_counter(a.counter, a.counter_dev);
+    const int64_t stride = int64_t(gridDim.x) * kBlock;
+    for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < a.n; i += stride) {
+        const double2 p = a.pos[i];
+        const float2 act = a.action[i];
+        // the step count is asked for with the other inputs, or behind a long step (the maze's 64 sub-steps run at ~110 VGPRs:
+        // the count would be held across them)
+        int32_t ti = 0;
+        if constexpr (!ENV::kLongStep) ti = a.t[i] + 1;
+        rrl_env::Outcome o;
+        if constexpr (EXT_NOISE) {
+            const double2 e = a.noise[i];
+            o = ENV::step(p, double(act.x), double(act.y), e.x, e.y);
+        } else {
+            o = ENV::step(a.seed, uint32_t(i), ctr, p, act);
+        }
+        if constexpr (ENV::kLongStep) ti = a.t[i] + 1;
+        const bool dn = ENV::timed_out(ti, a.horizon) | o.done;
+        const bool epd = dn | (ti == a.horizon);
+        a.next_obs[i] = make_float2(float(o.x), float(o.y));
+        a.reward[i] = o.reward;
+        a.done[i] = uint8_t(dn);
+        a.constraint[i] = uint8_t(o.constraint);
+        a.success[i] = uint8_t(o.success);
+        if (a.ep_done) a.ep_done[i] = uint8_t(epd);
+        double x = o.x, y = o.y;
+        if (a.auto_reset && epd) {
+            const double2 r = ENV::reset(a.seed, uint32_t(i), ctr);
+            x = r.x;
+            y = r.y;
+            ti = 0;
+        }
+        a.pos[i] = make_double2(x, y);
+        a.t[i] = ti;
+        if (a.obs) a.obs[i] = make_float2(float(x), float(y));
+    }
+    rrl::advance_counter(a.counter_dev, a.counter_inc);
+}
+
 
 namespace rrl_step {
 
-struct Outcome {
-    double x, y;        // next position (before an auto-reset)
-    float reward;
-    bool constraint, success, done;   // done = the env's own termination (the horizon is added by the kernel)
-};
+using rrl_env::Outcome;
 
 // Counterpart of the body of recovery_rl/experiment.py:420-461 for n envs: env.step, reward penalty,
 // mask = not done (before the horizon check), memory.push, recovery_memory.push, episode counters.
@@ -349,13 +390,17 @@ __device__ __forceinline__ void step_push_body(const StepPushArgs& p, const unsi
             ti += 1;
             double rx = 0.0, ry = 0.0;
             if constexpr (SPECULATE) {
-                if (a.auto_reset) ENV::reset(a, i, ctr, rx, ry);
+                if (a.auto_reset) {
+                    const double2 r = ENV::reset(a.seed, uint32_t(i), ctr);
+                    rx = r.x;
+                    ry = r.y;
+                }
             }
-            const Outcome out = ENV::step(a, i, ctr, pp, act, ti);
+            const Outcome out = ENV::step(a.seed, uint32_t(i), ctr, pp, act);
             double nx = out.x, ny = out.y;
             cons = out.constraint;
             succ = out.success;
-            const bool dn = out.done;
+            const bool dn = ENV::timed_out(ti, a.horizon) | out.done;
             epd = dn | (ti == a.horizon);
             if constexpr (SPECULATE) {
                 // the episode table's slots for this wave's finished episodes: ONE returning atomic per wave, requested as
@@ -398,7 +443,9 @@ __device__ __forceinline__ void step_push_body(const StepPushArgs& p, const unsi
                     nx = rx;
                     ny = ry;
                 } else {
-                    ENV::reset(a, i, ctr, nx, ny);
+                    const double2 r = ENV::reset(a.seed, uint32_t(i), ctr);
+                    nx = r.x;
+                    ny = r.y;
                 }
                 ti = 0;
             }

@@ -87,10 +87,11 @@ BUDGETS = (
     ("plan_first_step_kernel", 128, "planner, first step once per distinct row: the rollout kernel's phases, same occupancy"),
     ("mlp3_fwd_split_flat_group_kernel", 128, "acting forward riding with 256-row update forwards (both tile forms in one kernel)"),
     ("ens_big_fwd_bwd_kernel", 128, "large-batch ensemble step"),
-    ("step_push_kernelIN12_GLOBAL__N_16NavEnvILi0EEELi0E", 96, "fused env step + pushes + episode table, latency variant (speculated reset)"),
-    ("step_push_kernelIN12_GLOBAL__N_16NavEnvILi0EEELi2E", 64, "the same, bandwidth variant: 1024-thread workgroups, eight waves per SIMD"),
+    ("step_push_kernelIN7rrl_env6NavEnvILi0EEELi0E", 96, "fused env step + pushes + episode table, latency variant (speculated reset)"),
+    ("step_push_kernelIN7rrl_env6NavEnvILi0EEELi2E", 64, "the same, bandwidth variant: 1024-thread workgroups, eight waves per SIMD"),
     ("backward_pair_kernel", 256, "paired head + hidden backward: two 4-wave workgroups (8 tiles) per CU"),
-    ("nav_step_kernel", 64, "env step: eight waves per SIMD (bandwidth regime)"),
+    ("env_step_kernelIN7rrl_env6NavEnv", 64, "env step, one env per thread: eight waves per SIMD (bandwidth regime)"),
+    ("env_step_kernelIN7rrl_env7MazeEnv", 113, "the same kernel on the maze (64 collision sub-steps): what maze_step_kernel had, four waves"),
     ("sample_group_kernel", 64, "replay draws"),
 )
 
@@ -117,7 +118,7 @@ def test_step_push_has_no_loop_and_few_sgpr_spills(tmp_path):
     if not os.path.exists(_lib.SO_PATH):
         _lib.build()
     table = kernel_table(_lib.SO_PATH, str(tmp_path))
-    hits = {k: v for k, v in table.items() if "step_push_kernelIN12_GLOBAL__N_16NavEnv" in k}
+    hits = {k: v for k, v in table.items() if "step_push_kernelIN7rrl_env6NavEnv" in k}
     assert len(hits) == 6, sorted(hits)          # two env kinds x three launch shapes
     for k, v in hits.items():
         lanes = v["ins"].get("v_readlane_b32", 0) + v["ins"].get("v_writelane_b32", 0)
@@ -154,7 +155,7 @@ def test_early_tickets_are_not_waited_for_on_the_spot(kernels):
     from recovery_rl_amd import _lib
     if not _lib.flags_supported(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), _lib.SOURCE_FLAGS["update_kernels.hip"]):
         pytest.skip("this hipcc does not know -amdgpu-atomic-optimizer-strategy")
-    for piece in ("step_push_kernelIN12_GLOBAL__N_16NavEnvILi0EEELi0E", "adam_multi_kernel"):
+    for piece in ("step_push_kernelIN7rrl_env6NavEnvILi0EEELi0E", "adam_multi_kernel"):
         hits = [k for k in kernels if piece in k]
         assert hits, piece
         for k in hits:

@@ -141,8 +141,10 @@ def test_compact_step_matches_oracle_with_philox_noise(env, n):
 
 @pytest.mark.parametrize("env", ENVS)
 def test_compact_step_every_episode_ending_at_once(env):
-    """All envs reach the horizon on the same step (what a synchronously started sweep does): more finished episodes
-    per wave than its reset list holds -> the per-lane path; and a mixed case around the 64-entry limit."""
+    """All envs reach the horizon on the same step (what a synchronously started sweep does), then every fourth and every
+    fifth.  At n = 8192 both entries run their one-env-per-thread kernels, whose resets are drawn inline per lane: this
+    covers a reset in every lane and in regular subsets of the lanes.  The per-wave reset list and its 64-entry limit are
+    covered by test_every_episode_ending_at_once_on_the_wide_kernels."""
     n = 8192
     rng = np.random.RandomState(3)
     pos = np.c_[rng.uniform(-60, -40, n), rng.uniform(-3, 3, n)]
@@ -150,6 +152,23 @@ def test_compact_step_every_episode_ending_at_once(env):
     for t in (np.full(n, 99, np.int32), np.where(np.arange(n) % 4 == 0, 99, 5).astype(np.int32),
               np.where(np.arange(n) % 5 == 0, 99, 5).astype(np.int32)):
         ref = co.nav_step(env, pos, act, t, seed=11, counter=3, auto_reset=True)
+        assert_same(hip_step_compact(env, pos, act, t, seed=11, counter=3, auto_reset=True), ref)
+        assert_same(hip_step(env, pos, act, t, seed=11, counter=3, auto_reset=True), ref)
+
+
+@pytest.mark.parametrize("env", ENVS)
+@pytest.mark.parametrize("n", (1 << 19, (1 << 22) + 2))
+def test_every_episode_ending_at_once_on_the_wide_kernels(env, n):
+    """The same three step-count patterns at the sizes where both entries draw resets once per wave (four envs per thread at
+    2^19, two envs per thread and two parked passes at 2^22 + 2; either way a wave lists the finished rows of 256 envs): all
+    256 finished -> more than the list's 64 entries, the per-lane path; every fourth -> exactly 64; every fifth -> below."""
+    rng = np.random.RandomState(3)
+    pos = np.c_[rng.uniform(-60, -40, n), rng.uniform(-3, 3, n)]
+    act = rng.uniform(-1, 1, (n, 2)).astype(np.float32)
+    for t in (np.full(n, 99, np.int32), np.where(np.arange(n) % 4 == 0, 99, 5).astype(np.int32),
+              np.where(np.arange(n) % 5 == 0, 99, 5).astype(np.int32)):
+        ref = co.nav_step(env, pos, act, t, seed=11, counter=3, auto_reset=True)
+        assert np.array_equal(ref["ep_done"] != 0, t == 99)       # nothing else ends: the counts per wave are the patterns'
         assert_same(hip_step_compact(env, pos, act, t, seed=11, counter=3, auto_reset=True), ref)
         assert_same(hip_step(env, pos, act, t, seed=11, counter=3, auto_reset=True), ref)
 
@@ -181,9 +200,10 @@ def test_compact_step_rejects_what_the_status_word_cannot_hold():
 
 
 @pytest.mark.parametrize("env", ENVS)
-def test_vector_path_with_explicit_noise_and_device_tick(env):
-    """The 4-envs-per-thread kernel (n >= 2^19) with caller-supplied noise, and its device-side tick."""
-    n = 1 << 19
+@pytest.mark.parametrize("n", (1 << 19, (1 << 22) + 2))
+def test_vector_path_with_explicit_noise_and_device_tick(env, n):
+    """The 4-envs-per-thread kernel (n >= 2^19) and the two-envs-per-thread kernel with parked passes (n >= 2^22) with
+    caller-supplied noise, and their device-side tick."""
     rng = np.random.RandomState(5)
     pos = np.c_[rng.uniform(-60, 10, n), rng.uniform(-12, 12, n)]
     act = rng.uniform(-1.5, 1.5, (n, 2)).astype(np.float32)
@@ -196,6 +216,20 @@ def test_vector_path_with_explicit_noise_and_device_tick(env):
     got = hip_step(env, pos, act, t, seed=3, counter=5, auto_reset=True, tick=tick, inc=2)
     assert_same(got, co.nav_step(env, pos, act, t, seed=3, counter=9, auto_reset=True))
     assert tick.tolist() == [6, 0]
+
+
+@pytest.mark.parametrize("env", ENVS)
+@pytest.mark.parametrize("n", (600001, (1 << 22) + 3))
+def test_compact_vector_path_with_explicit_noise(env, n):
+    """The compact entry's four-envs-per-thread kernel (ragged last group) and its two-envs-per-thread kernel with parked
+    passes, with caller-supplied noise."""
+    rng = np.random.RandomState(6)
+    pos = np.c_[rng.uniform(-60, 10, n), rng.uniform(-12, 12, n)]
+    act = rng.uniform(-1.5, 1.5, (n, 2)).astype(np.float32)
+    t = rng.randint(0, 100, n).astype(np.int32)
+    noise = rng.randn(n, 2)
+    ref = co.nav_step(env, pos, act, t, noise=noise, seed=3, counter=9, auto_reset=True)
+    assert_same(hip_step_compact(env, pos, act, t, noise=noise, seed=3, counter=9, auto_reset=True), ref)
 
 
 @pytest.mark.parametrize("env", ENVS)
