@@ -22,6 +22,14 @@ tr.epoch(idxs, 32)
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 print("fused ensemble step: %.1f us per optimiser step (200 steps)" % (dt / 200 * 1e6))
+b32 = idxs[:, :32]
+tr.gradients(b32)
+torch.cuda.synchronize()
+t0 = time.perf_counter()
+for _ in range(200):
+    tr.gradients(b32)
+torch.cuda.synchronize()
+print("lone gradient launch: %.1f us per rrl_ens_train_grad at batch 32 (200 calls)" % ((time.perf_counter() - t0) / 200 * 1e6))
 if os.environ.get("RRL_HIP_LIB", "").endswith("_ab_enstiming.so"):       # built with -DRRL_ENS_TIMING
     tr.gradients(idxs[:, :32])
     torch.cuda.synchronize()

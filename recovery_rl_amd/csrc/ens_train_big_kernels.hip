@@ -22,32 +22,28 @@
 // the batch-32 kernel.
 #include <hip/hip_runtime.h>
 
+#include "ens_model.hpp"
 #include "mfma_tile.hpp"
-#include "rrl_host.hpp"
 
 namespace {
 
+using namespace rrl_ens;      // the model, the loss and the host checks: shared with ens_train_kernels.hip
 using rrl_host::check_launch;
 using rrl_tile::f32x4;
 using rrl_tile::mfma;
 using rrl_tile::opaque;
 
-constexpr int kH = 200, kDin = 4, kDout = 4;
-constexpr int kR = 64;               // rows per tile
+constexpr int kR = 64;              // rows per tile
 constexpr int kS = 204;              // LDS row stride (floats): row r starts at bank 12 r mod 32 -> conflict-free b128 reads
 constexpr int kThreadsA = 512;       // 8 waves
 constexpr int kBuf = kR * kS;
 constexpr int kLdsFloatsA = 3 * kBuf + kR * (kDin + 2 + kDout + kDout) + 16;
 constexpr int kLdsBytesA = kLdsFloatsA * 4;          // 160 320 B (of 163 840)
 constexpr int kPartA = 2304;         // floats per workgroup partial: gW0 800 | gW3 800 | gb0 200 | gb1 200 | gb2 200 | gb3 4 | lv 4 | loss 1
-constexpr int kOffW0 = 0, kOffW3 = 800, kOffB0 = 1600, kOffB1 = 1800, kOffB2 = 2000, kOffB3 = 2200, kOffLv = 2204,
-              kOffLoss = 2208;
+constexpr int kOffW0 = 0, kOffW3 = 800, kOffB0 = 1600, kOffB1 = 1800, kOffB2 = 2000, kOffB3 = 2200,
+              kOffLv = kOffB3 + kDout, kOffLoss = 2208;      // up to kOffLv: what the reduce kernel sums per member
 constexpr int kThreadsB = 1024;      // 16 waves
 constexpr int kMaxP = 64, kMaxQ = 32;
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ float softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }   // F.softplus
-__device__ __forceinline__ float softplus_grad(float x) { return x > 20.f ? 1.f : sigm(x); }
 
 // A wave's share of a [64 x 200] = [64 x 200] . [200 x 200] product: row tiles {2 rh, 2 rh + 1} x column tiles {cs, cs + 4,
 // cs + 8} (rh = wave & 1, cs = wave >> 1), plus tile (row tile `wave`, column tile 12) on waves 0..3 -- 7 or 6 of the 52
@@ -178,14 +174,7 @@ __global__ __launch_bounds__(kThreadsA) void ens_big_fwd_bwd_kernel(BigArgs g) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int e = blockIdx.x / g.P, p = blockIdx.x % g.P;
-    const float* W0 = m.w0 + (size_t)e * kDin * kH;
-    const float* b0 = m.b0 + (size_t)e * kH;
-    const float* W1 = m.w1 + (size_t)e * kH * kH;
-    const float* b1 = m.b1 + (size_t)e * kH;
-    const float* W2 = m.w2 + (size_t)e * kH * kH;
-    const float* b2 = m.b2 + (size_t)e * kH;
-    const float* W3 = m.w3 + (size_t)e * kH * kDout;
-    const float* b3 = m.b3 + (size_t)e * kDout;
+    const Member me = member_of(m, e);
     const size_t mem_off = (size_t)e * g.rows_pad * kH;
     float* const h0g = g.h0 + mem_off;
     float* const h1g = g.h1 + mem_off;
@@ -209,10 +198,7 @@ __global__ __launch_bounds__(kThreadsA) void ens_big_fwd_bwd_kernel(BigArgs g) {
         if (tid < kR * kDin) {
             const int rl = tid / kDin, k = tid % kDin;
             const long long r = row0 + rl;
-            const bool live = r < g.nb;
-            const int64_t row = live ? g.idx[(size_t)e * g.idx_stride + r] : 0;
-            xin[tid] = live ? (g.train_in[row * kDin + k] - m.mu[k]) / m.sigma[k] : 0.f;
-            if (k < 2) yt[rl * 2 + k] = live ? g.train_targ[row * 2 + k] : 0.f;
+            gather(m, g.train_in, g.train_targ, g.idx + (size_t)e * g.idx_stride + r, r < g.nb, k, xin + tid, yt + rl * 2 + k);
         }
         __syncthreads();
         // ---- layer 0 (K = 4: one MFMA step per tile) -> h0 in A ----
@@ -225,18 +211,19 @@ __global__ __launch_bounds__(kThreadsA) void ens_big_fwd_bwd_kernel(BigArgs g) {
             for (int a = 0; a < 2; ++a) {
                 const float av = xin[(16 * (2 * rh + a) + lr) * kDin + lq];
 #pragma unroll
-                for (int c = 0; c < 3; ++c) acc.main[a][c] = mfma(av, W0[lq * kH + 16 * (cs + 4 * c) + lr], z);
+                for (int c = 0; c < 3; ++c) acc.main[a][c] = mfma(av, me.w0[lq * kH + 16 * (cs + 4 * c) + lr], z);
             }
             acc.extra = z;
             if (wave < 4) {
                 const int nx = 192 + lr;
-                acc.extra = mfma(xin[(16 * wave + lr) * kDin + lq], nx < kH ? W0[lq * kH + nx] : 0.f, z);
+                acc.extra = mfma(xin[(16 * wave + lr) * kDin + lq], nx < kH ? me.w0[lq * kH + nx] : 0.f, z);
             }
             for_each_elem(acc, wave, lane, [&](int r, int n, float v) {
-                const float pre = v + b0[n], sg = sigm(pre), h = pre * sg;
+                float h, dh;
+                swish(v + me.b0[n], h, dh);
                 bufA[r * kS + n] = h;
                 h0g[(size_t)(row0 + r) * kH + n] = h;
-                sp0g[(size_t)(row0 + r) * kH + n] = sg * (1.f + pre * (1.f - sg));      // d swish / d pre
+                sp0g[(size_t)(row0 + r) * kH + n] = dh;
             });
         }
         __syncthreads();
@@ -244,12 +231,13 @@ __global__ __launch_bounds__(kThreadsA) void ens_big_fwd_bwd_kernel(BigArgs g) {
         // ---- layer 1: h0 (A) -> h1 (B) ----
         {
             Acc acc;
-            wave_gemm<false>(bufA, W1, wave, lane, acc);
+            wave_gemm<false>(bufA, me.w1, wave, lane, acc);
             for_each_elem(acc, wave, lane, [&](int r, int n, float v) {
-                const float pre = v + b1[n], sg = sigm(pre), h = pre * sg;
+                float h, dh;
+                swish(v + me.b1[n], h, dh);
                 bufB[r * kS + n] = h;
                 h1g[(size_t)(row0 + r) * kH + n] = h;
-                sp1g[(size_t)(row0 + r) * kH + n] = sg * (1.f + pre * (1.f - sg));
+                sp1g[(size_t)(row0 + r) * kH + n] = dh;
             });
         }
         __syncthreads();
@@ -257,11 +245,9 @@ __global__ __launch_bounds__(kThreadsA) void ens_big_fwd_bwd_kernel(BigArgs g) {
         // ---- layer 2: h1 (B) -> h2 (A), swish' (C) ----
         {
             Acc acc;
-            wave_gemm<false>(bufB, W2, wave, lane, acc);
+            wave_gemm<false>(bufB, me.w2, wave, lane, acc);
             for_each_elem(acc, wave, lane, [&](int r, int n, float v) {
-                const float pre = v + b2[n], sg = sigm(pre);
-                bufA[r * kS + n] = pre * sg;
-                bufC[r * kS + n] = sg * (1.f + pre * (1.f - sg));
+                swish(v + me.b2[n], bufA[r * kS + n], bufC[r * kS + n]);
             });
         }
         __syncthreads();
@@ -272,31 +258,23 @@ __global__ __launch_bounds__(kThreadsA) void ens_big_fwd_bwd_kernel(BigArgs g) {
             const int r = o_idx >> 2, o = o_idx & 3;
             float acc = 0.f;
             const float* hr = bufA + r * kS + half * (kH / 2);
-            const float* wr = W3 + (size_t)half * (kH / 2) * kDout + o;
+            const float* wr = me.w3 + (size_t)half * (kH / 2) * kDout + o;
 #pragma unroll 10
             for (int k = 0; k < kH / 2; ++k) acc = fmaf(hr[k], wr[k * kDout], acc);
             const float other = __shfl_xor(acc, 1, 64);
-            if (half == 0) outb[o_idx] = (acc + other) + b3[o];
+            if (half == 0) outb[o_idx] = (acc + other) + me.b3[o];
         }
         __syncthreads();
         tid = opaque(tid_k); lane = opaque(lane_k);
         // ---- loss (MPC.py:276-287) and its gradient w.r.t. the outputs; one thread per (row, dim) ----
         if (tid < 2 * kR) {
             const int r = tid >> 1, k = tid & 1;
-            const float mx = m.max_logvar[k], mn = m.min_logvar[k];
-            const float mean = outb[r * kDout + k], lv0 = outb[r * kDout + 2 + k];
-            const float a1 = mx - lv0, lv1 = mx - softplus(a1);
-            const float a2 = lv1 - mn, lv2 = mn + softplus(a2);
-            const float inv = expf(-lv2), diff = mean - yt[r * 2 + k];
             const float live = row0 + r < g.nb ? 1.f : 0.f;
-            float tl = (diff * diff * inv + lv2) * live;
-            const float scale = live / float(g.nb * 2);              // mean over the real rows and the two dims
-            const float d_lv2 = (1.f - diff * diff * inv) * scale;
-            const float s2 = softplus_grad(a2), d_lv1 = d_lv2 * s2;
-            const float s1 = softplus_grad(a1);
-            doutb[r * kDout + k] = 2.f * diff * inv * scale;
-            doutb[r * kDout + 2 + k] = d_lv1 * s1;
-            float d_min = d_lv2 * (1.f - s2), d_max = d_lv1 * (1.f - s1);
+            const NllTerm t = nll(m.max_logvar[k], m.min_logvar[k], outb[r * kDout + k], outb[r * kDout + 2 + k],
+                                  yt[r * 2 + k], live, g.nb * 2);
+            doutb[r * kDout + k] = t.d_mean;
+            doutb[r * kDout + 2 + k] = t.d_lv;
+            float tl = t.tl, d_min = t.d_min, d_max = t.d_max;
             // fixed-order reductions over the 64 rows: lanes of equal parity inside each wave, then the two waves
 #pragma unroll
             for (int off = 2; off < 64; off <<= 1) {
@@ -340,7 +318,7 @@ __global__ __launch_bounds__(kThreadsA) void ens_big_fwd_bwd_kernel(BigArgs g) {
             for (int i = tid; i < kR * kH; i += kThreadsA) {
                 const int r = i / kH, k = i % kH;
                 const float4 d = *reinterpret_cast<const float4*>(doutb + r * kDout);
-                const float4 w = *reinterpret_cast<const float4*>(W3 + (size_t)k * kDout);
+                const float4 w = *reinterpret_cast<const float4*>(me.w3 + (size_t)k * kDout);
                 const float v = (d.x * w.x + d.y * w.y + d.z * w.z + d.w * w.w) * bufC[r * kS + k];
                 bufC[r * kS + k] = v;
                 d2g[(size_t)(row0 + r) * kH + k] = v;
@@ -357,7 +335,7 @@ __global__ __launch_bounds__(kThreadsA) void ens_big_fwd_bwd_kernel(BigArgs g) {
         // ---- hidden layer 2: dpre1 = (dpre2 W2^T) * swish'(pre1) -> A ----
         {
             Acc acc;
-            wave_gemm<true>(bufC, W2, wave, lane, acc);
+            wave_gemm<true>(bufC, me.w2, wave, lane, acc);
             for_each_elem(acc, wave, lane, [&](int r, int n, float v) {
                 const float d = v * sp1g[(size_t)(row0 + r) * kH + n];
                 bufA[r * kS + n] = d;
@@ -375,7 +353,7 @@ __global__ __launch_bounds__(kThreadsA) void ens_big_fwd_bwd_kernel(BigArgs g) {
         // ---- hidden layer 1: dpre0 = (dpre1 W1^T) * swish'(pre0) -> B ----
         {
             Acc acc;
-            wave_gemm<true>(bufA, W1, wave, lane, acc);
+            wave_gemm<true>(bufA, me.w1, wave, lane, acc);
             for_each_elem(acc, wave, lane, [&](int r, int n, float v) {
                 bufB[r * kS + n] = v * sp0g[(size_t)(row0 + r) * kH + n];
             });
@@ -534,7 +512,7 @@ __global__ __launch_bounds__(256) void ens_big_reduce_kernel(BigArgs g, float* _
     const rrl_ens_t& m = g.m;
     const int E = m.n_nets;
     const long long n_big = 2LL * E * kH * kH;
-    const long long n_small = (long long)E * 2204;          // gW0 | gW3 | gb0 | gb1 | gb2 | gb3 per member
+    const long long n_small = (long long)E * kOffLv;        // gW0 | gW3 | gb0 | gb1 | gb2 | gb3 per member
     const long long total = n_big + n_small + 4 + E;
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         if (i < n_big) {
@@ -548,12 +526,12 @@ __global__ __launch_bounds__(256) void ens_big_reduce_kernel(BigArgs g, float* _
             (layer ? m.g_w2 : m.g_w1)[(size_t)e * kH * kH + el] = s;
         } else if (i < n_big + n_small) {
             const long long j = i - n_big;
-            const int e = int(j / 2204), off = int(j % 2204);
+            const int e = int(j / kOffLv), off = int(j % kOffLv);
             const float* src = g.partA + (size_t)e * g.P * kPartA + off;
             float s = 0.f;
             for (int p = 0; p < g.P; ++p) s += src[(size_t)p * kPartA];
-            if (off < kOffW3) m.g_w0[(size_t)e * 800 + off] = s;
-            else if (off < kOffB0) m.g_w3[(size_t)e * 800 + (off - kOffW3)] = s;
+            if (off < kOffW3) m.g_w0[(size_t)e * (kDin * kH) + off] = s;
+            else if (off < kOffB0) m.g_w3[(size_t)e * (kH * kDout) + (off - kOffW3)] = s;
             else if (off < kOffB1) m.g_b0[(size_t)e * kH + (off - kOffB0)] = s;
             else if (off < kOffB2) m.g_b1[(size_t)e * kH + (off - kOffB1)] = s;
             else if (off < kOffB3) m.g_b2[(size_t)e * kH + (off - kOffB2)] = s;
@@ -563,8 +541,8 @@ __global__ __launch_bounds__(256) void ens_big_reduce_kernel(BigArgs g, float* _
             const int k = int(i - n_big - n_small);
             float s = 0.f;
             for (int ep = 0; ep < E * g.P; ++ep) s += g.partA[(size_t)ep * kPartA + kOffLv + k];
-            if (k < 2) m.g_max_logvar[k] = 0.01f + s;
-            else m.g_min_logvar[k - 2] = -0.01f + s;
+            if (k < 2) m.g_max_logvar[k] = kLogvarReg + s;
+            else m.g_min_logvar[k - 2] = -kLogvarReg + s;
         } else if (loss_out) {
             const int e = int(i - n_big - n_small - 4);
             float s = 0.f;
@@ -607,24 +585,13 @@ long long rrl_ens_big_scratch_floats(int n_nets, long long batch) {
 
 int rrl_ens_train_grad_big(const rrl_ens_t* m, long long batch, const float* train_in, const float* train_targ,
                            const int64_t* idx, long long idx_stride, float* scratch, float* loss_out, void* stream) {
-    if (!m || !train_in || !train_targ || !idx || !scratch || m->n_nets <= 0 || m->n_nets > 60 || batch <= 0)
-        return RRL_EINVAL;
+    if (!m || !train_in || !train_targ || !idx || !scratch || m->n_nets <= 0 || batch <= 0) return RRL_EINVAL;
     if (!rrl_ens_train_big_supported(m->d_in, m->hidden, m->d_out)) return RRL_ERANGE;
-    if (!m->w0 || !m->b0 || !m->w1 || !m->b1 || !m->w2 || !m->b2 || !m->w3 || !m->b3 || !m->max_logvar ||
-        !m->min_logvar || !m->mu || !m->sigma || !m->g_w0 || !m->g_b0 || !m->g_w1 || !m->g_b1 || !m->g_w2 ||
-        !m->g_b2 || !m->g_w3 || !m->g_b3 || !m->g_max_logvar || !m->g_min_logvar)
-        return RRL_EINVAL;
-    static bool lds_set = false;
-    if (!lds_set) {
-        if (hipFuncSetAttribute((const void*)ens_big_fwd_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kLdsBytesA) != hipSuccess ||
-            hipFuncSetAttribute((const void*)ens_big_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kLdsBytesB) != hipSuccess) {
-            rrl_host::last_hip_error = int(hipGetLastError());
-            return RRL_ELAUNCH;
-        }
-        lds_set = true;
-    }
+    if (!desc_complete(m, false)) return RRL_EINVAL;
+    static bool lds_A = false, lds_B = false;
+    int rc = rrl_host::grant_lds(ens_big_fwd_bwd_kernel, kLdsBytesA, lds_A);
+    if (rc == RRL_OK) rc = rrl_host::grant_lds(ens_big_wgrad_kernel, kLdsBytesB, lds_B);
+    if (rc != RRL_OK) return rc;
     BigArgs g;
     g.m = *m;
     g.train_in = train_in;
@@ -657,15 +624,9 @@ int rrl_ens_train_epoch_big(const rrl_ens_t* m, int n_seg, const rrl_adam_seg_t*
                             float eps, const float* train_in, const float* train_targ, const int64_t* idx,
                             long long idx_stride, long long n_rows, long long batch, float* scratch, float* loss_out,
                             void* stream) {
-    if (!idx || n_rows <= 0 || batch <= 0 || !segs) return RRL_EINVAL;
-    for (long long lo = 0; lo < n_rows; lo += batch) {
-        const long long nb = n_rows - lo < batch ? n_rows - lo : batch;
-        int rc = rrl_ens_train_grad_big(m, nb, train_in, train_targ, idx + lo, idx_stride, scratch, loss_out, stream);
-        if (rc != RRL_OK) return rc;
-        rc = rrl_adam_step_multi(n_seg, segs, lr, beta1, beta2, eps, stream);
-        if (rc != RRL_OK) return rc;
-    }
-    return RRL_OK;
+    return train_epoch(n_seg, segs, lr, beta1, beta2, eps, idx, n_rows, batch, stream, [&](long long nb, const int64_t* cols) {
+        return rrl_ens_train_grad_big(m, nb, train_in, train_targ, cols, idx_stride, scratch, loss_out, stream);
+    });
 }
 
 }  // extern "C"

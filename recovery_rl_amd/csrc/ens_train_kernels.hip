@@ -13,29 +13,23 @@
 // logvar 2), batch 32.  Weight layout [net][in][out] (torch.baddbmm(b, x, w)).
 #include <hip/hip_runtime.h>
 
+#include "ens_model.hpp"
 #include "mfma_tile.hpp"
-#include "rrl_host.hpp"
 
 namespace {
 
+using namespace rrl_ens;      // the model, the loss and the host checks: shared with ens_train_big_kernels.hip
 using rrl_host::check_launch;
 using rrl_tile::f32x4;
 using rrl_tile::mfma;
 
-constexpr int kH = 200;          // hidden width
 constexpr int kB = 32;           // batch rows per net
 constexpr int kR = 16;           // rows per workgroup: a member's batch is split over kHalves workgroups (CUs)
 constexpr int kHalves = kB / kR;
-constexpr int kDin = 4, kDout = 4;
 constexpr int kThreads = 1024;
 constexpr int kSmall = 3 * kH + kH * kDout + kDout;   // b0, b1, b2, W3, b3 staged in LDS with the first loads
 constexpr int kLdsFloats = 5 * kR * kH + kR * (kDin + 2 + kDout + kDout) + 16 + kSmall;
 constexpr int kLdsBytes = kLdsFloats * 4;      // 71 KB
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ float softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }   // F.softplus
-__device__ __forceinline__ float softplus_grad(float x) { return x > 20.f ? 1.f : sigm(x); }
-
 constexpr int kColTiles = (kH + 15) / 16;     // 13 (200 = 12.5 x 16: the last tile is half masked)
 
 // The three products of a layer are 16x16x4 f32 MFMA tiles (one ensemble member = one CU: an LDS-fed VALU
@@ -73,9 +67,7 @@ __device__ __forceinline__ void fwd_layer(const float* in, int ld_in, const floa
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int row = 4 * lq + i;
-            const float p = acc0[i] + bj, sg = sigm(p);
-            h_out[row * kH + col] = p * sg;
-            sp[row * kH + col] = sg * (1.f + p * (1.f - sg));      // d swish / d pre
+            swish(acc0[i] + bj, h_out[row * kH + col], sp[row * kH + col]);
         }
     }
 }
@@ -202,14 +194,7 @@ __global__ __launch_bounds__(kThreads) void ens_train_grad_kernel(rrl_ens_t m, c
 #define STAMP() do { } while (0)
 #endif
     STAMP();
-    const float* W0 = m.w0 + (size_t)e * kDin * kH;
-    const float* b0 = m.b0 + (size_t)e * kH;
-    const float* W1 = m.w1 + (size_t)e * kH * kH;
-    const float* b1 = m.b1 + (size_t)e * kH;
-    const float* W2 = m.w2 + (size_t)e * kH * kH;
-    const float* b2 = m.b2 + (size_t)e * kH;
-    const float* W3 = m.w3 + (size_t)e * kH * kDout;
-    const float* b3 = m.b3 + (size_t)e * kDout;
+    const Member me = member_of(m, e);
     float* sp = scratch + (size_t)part * 3 * kR * kH;   // swish' of the three hidden layers (L2-resident)
     // gradient outputs of this half (the Adam kernel adds the halves)
     float* const gw0 = (half ? m.g2_w0 : m.g_w0) + (size_t)e * kDin * kH;
@@ -225,29 +210,27 @@ __global__ __launch_bounds__(kThreads) void ens_train_grad_kernel(rrl_ens_t m, c
     // the small parameters ride in the same round trip as the batch gather
     for (int i = tid; i < kSmall; i += kThreads) {
         float v;
-        if (i < kH) v = b0[i];
-        else if (i < 2 * kH) v = b1[i - kH];
-        else if (i < 3 * kH) v = b2[i - 2 * kH];
-        else if (i < 3 * kH + kH * kDout) v = W3[i - 3 * kH];
-        else v = b3[i - 3 * kH - kH * kDout];
+        if (i < kH) v = me.b0[i];
+        else if (i < 2 * kH) v = me.b1[i - kH];
+        else if (i < 3 * kH) v = me.b2[i - 2 * kH];
+        else if (i < 3 * kH + kH * kDout) v = me.w3[i - 3 * kH];
+        else v = me.b3[i - 3 * kH - kH * kDout];
         bs[i] = v;
     }
     // nb <= 32 rows are real (the last batch of an epoch is shorter); the others contribute zero gradient
     if (tid < kR * kDin) {
         const int rl = tid / kDin, k = tid % kDin, r = half * kR + rl;      // r = row of the member's batch
-        const int64_t row = r < nb ? idx[(size_t)e * idx_stride + r] : 0;
-        xin[tid] = r < nb ? (train_in[row * kDin + k] - m.mu[k]) / m.sigma[k] : 0.f;
-        if (k < 2) yt[rl * 2 + k] = r < nb ? train_targ[row * 2 + k] : 0.f;
+        gather(m, train_in, train_targ, idx + (size_t)e * idx_stride + r, r < nb, k, xin + tid, yt + rl * 2 + k);
     }
     __syncthreads();
     STAMP();
-    fwd_layer<kDin>(xin, kDin, W0, bs, h0, sp, tid);
+    fwd_layer<kDin>(xin, kDin, me.w0, bs, h0, sp, tid);
     __syncthreads();
     STAMP();
-    fwd_layer<kH>(h0, kH, W1, bs + kH, h1, sp + kR * kH, tid);
+    fwd_layer<kH>(h0, kH, me.w1, bs + kH, h1, sp + kR * kH, tid);
     __syncthreads();
     STAMP();
-    fwd_layer<kH>(h1, kH, W2, bs + 2 * kH, h2, sp + 2 * kR * kH, tid);
+    fwd_layer<kH>(h1, kH, me.w2, bs + 2 * kH, h2, sp + 2 * kR * kH, tid);
     __syncthreads();
     STAMP();
     // ---- output layer (4 wide) ----
@@ -263,20 +246,12 @@ __global__ __launch_bounds__(kThreads) void ens_train_grad_kernel(rrl_ens_t m, c
     // ---- loss (MPC.py:276-287) and its gradient w.r.t. the outputs; one thread per (row, dim) ----
     if (tid < 2 * kR) {
         const int r = tid >> 1, k = tid & 1;
-        const float mx = m.max_logvar[k], mn = m.min_logvar[k];
-        const float mean = out[r * kDout + k], lv0 = out[r * kDout + 2 + k];
-        const float a1 = mx - lv0, lv1 = mx - softplus(a1);
-        const float a2 = lv1 - mn, lv2 = mn + softplus(a2);
-        const float inv = expf(-lv2), diff = mean - yt[r * 2 + k];
         const float live = half * kR + r < nb ? 1.f : 0.f;
-        float tl = (diff * diff * inv + lv2) * live;
-        const float scale = live / float(nb * 2);                // mean over the real rows and the two dims
-        const float d_lv2 = (1.f - diff * diff * inv) * scale;
-        const float s2 = softplus_grad(a2), d_lv1 = d_lv2 * s2;
-        const float s1 = softplus_grad(a1);
-        dout[r * kDout + k] = 2.f * diff * inv * scale;
-        dout[r * kDout + 2 + k] = d_lv1 * s1;
-        float d_min = d_lv2 * (1.f - s2), d_max = d_lv1 * (1.f - s1);
+        const NllTerm t = nll(m.max_logvar[k], m.min_logvar[k], out[r * kDout + k], out[r * kDout + 2 + k], yt[r * 2 + k],
+                              live, nb * 2);
+        dout[r * kDout + k] = t.d_mean;
+        dout[r * kDout + 2 + k] = t.d_lv;
+        float tl = t.tl, d_min = t.d_min, d_max = t.d_max;
         // fixed-order reductions over the 16 rows (lanes 0..31 with the same parity)
 #pragma unroll
         for (int off = 2; off < 2 * kR; off <<= 1) {
@@ -325,7 +300,7 @@ __global__ __launch_bounds__(kThreads) void ens_train_grad_kernel(rrl_ens_t m, c
     // ---- hidden layer 2: grads of W2/b2 from (h1, da), then dpre1 -> db ----
     {
         GradInput gi;
-        gi.prefetch(W2, sp + kR * kH, tid);           // the L2 round trip hides behind the weight-gradient tiles
+        gi.prefetch(me.w2, sp + kR * kH, tid);          // the L2 round trip hides behind the weight-gradient tiles
         grad_weights<kH>(h1, kH, da, gw2, gb2, tid);
         gi.compute(da, db, tid);
     }
@@ -334,7 +309,7 @@ __global__ __launch_bounds__(kThreads) void ens_train_grad_kernel(rrl_ens_t m, c
     // ---- hidden layer 1 ----
     {
         GradInput gi;
-        gi.prefetch(W1, sp, tid);
+        gi.prefetch(me.w1, sp, tid);
         grad_weights<kH>(h0, kH, db, gw1, gb1, tid);
         gi.compute(db, da, tid);
     }
@@ -356,8 +331,8 @@ __global__ void ens_logvar_grad_kernel(int n_nets, const float* __restrict__ par
     if (k < 4) {
         float s = 0.f;
         for (int p = 0; p < n_nets * kHalves; ++p) s += part[p * 4 + k];
-        if (k < 2) g_max[k] = 0.01f + s;
-        else g_min[k - 2] = -0.01f + s;
+        if (k < 2) g_max[k] = kLogvarReg + s;
+        else g_min[k - 2] = -kLogvarReg + s;
     } else if (loss_out && k - 4 < n_nets) {
         const int e = k - 4;
         float s = 0.f;
@@ -380,21 +355,10 @@ int rrl_ens_train_grad(const rrl_ens_t* m, int batch, const float* train_in, con
                        const int64_t* idx, long long idx_stride, float* scratch, float* loss_out, void* stream) {
     if (!m || !train_in || !train_targ || !idx || !scratch || m->n_nets <= 0) return RRL_EINVAL;
     if (!rrl_ens_train_supported(m->d_in, m->hidden, m->d_out, batch)) return RRL_ERANGE;
-    if (!m->w0 || !m->b0 || !m->w1 || !m->b1 || !m->w2 || !m->b2 || !m->w3 || !m->b3 || !m->max_logvar ||
-        !m->min_logvar || !m->mu || !m->sigma || !m->g_w0 || !m->g_b0 || !m->g_w1 || !m->g_b1 || !m->g_w2 ||
-        !m->g_b2 || !m->g_w3 || !m->g_b3 || !m->g2_w0 || !m->g2_b0 || !m->g2_w1 || !m->g2_b1 || !m->g2_w2 || !m->g2_b2 ||
-        !m->g2_w3 || !m->g2_b3 || !m->g_max_logvar || !m->g_min_logvar || !m->g_logvar_part || !m->loss_part ||
-        m->n_nets > 60)
-        return RRL_EINVAL;
+    if (!desc_complete(m, true)) return RRL_EINVAL;
     static bool lds_set = false;
-    if (!lds_set) {
-        if (hipFuncSetAttribute((const void*)ens_train_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kLdsBytes) != hipSuccess) {
-            rrl_host::last_hip_error = int(hipGetLastError());
-            return RRL_ELAUNCH;
-        }
-        lds_set = true;
-    }
+    const int rc = rrl_host::grant_lds(ens_train_grad_kernel, kLdsBytes, lds_set);
+    if (rc != RRL_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(ens_train_grad_kernel, dim3(m->n_nets * kHalves), dim3(kThreads), kLdsBytes, st, *m, train_in, train_targ,
                        idx, idx_stride, batch, scratch, loss_out);
@@ -403,22 +367,14 @@ int rrl_ens_train_grad(const rrl_ens_t* m, int batch, const float* train_in, con
     return check_launch();
 }
 
-// One epoch of MPC.train's batch loop (MPC.py:266-292) issued from C: ceil(n_rows / batch) x {gradient kernel,
-// logvar reduction, Adam}.  Launching from a C loop costs ~4 us per launch on the host instead of ~20 us through
-// Python, which keeps the 35-us optimiser step GPU-bound.
+// One epoch of MPC.train's batch loop issued from C: ceil(n_rows / batch) x {gradient kernel, logvar reduction, Adam}
 int rrl_ens_train_epoch(const rrl_ens_t* m, int n_seg, const rrl_adam_seg_t* segs, float lr, float beta1, float beta2,
                         float eps, const float* train_in, const float* train_targ, const int64_t* idx,
                         long long idx_stride, long long n_rows, int batch, float* scratch, float* loss_out,
                         void* stream) {
-    if (!idx || n_rows <= 0 || batch <= 0 || !segs) return RRL_EINVAL;
-    for (long long lo = 0; lo < n_rows; lo += batch) {
-        const int nb = int(n_rows - lo < batch ? n_rows - lo : batch);
-        int rc = rrl_ens_train_grad(m, nb, train_in, train_targ, idx + lo, idx_stride, scratch, loss_out, stream);
-        if (rc != RRL_OK) return rc;
-        rc = rrl_adam_step_multi(n_seg, segs, lr, beta1, beta2, eps, stream);
-        if (rc != RRL_OK) return rc;
-    }
-    return RRL_OK;
+    return train_epoch(n_seg, segs, lr, beta1, beta2, eps, idx, n_rows, batch, stream, [&](int nb, const int64_t* cols) {
+        return rrl_ens_train_grad(m, nb, train_in, train_targ, cols, idx_stride, scratch, loss_out, stream);
+    });
 }
 
 }  // extern "C"

@@ -35,22 +35,26 @@ class FusedEnsembleTrainer:
         self.loss_part = torch.zeros(2 * self.E, device=dev)
         self.scratch = torch.empty(int(self.lib.rrl_ens_scratch_floats(self.E)), device=dev)
         self.loss = torch.zeros(self.E, device=dev)
-        self._segs = (_lib.rrl_adam_seg_t * len(self.params))()
-        for k, p in enumerate(self.params):
-            self._segs[k] = _lib.rrl_adam_seg_t(p.numel(), p.data_ptr(), self.grads[k].data_ptr(), self.m[k].data_ptr(),
-                                                self.v[k].data_ptr(), self.steps[k].data_ptr(), None, 0.0,
-                                                DECAY.get(PARAMS[k], 0.0),
-                                                self.grads2[k].data_ptr() if k < 8 else None)
-
-        # large-batch path (rrl_ens_train_grad_big): gradients land in self.grads only
-        self._segs_big = (_lib.rrl_adam_seg_t * len(self.params))()
-        for k, p in enumerate(self.params):
-            self._segs_big[k] = _lib.rrl_adam_seg_t(p.numel(), p.data_ptr(), self.grads[k].data_ptr(),
-                                                    self.m[k].data_ptr(), self.v[k].data_ptr(), self.steps[k].data_ptr(),
-                                                    None, 0.0, DECAY.get(PARAMS[k], 0.0), None)
+        self._segs = self._segments(True)
+        self._segs_big = self._segments(False)      # rrl_ens_train_grad_big: gradients land in self.grads only
         self._scratch_big = None
 
     SMALL_BATCH = 32
+
+    def _segments(self, with_second_halves):
+        """Adam's view of the ten parameters; with_second_halves: g + g2 for the eight weights and biases."""
+        segs = (_lib.rrl_adam_seg_t * len(self.params))()
+        for k, p in enumerate(self.params):
+            g2 = self.grads2[k].data_ptr() if with_second_halves and k < 8 else None
+            segs[k] = _lib.rrl_adam_seg_t(p.numel(), p.data_ptr(), self.grads[k].data_ptr(), self.m[k].data_ptr(),
+                                          self.v[k].data_ptr(), self.steps[k].data_ptr(), None, 0.0,
+                                          DECAY.get(PARAMS[k], 0.0), g2)
+        return segs
+
+    def _adam(self, segs):
+        rc = self.lib.rrl_adam_step_multi(len(self.params), segs, self.lr, self.betas[0], self.betas[1], self.eps,
+                                          _lib.current_stream())
+        _lib.check(rc, "rrl_adam_step_multi")
 
     @staticmethod
     def supported(model, batch_size):
@@ -91,9 +95,7 @@ class FusedEnsembleTrainer:
 
     def step(self, idx):
         self.gradients(idx)
-        rc = self.lib.rrl_adam_step_multi(len(self.params), self._segs, self.lr, self.betas[0], self.betas[1],
-                                          self.eps, _lib.current_stream())
-        _lib.check(rc, "rrl_adam_step_multi")
+        self._adam(self._segs)
 
     def _big_scratch(self, batch):
         need = int(self.lib.rrl_ens_big_scratch_floats(self.E, int(batch)))
@@ -114,9 +116,7 @@ class FusedEnsembleTrainer:
 
     def step_big(self, idx):
         self.gradients_big(idx)
-        rc = self.lib.rrl_adam_step_multi(len(self.params), self._segs_big, self.lr, self.betas[0], self.betas[1],
-                                          self.eps, _lib.current_stream())
-        _lib.check(rc, "rrl_adam_step_multi")
+        self._adam(self._segs_big)
 
     def epoch(self, idxs, batch_size):
         """All ceil(n / batch_size) steps over the columns of idxs [E, n], launched from one C loop."""

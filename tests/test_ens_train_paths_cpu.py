@@ -1,6 +1,6 @@
 """The case table of ens_train_cases.py reaches every launch edge of the PETS ensemble training kernels -- proven on the host from
-the constants and the bodies of parts_A / parts_B parsed out of csrc/ens_train_kernels.hip and csrc/ens_train_big_kernels.hip, so
-that a retuned constant fails here instead of moving a case of test_ens_train_paths_gpu.py off its edge unnoticed --, its
+the constants and the bodies of parts_A / parts_B parsed out of csrc/ens_train_kernels.hip, csrc/ens_train_big_kernels.hip and the
+csrc/ens_model.hpp they share, so that a retuned constant fails here instead of moving a case of test_ens_train_paths_gpu.py off its edge unnoticed --, its
 restatement is PtModel's forward with MPC.train's loss, every operand kind reaches its regime, the f32 restatement stays inside
 CAP, and rule 1 catches a kernel that is wrong in the ways of ens_train_cases.MUTATIONS."""
 import os
@@ -34,15 +34,19 @@ def _body(name, text):
 
 # ---- the restatement is the sources' ------------------------------------------------------------------------------------------
 def test_the_restated_constants_are_the_sources():
-    small, big = _src("ens_train_kernels.hip"), _src("ens_train_big_kernels.hip")
-    got = dict(kH=_const("kH", small), kB=_const("kB", small), kR=_const("kR", small), kRbig=_const("kR", big),
+    small, big, model = _src("ens_train_kernels.hip"), _src("ens_train_big_kernels.hip"), _src("ens_model.hpp")
+    got = dict(kH=_const("kH", model), kB=_const("kB", small), kR=_const("kR", small), kRbig=_const("kR", big),
                kGB=_const("kGB", big), kMaxP=_const("kMaxP", big), kMaxQ=_const("kMaxQ", big), kPartA=_const("kPartA", big))
-    assert _const("kH", big) == got["kH"]
+    # one width for both files: the header's, and neither states a model constant of its own
+    for text in (small, big):
+        assert '#include "ens_model.hpp"' in text and "using namespace rrl_ens;" in text
+        assert not re.search(r"constexpr\s+\w+\s[^;]*\b(kH|kDin|kDout|kMaxNets|kLogvarReg)\s*=", text)
     assert "constexpr int kHalves = kB / kR;" in small
     got["kHalves"] = got["kB"] // got["kR"]
-    nets = re.findall(r"n_nets > (\d+)", small + big)
-    assert len(nets) == 2 and len(set(nets)) == 1                   # one limit in each entry
-    got["max_nets"] = int(nets[0])
+    # one limit, in the check both entries call
+    assert [x for x in re.findall(r"n_nets (?:>|<=) (\w+)", small + big + model) if x != "0"] == ["kMaxNets"]
+    assert "if (!desc_complete(m, true)) return RRL_EINVAL;" in small and "if (!desc_complete(m, false)) return RRL_EINVAL;" in big
+    got["max_nets"] = _const("kMaxNets", model)
     assert _body("parts_A", big) == ["long long tiles = rows_pad / kR;", "long long want = 256 / (E > 0 ? E : 1);",
                                      "if (want < 1) want = 1;", "long long P = tiles < want ? tiles : want;",
                                      "return int(P > kMaxP ? kMaxP : P);"]
@@ -50,8 +54,10 @@ def test_the_restated_constants_are_the_sources():
                                      "if (want < 1) want = 1;", "long long Q = groups < want ? groups : want;",
                                      "return int(Q > kMaxQ ? kMaxQ : Q);"]
     got["wish"] = 256
-    m = re.search(r"const long long n_small = \(long long\)E \* (\d+);", big)
-    got["small_total"] = int(m.group(1))
+    m = re.search(r"const long long n_small = \(long long\)E \* (\w+);", big)
+    assert m.group(1) == "kOffLv" and "const int e = int(j / kOffLv), off = int(j % kOffLv);" in big
+    assert "kOffLv = kOffB3 + kDout," in big
+    got["small_total"] = _const("kOffB3", big) + _const("kDout", model)
     m = re.search(r"hipLaunchKernelGGL\(ens_big_reduce_kernel, dim3\((\d+)\), dim3\((\d+)\), 0, st, g, loss_out\);", big)
     got["reduce_grid"], got["reduce_block"] = int(m.group(1)), int(m.group(2))
     assert got == EC.CONSTANTS
@@ -61,7 +67,7 @@ def test_the_restated_constants_are_the_sources():
         got["kPartA"], got["wish"], got["small_total"], got["reduce_grid"] * got["reduce_block"])
     # the index arithmetic and the sizes launch_facts() restates
     for line in ("const int e = blockIdx.x / kHalves, half = blockIdx.x % kHalves, tid = threadIdx.x;",
-                 "const float live = half * kR + r < nb ? 1.f : 0.f;", "const float scale = live / float(nb * 2);",
+                 "const float live = half * kR + r < nb ? 1.f : 0.f;", "live, nb * 2);",       # nll's live and n2
                  "long long rrl_ens_scratch_floats(int n_nets) { return (long long)n_nets * kHalves * 3 * kR * kH + 64; }",
                  "return d_in == kDin && hidden == kH && d_out == kDout && batch >= 1 && batch <= kB;",
                  "hipLaunchKernelGGL(ens_logvar_grad_kernel, dim3(1), dim3(64), 0, st,",
@@ -71,7 +77,7 @@ def test_the_restated_constants_are_the_sources():
                  "for (long long tile = p; tile < n_tiles; tile += g.P) {", "const long long n_tiles = g.rows_pad / kR;",
                  "const long long groups = g.rows_pad / kGB;",
                  "const long long g_lo = groups * q / g.Q, g_hi = groups * (q + 1) / g.Q;",
-                 "const float scale = live / float(g.nb * 2);", "const long long n_big = 2LL * E * kH * kH;",
+                 "const float live = row0 + r < g.nb ? 1.f : 0.f;", "live, g.nb * 2);", "const long long n_big = 2LL * E * kH * kH;",
                  "const long long total = n_big + n_small + 4 + E;",
                  "for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {",
                  "return 6LL * n_nets * rp * kH + (long long)n_nets * parts_A(rp, n_nets) * kPartA +",
@@ -81,10 +87,13 @@ def test_the_restated_constants_are_the_sources():
         assert line in big, line
     # the 64 threads of ens_logvar_grad_kernel: 4 bound sums + one loss per member
     assert 4 + got["max_nets"] == 64
-    # F.softplus's threshold and the +-0.01 of the bound gradients, in both files
+    # the mean over the real rows and the two dims, F.softplus's threshold and the +-0.01 of the bound gradients: stated once,
+    # in the header, and used by both files
+    assert "const float scale = live / float(n2);" in model and "constexpr float kLogvarReg = 0.01f;" in model
+    assert "return x > 20.f ? x : log1pf(expf(x));" in model and "return x > 20.f ? 1.f : sigm(x);" in model
     for text in (small, big):
-        assert "return x > 20.f ? x : log1pf(expf(x));" in text and "return x > 20.f ? 1.f : sigm(x);" in text
-        assert "= 0.01f + s;" in text and "= -0.01f + s;" in text
+        assert "const NllTerm t = nll(" in text and "log1pf(" not in text and "softplus(" not in text
+        assert "= kLogvarReg + s;" in text and "= -kLogvarReg + s;" in text and "0.01f" not in text
 
 
 def test_launch_facts_on_shapes_counted_by_hand():
